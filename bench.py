@@ -2,7 +2,15 @@
 """bench.py -- headline benchmark of the hot path (BASELINE.json metric):
 SA build chars/s (N = 1e9) + batched queries/s (Q = 1e6) on one MI355X, % of HBM roofline.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--chars CHARS] [--queries QUERIES]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--chars CHARS] [--queries QUERIES] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the line: `value`, `ms_per_step` (wall clock of one timed step) and
+the figures derived from the timed steps' own statistics.  --full adds everything that takes work of its own, after the
+timed steps: the correctness gates (on-device sufcheck, query hit rate), the query sub-populations, the CPU baseline
+(--no-cpu-baseline to skip) and the secondary configurations (--no-secondary, --no-words-1e9, --no-beyond-u32).
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float64, exact for these
+integers; 64 MB at most, larger outputs as a fixed, seeded sample): the same arguments give the same inputs, so two
+builds can be compared output for output.
 
 N = 1 (BASELINE config 3: "1 GB text (libsais64 path), 64-bit SA build + 1M batched 16-byte queries"):
 a "step" = one device build of the suffix array of the N-char synthetic text D1 (uniform27; text
@@ -389,7 +397,13 @@ def main():
     ap.add_argument("--dump", default=None, help="config 4: write the gathered ranges (+ the SA for N <= 1e8) to this .npz (tests)")
     ap.add_argument("--exercise-dist", action="store_true",
                     help="run the multi-GPU path (RCCL init, index broadcast, sharded batch, all-gather) at world size 1")
+    ap.add_argument("--full", action="store_true",
+                    help="1 GPU: after the timed steps also the gates, query sub-populations, CPU baseline and secondary configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -412,6 +426,47 @@ def main():
         dist.destroy_process_group()
         return
     print(json.dumps(run_single(args, torch, _capi, synth, dev, local_rank)))
+
+
+def _dump_sample(count, limit, seed):
+    """None (all of 0..count-1) when count <= limit, else a fixed, seeded, sorted sample of at most `limit` of them."""
+    if count <= limit:
+        return None
+    return np.unique(np.random.default_rng(seed).integers(0, count, limit))
+
+
+def dump_outputs(path, torch, sa64=None, ranges=None, row_ids=None, row_counts=None):
+    """--dump-outputs: what the timed path returned in its last step, as float64 .npy files (exact: every value is an
+    integer below 2^53), 53 MB at most.  sa64 (int64[N] device tensor): 2^20 slots at fixed, seeded positions
+    (sa64_sample_pos, sa64_sample).  ranges (Q (first, second) pairs, uint32): query_ranges [Q, 2]; row_ids / row_counts
+    (--dist-mode sharded_rows): the distinct row ids of each query, slots beyond its count as -1.  Batches too large for
+    the budget are sampled the same way (query_sample_index)."""
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    if sa64 is not None:
+        n = sa64.numel()
+        pos = _dump_sample(n, 1 << 20, seed=1)
+        pos = np.arange(n, dtype=np.int64) if pos is None else pos
+        save("sa64_sample_pos", pos)
+        save("sa64_sample", sa64.index_select(0, torch.from_numpy(pos).to(sa64.device)).cpu().numpy())
+    if ranges is None:
+        return
+    ranges = np.asarray(ranges, dtype=np.uint32).reshape(-1, 2)
+    per_query = 2 + (1 + row_ids.shape[1] if row_ids is not None else 0) + 1   # + 1: the sample index
+    sel = _dump_sample(ranges.shape[0], 36_000_000 // (8 * per_query), seed=2)
+    pick = (lambda a: a) if sel is None else (lambda a: a[sel])
+    if sel is not None:
+        save("query_sample_index", sel)
+    save("query_ranges", pick(ranges))
+    if row_ids is not None:
+        counts = pick(np.asarray(row_counts))
+        ids = pick(row_ids).astype(np.float64)
+        ids[np.arange(ids.shape[1])[None, :] >= counts[:, None]] = -1.0
+        save("row_counts", counts)
+        save("row_ids", ids)
 
 
 def run_single(args, torch, _capi, synth, dev, device):
@@ -463,15 +518,8 @@ def run_single(args, torch, _capi, synth, dev, device):
     dt = time.perf_counter() - t0
     last = idx.build_stats()
     steps = args.steps
-
-    # correctness gates, outside the timed region: on-device sufcheck of the last step's SA (the SA is unique:
-    # verified == bit-exact), and -- with the CPU baseline -- equality with the reference's libsais64 output
-    res = out_t.cpu().numpy().view(np.uint32).reshape(-1, 2)
-    hits = ((res[:, 1].astype(np.int64) - res[:, 0].astype(np.int64) + 1) & 0xFFFFFFFF) > 0
-    hits &= res[:, 0] != 0xFFFFFFFF
-    violations = idx.verify()
-    gate = {"verify_violations": violations, "query_hit_rate": float(hits.mean())}
-    populations = query_populations(idx, synth, torch, dev, text, Q, m)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, sa64=sa64_t, ranges=out_t.cpu().numpy().view(np.uint32))
 
     total_ms = build_ms + widen_ms
     chars_per_s = N * steps / (total_ms / 1e3)
@@ -558,8 +606,6 @@ def run_single(args, torch, _capi, synth, dev, device):
                   {"fused": False, "bytes_per_launch": 12.0 * N, "avg_launch_ms": widen_ms / steps,
                    "achieved": 12.0 * N * steps / (widen_ms / 1e3) / 1e9 if widen_ms > 0 else None, "unit": "GB/s"}),
         "roofline_query": rq,
-        "query_populations": populations,
-        "gate": gate,
     }
     if last.get("narrow_k") and last.get("text_top_pass") and last.get("rounds") == 0:
         # the whole build with its own bytes / time: the sort passes as accounted above + per character
@@ -573,6 +619,20 @@ def run_single(args, torch, _capi, synth, dev, device):
         total_bytes = radix_bytes + other * N * steps
         line["whole_build"] = {"bytes_per_char_model": total_bytes / (N * steps), "achieved": total_bytes / (total_ms / 1e3) / 1e9,
                                "unit": "GB/s", "frac": total_bytes / (total_ms / 1e3) / HBM_PEAK}
+    if not args.full:
+        del sa64_t
+        idx.close()
+        return line
+
+    # --full.  Correctness gates, outside the timed region: on-device sufcheck of the last step's SA (the SA is unique:
+    # verified == bit-exact), and -- with the CPU baseline -- equality with the reference's libsais64 output
+    res = out_t.cpu().numpy().view(np.uint32).reshape(-1, 2)
+    hits = ((res[:, 1].astype(np.int64) - res[:, 0].astype(np.int64) + 1) & 0xFFFFFFFF) > 0
+    hits &= res[:, 0] != 0xFFFFFFFF
+    violations = idx.verify()
+    gate = {"verify_violations": violations, "query_hit_rate": float(hits.mean())}
+    line["query_populations"] = query_populations(idx, synth, torch, dev, text, Q, m)
+    line["gate"] = gate
     gpu_sa64 = sa64_t.cpu().numpy() if not (args.no_cpu_baseline and args.no_secondary) else None
     del sa64_t
     if not args.no_cpu_baseline:
@@ -826,6 +886,8 @@ def run_sharded(args, torch, dist, _capi, synth, rank, local_rank, world, dev):
                    "search_kernel_ms": idx.query_stats()["kernel_ms_sum"] / args.steps,
                    "note": "the whole batch on rank 0's GPU alone, ranges left in HBM (no gather): the 1-GPU reference for `value`"}
         del pat_all, off_all, out_all
+        if args.dump_outputs:   # the gathered table of the last step, as rank 0 received it
+            dump_outputs(args.dump_outputs, torch, ranges=np.stack([got["first"], got["second"]], axis=1))
         if args.dump:   # tests/test_gpu_dist.py: the gathered ranges and the suffix array, to be checked against the oracle
             np.savez(args.dump, first=got["first"], second=got["second"], sa=idx.sa_u32() if N <= 100_000_000 else np.zeros(0, np.uint32))
     steps = args.steps
@@ -920,6 +982,9 @@ def run_sharded_rows(args, torch, dist, synth, rank, world, dev, text, idx, sear
         gate = {"sharded_equals_single_gpu": same, "verify_violations": idx.verify(), "rows_found": int(totals[1]),
                 "queries_with_rows": int(totals[2])}
         gate["ok"] = bool(same and gate["verify_violations"] == 0)
+        if args.dump_outputs:   # rank 0's slice of the last step: ranges, row counts, row ids
+            dump_outputs(args.dump_outputs, torch, ranges=np.stack([ranges["first"], ranges["second"]], axis=1),
+                         row_ids=rows[0][:ql], row_counts=rows[1][:ql])
         line = {
             "metric": "batched_queries_per_s", "value": Qg * args.steps / dt, "unit": "queries/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt * 1e3 / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,

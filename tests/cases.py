@@ -36,6 +36,27 @@ def small_texts():
     return c
 
 
+def reference_query_cases():
+    """(alphabet size, text, patterns) of the oracle-against-the-reference query test: 100 000 characters with 4 % newlines,
+    1500 patterns of 1..40 bytes, half of them text windows.  Their reference ranges are in tests/golden/golden_ref_cases.npz."""
+    rng = np.random.default_rng(11)
+    out = []
+    for sig in (26, 4, 2):
+        n = 100_000
+        t = (rng.integers(0, sig, n) + 97).astype(np.uint8)
+        t[rng.random(n) < 0.04] = 10
+        pats = []
+        for i in range(1500):
+            m = int(rng.integers(1, 41))
+            if i % 2 == 0:
+                p = int(rng.integers(0, n - m))
+                pats.append(bytes(t[p:p + m]).replace(b"\n", b"a"))
+            else:
+                pats.append(bytes((rng.integers(0, sig, m) + 97).astype(np.uint8)))
+        out.append((sig, t, pats))
+    return out
+
+
 def query_patterns(text, count, rng, maxlen=40):
     n = text.size
     pats = []

@@ -10,6 +10,8 @@ outputs of the reference itself on inputs chosen per SURVEY.md 8(c):
                      (get_substring_positions on the libsais SA, L = 32) and the same ranges on the
                      reference's own truncated SA (construct_truncated_suffix_array, L = 32)
   golden_csv.npz     CSV mode through the reference's C functions (csv_golden below): hit counts and returned row ids
+  golden_ref_cases.npz  the reference on tests/cases.py's parity inputs (ref_cases_golden below): sha256 of its suffix
+                     arrays, get_substring_positions ranges (python tests/golden/make_golden.py --ref-cases-only)
 """
 import hashlib
 import os
@@ -253,7 +255,45 @@ def csv_golden():
     print("golden_csv.npz", os.path.getsize(os.path.join(OUT, "golden_csv.npz")))
 
 
+# ---- the reference on the parity cases (tests/cases.py) ----------------------------------------------------------------
+def ref_cases_golden():
+    """golden_ref_cases.npz: what tests/test_oracle.py compares the oracle with, so that it needs no compiled reference.
+    Per text of cases.small_texts(): sha256 of the text and of the reference's suffix array from libsais (1 thread),
+    libsais_omp (4 threads) and libsais64_omp (2 threads).  Per alphabet of the query test: sha256 of the text and
+    get_substring_positions (L = 32) for its 1500 patterns over the oracle's suffix array."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cases
+    from oracle.oracle import Oracle
+    ref, orc = Ref(), Oracle()
+    sha = lambda a: np.array([hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()])
+    arrays, names = {}, []
+    for name, t in cases.small_texts().items():
+        if t.size < 1:
+            continue
+        names.append(name)
+        arrays[f"text_sha256__{name}"] = sha(t)
+        arrays[f"libsais_sha256__{name}"] = sha(ref.libsais(t, threads=1).astype("<i4"))
+        arrays[f"libsais_omp4_sha256__{name}"] = sha(ref.libsais(t, threads=4).astype("<i4"))
+        if t.size > 1:
+            arrays[f"libsais64_omp2_sha256__{name}"] = sha(ref.libsais64(t, threads=2).astype("<i8"))
+    arrays["names"] = np.array(names)
+    for sig, t, pats in cases.reference_query_cases():
+        sa = orc.sais(t).astype(np.uint32)
+        tn = np.concatenate([t, np.zeros(64, np.uint8)])
+        rr = np.zeros(len(pats), dtype=PAIR)
+        for i, p in enumerate(pats):
+            rr[i] = ref.query(tn, sa, 32, p)
+        arrays[f"query_text_sha256__{sig}"] = sha(t)
+        arrays[f"query_ranges__{sig}"] = rr
+    np.savez_compressed(os.path.join(OUT, "golden_ref_cases.npz"), **arrays)
+    print("golden_ref_cases.npz", os.path.getsize(os.path.join(OUT, "golden_ref_cases.npz")))
+
+
 if __name__ == "__main__":
+    if "--ref-cases-only" in sys.argv:
+        ref_cases_golden()
+        sys.exit(0)
     if "--csv-only" not in sys.argv:
         main()
     csv_golden()
+    ref_cases_golden()

@@ -80,35 +80,52 @@ def test_truncated_contract(oracle):
             check_truncated_order(t, oracle.truncated_sa(t, L), L)
 
 
-def test_oracle_vs_reference_build(oracle, ref):
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def _live_ref():
+    """The reference itself where oracle/_ref is built; the stored outputs in golden_ref_cases.npz are checked either way."""
+    from oracle.oracle import Ref
+    return Ref() if Ref.available() else None
+
+
+def test_oracle_vs_reference_build(oracle):
+    g = _load("golden_ref_cases.npz")
+    ref = _live_ref()
+    names = [name for name, t in cases.small_texts().items() if t.size >= 1]
+    assert names == list(g["names"])
     for name, t in cases.small_texts().items():
         if t.size < 1:
             continue
-        assert np.array_equal(oracle.sais(t), ref.libsais(t, threads=1)), name
-        assert np.array_equal(oracle.sais(t), ref.libsais(t, threads=4)), name
+        assert _sha(t) == str(g[f"text_sha256__{name}"][0]), name   # the input the reference saw
+        sa = oracle.sais(t)
+        assert _sha(sa.astype("<i4")) == str(g[f"libsais_sha256__{name}"][0]), name
+        assert _sha(sa.astype("<i4")) == str(g[f"libsais_omp4_sha256__{name}"][0]), name
         if t.size > 1:
-            assert np.array_equal(oracle.sais64(t), ref.libsais64(t, threads=2)), name
+            assert _sha(oracle.sais64(t).astype("<i8")) == str(g[f"libsais64_omp2_sha256__{name}"][0]), name
+        if ref is not None:
+            assert np.array_equal(sa, ref.libsais(t, threads=1)), name
+            assert np.array_equal(sa, ref.libsais(t, threads=4)), name
+            if t.size > 1:
+                assert np.array_equal(oracle.sais64(t), ref.libsais64(t, threads=2)), name
 
 
-def test_oracle_vs_reference_query(oracle, ref):
-    rng = np.random.default_rng(11)
-    for sig in (26, 4, 2):
-        n = 100_000
-        t = (rng.integers(0, sig, n) + 97).astype(np.uint8)
-        t[rng.random(n) < 0.04] = 10
+def test_oracle_vs_reference_query(oracle):
+    g = _load("golden_ref_cases.npz")
+    ref = _live_ref()
+    for sig, t, pats in cases.reference_query_cases():
+        assert _sha(t) == str(g[f"query_text_sha256__{sig}"][0]), sig
         sa = oracle.sais(t).astype(np.uint32)
-        tn = np.concatenate([t, np.zeros(64, np.uint8)])
-        pats = []
-        for i in range(1500):
-            m = int(rng.integers(1, 41))
-            if i % 2 == 0:
-                p = int(rng.integers(0, n - m))
-                pats.append(bytes(t[p:p + m]).replace(b"\n", b"a"))
-            else:
-                pats.append(bytes((rng.integers(0, sig, m) + 97).astype(np.uint8)))
         got = oracle.query_batch(t, sa, 32, pats)
-        for q, g in zip(pats, got):
-            assert tuple(g) == ref.query(tn, sa, 32, q), q
+        exp = g[f"query_ranges__{sig}"]
+        assert exp.size == len(pats) == got.size
+        for q, a, e in zip(pats, got, exp):
+            assert tuple(a) == tuple(e), q
+        if ref is not None:
+            tn = np.concatenate([t, np.zeros(64, np.uint8)])
+            for q, a in zip(pats, got):
+                assert tuple(a) == ref.query(tn, sa, 32, q), q
 
 
 def test_query_edge_conventions(oracle):

@@ -26,7 +26,7 @@ KEEP = ("onesweep", "text_top_pass", "query_kernel", "flags_kernel", "seg_hist",
 
 
 def counter_file(tag, what):
-    g = glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc_{tag}_{what}", "*", "*_counter_collection.csv"))
+    g = glob.glob(os.path.join(ROOT, os.environ.get("PROFILE_OUT", "profile_out"), f"pmc_{tag}_{what}", "*", "*_counter_collection.csv"))
     return g[0] if g else None
 
 
@@ -57,7 +57,7 @@ def main():
     fetch, write, raw = rows(counter_file(tag, "fetch")), rows(counter_file(tag, "write")), rows(counter_file(tag, "raw"))
     for what, data in (("fetch", fetch), ("write", write), ("raw", raw)):
         keep_csv(tag, what, data)
-    light = "--no-cpu-baseline --no-secondary"
+    light = "--full --no-cpu-baseline --no-secondary"
     cmds = [f"rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python3 bench.py --steps 1 --warmup 0 {light}",
             f"rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -- python3 bench.py --steps 1 --warmup 0 {light}"]
 
@@ -97,7 +97,7 @@ def main():
         print(json.dumps(j, indent=1))
 
     # ---- query kernel: one launch per bench step -------------------------------------------------------------------
-    # launches of query_kernel in `bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-secondary`, in order: [0] the timed batch
+    # launches of query_kernel in `bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-secondary`, in order: [0] the timed batch
     # (what the line's rate belongs to), [1] the 8Q classification batch of query_populations, [2..7] six launches of the
     # hits-only batch, [8..13] six of the misses-only batch (round 4; before that the batch was the only / last launch)
     qf = [v for _, k, g, c, v in fetch if c == "FETCH_SIZE" and "query_kernel" in k]
@@ -169,7 +169,7 @@ def main():
                 a[c] = a.get(c, 0.0) + v
         lines = [f"# Instruction counters of a D1 build at N = {n_chars:,} ({tag})", "",
                  "`rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAVES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --kernel-trace",
-                 "--output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-secondary`; per launch, launches over the whole input.",
+                 "--output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-secondary`; per launch, launches over the whole input.",
                  "SQ_ACTIVE_INST_* and SQ_WAVE_CYCLES count quad-cycles (MI355X_MICROARCH.md); busy = active cycles of the unit / (GRBM_GUI_ACTIVE / 8 XCDs x 4 SIMDs x 256 CUs / 8).", "",
                  "| kernel | launches | waves | VALU instr / wave | LDS instr / wave | VALU active (quad-cycles) / wave | LDS active / wave | wave cycles / wave |",
                  "|---|---|---|---|---|---|---|---|"]
