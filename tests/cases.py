@@ -137,3 +137,164 @@ def check_partitioned_csv(SuffixArray, tmp_path):
     assert ids(back.query_records("stark", k=10**6)) == sorted(int(r[0]) for r in rows if "stark" in r[1].lower())
     for x in (one, part, back):
         x.close()
+
+
+# -- alphabets of every code width ---------------------------------------------------------------------------------------------
+# The build packs every byte into a code of b = bits_for(sigma + 1) bits (code 0 stays free), and b picks the key length and
+# with it the sort plan.  These sigmas put every b from 1 to 9 at both of its ends: 2^(b-1) and the all-ones 2^b - 1.
+ALPHABET_SIGMAS = (1, 2, 3, 4, 7, 8, 15, 16, 31, 32, 63, 64, 127, 128, 255, 256)
+_VARIANTS = ("mid", "lo", "hi", "ends")
+
+
+def code_bits(sigma):
+    """b of an alphabet of sigma bytes: the smallest b with 2^b >= sigma + 1 (csrc/common.hpp: bits_for)."""
+    return max(1, int(sigma).bit_length())
+
+
+def alphabet(sigma, variant):
+    """sigma distinct byte values, evenly spaced so that absent ("gap") bytes lie between present ones wherever sigma < 256.
+    variant: "mid" holds neither byte 0 nor byte 255, "lo" holds byte 0, "hi" holds byte 255, "ends" holds both."""
+    lo = 0 if variant in ("lo", "ends") else 1
+    hi = 255 if variant in ("hi", "ends") else 254
+    if sigma > hi - lo + 1:
+        raise ValueError("alphabet %d does not fit variant %s" % (sigma, variant))
+    if sigma == 1:
+        return np.array([hi if variant == "hi" else lo], dtype=np.uint8)
+    vals = np.round(np.linspace(lo, hi, sigma)).astype(np.int64)
+    assert np.unique(vals).size == sigma
+    return vals.astype(np.uint8)
+
+
+def alphabet_cases():
+    """(id, sigma, variant) of the sweep: the variants rotate through the sigmas; 255 bytes are spaced only with both ends."""
+    out = []
+    for i, s in enumerate(ALPHABET_SIGMAS):
+        v = "ends" if s >= 255 else _VARIANTS[i % 4]
+        out.append(("s%d_b%d" % (s, code_bits(s)), s, v))
+    return out
+
+
+def gap_bytes(alph):
+    """absent bytes strictly between the smallest and the largest present one"""
+    present = np.zeros(256, bool)
+    present[alph] = True
+    return np.flatnonzero(~present[int(alph.min()):int(alph.max()) + 1]) + int(alph.min())
+
+
+def alphabet_text(alph, n, kind, seed):
+    """n bytes over exactly the bytes of alph (every one occurs).
+    kind "uniform": i.i.d. uniform.  kind "binary": binary-like -- Zipf weights (the smallest byte the most frequent, the
+    others in a random order of rank) and runs of the smallest byte (byte 0 where the alphabet has it) of geometric length,
+    about a tenth of the text: skewed top-digit buckets and long ties."""
+    rng = np.random.default_rng(seed)
+    alph = np.sort(np.asarray(alph, dtype=np.uint8))
+    s = alph.size
+    if kind == "uniform":
+        t = alph[rng.integers(0, s, n)]
+    elif kind == "binary":
+        order = np.concatenate([[0], 1 + rng.permutation(s - 1)])
+        w = 1.0 / (np.arange(s) + 1.0) ** 1.1
+        p = np.empty(s)
+        p[order] = w / w.sum()
+        t = alph[rng.choice(s, n, p=p)]
+        runs = int(n * 0.1 / 64) + 1
+        starts = rng.integers(0, n, runs)
+        lens = rng.geometric(1.0 / 64, runs)
+        for a, m in zip(starts, lens):
+            t[a:a + m] = alph[0]
+    else:
+        raise ValueError(kind)
+    if n >= s:   # every byte present: one shuffled copy of the alphabet somewhere
+        p0 = int(rng.integers(0, n - s + 1))
+        t[p0:p0 + s] = rng.permutation(alph)
+    return np.ascontiguousarray(t, dtype=np.uint8)
+
+
+WORD_LENGTHS = (8, 9, 16, 31, 32, 33, 40, 64)   # the word boundaries of the query's pattern_words / cmp_suffix
+
+
+def edge_patterns(text, alph, k0, k2n, L, rng):
+    """Patterns where a query over packed keys can go wrong: text windows of every length around the key and the second-level
+    key (1 .. k0 + k2n + 2) and at the 8-byte word boundaries; runs of the largest and of the smallest present byte; windows
+    with one byte replaced by an absent byte between present ones, a byte below the smallest or one above the largest, at
+    positions 0, k0 - 1, k0, k0 + 1 and last; windows that run past the end of the text; the empty pattern; and, for a
+    truncated build (L > 0), patterns longer than L."""
+    n = int(text.size)
+    alph = np.sort(np.asarray(alph, dtype=np.uint8))
+    lo, hi = int(alph[0]), int(alph[-1])
+    pats = [b""]
+
+    def window(m):
+        m = min(m, n)
+        p = int(rng.integers(0, n - m + 1))
+        return bytes(text[p:p + m])
+
+    lengths = sorted(set(range(1, k0 + k2n + 3)) | set(WORD_LENGTHS))
+    for m in lengths:
+        pats += [window(m) for _ in range(3)]
+    for m in sorted({1, 2, max(k0 - 1, 1), k0, k0 + 1, k0 + k2n + 1, 40, 65}):
+        pats += [bytes([hi]) * m, bytes([lo]) * m]
+    gaps = gap_bytes(alph)
+    subs = []
+    if gaps.size:
+        subs += [int(gaps[0]), int(gaps[-1]), int(gaps[gaps.size // 2])]
+    if lo > 0:
+        subs += [lo - 1, 0]
+    if hi < 255:
+        subs += [hi + 1, 255]
+    for m in (k0 + 2, k0 + k2n + 2, 33):
+        for pos in sorted({0, max(k0 - 1, 0), k0, k0 + 1, m - 1}):
+            if pos >= m:
+                continue
+            for c in subs:
+                for _ in range(2):
+                    w = bytearray(window(m))
+                    if pos < len(w):
+                        w[pos] = c
+                    pats.append(bytes(w))
+    for m in sorted({1, max(k0 - 1, 1), k0, k0 + 3, 40}):
+        tail = bytes(text[max(n - m, 0):])
+        pats += [tail, tail + bytes([lo]), tail + bytes([hi]), tail + bytes(text[:5])]
+        if subs:
+            pats.append(tail + bytes([subs[0]]))
+    if L:
+        for m in (L + 1, L + 5, 2 * L + 3, 70):
+            w = bytearray(window(m))
+            pats.append(bytes(w))
+            if subs and len(w) > L:
+                w[L] = subs[0]                # a change past L does not matter
+                pats.append(bytes(w))
+                w[L - 1] = subs[-1]           # a change at L - 1 does
+                pats.append(bytes(w))
+    return pats
+
+
+def big_batch(text, edge, count, rng, maxlen=80):
+    """the edge patterns followed by text windows of 1 .. maxlen bytes, count patterns in all (a batch this large builds the
+    second-level keys of a wide-key index, csrc/sa_capi.hip: K2_AUTO_BATCH)"""
+    n = int(text.size)
+    out = list(edge)
+    while len(out) < count:
+        m = int(rng.integers(1, maxlen + 1))
+        p = int(rng.integers(0, max(n - m, 0) + 1))
+        out.append(bytes(text[p:p + m]))
+    return out[:count]
+
+
+def brute_ranges(text, max_suffix_length, patterns):
+    """The query's result from Python's own order of the suffixes: {lb, ub - 1} over the suffixes whose first
+    c = min(len, max_suffix_length) bytes compare below / not above the pattern's (a suffix that ends first is smaller),
+    lb == n -> {UINT32_MAX, UINT32_MAX} (the conventions of test_oracle.py::test_query_edge_conventions).  Quadratic in n."""
+    import bisect
+    raw = bytes(text)
+    n = len(raw)
+    suffixes = sorted(raw[s:] for s in range(n))   # a suffix order sorts every prefix length the same way
+    L = max_suffix_length if max_suffix_length else 1 << 32
+    out = []
+    for q in patterns:
+        c = min(len(q), L)
+        q = q[:c]
+        lb = bisect.bisect_left(suffixes, q, key=lambda x: x[:c])
+        ub = bisect.bisect_right(suffixes, q, key=lambda x: x[:c])
+        out.append((0xFFFFFFFF, 0xFFFFFFFF) if lb == n else (lb, (ub - 1) & 0xFFFFFFFF))
+    return out
