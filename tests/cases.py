@@ -298,3 +298,195 @@ def brute_ranges(text, max_suffix_length, patterns):
         ub = bisect.bisect_right(suffixes, q, key=lambda x: x[:c])
         out.append((0xFFFFFFFF, 0xFFFFFFFF) if lb == n else (lb, (ub - 1) & 0xFFFFFFFF))
     return out
+
+
+# -- record retrieval: a row model and texts with planted hits ---------------------------------------------------------------
+# Hits -> distinct rows runs as six pieces of code (csrc/rows_device.hpp: lane, wave, two workgroup tables, the fused single query;
+# csrc/records.hpp: the host path).  The model below is plain NumPy over a suffix array that the caller has checked; the texts
+# below put exact hit counts, row counts and suffix-array orders of the hits where those pieces switch and where their tables fill.
+MISS = 0xFFFFFFFF
+
+
+def range_hits(ranges):
+    """hit counts of query ranges (structured first / second) under every miss encoding: {UINT32_MAX, UINT32_MAX} (lb = n) and
+    second = first - 1, which wraps to UINT32_MAX when first = 0"""
+    f = np.asarray(ranges["first"]).astype(np.int64)
+    s = np.asarray(ranges["second"]).astype(np.int64)
+    return np.where(f == MISS, 0, (s - f + 1) & 0xFFFFFFFF)
+
+
+def rows_reference(sa, starts, ranges, k, with_first_hits=False):
+    """The rows of every range: the hits sa[first .. second] (none for a miss), each mapped to the last row whose start is <= the
+    hit (upper bound: of several zero-length rows at one offset the last wins), each row kept once in order of its first hit along
+    the range (suffix-array order), the first min(k, num_rows) of them.  -> (counts int64[R], list of int64 row arrays) and, with
+    with_first_hits, the index along its range of every kept row's first hit.  Vectorised: sort by (range, row, hit index), mark
+    the first hit of every pair, order those by (range, hit index)."""
+    sa = np.asarray(sa)
+    starts = np.asarray(starts, dtype=np.uint64)
+    cnt = range_hits(ranges)
+    R = cnt.size
+    first = np.where(cnt > 0, np.asarray(ranges["first"]).astype(np.int64), 0)
+    total = int(cnt.sum())
+    qid = np.repeat(np.arange(R, dtype=np.int64), cnt)
+    hidx = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    pos = sa[np.repeat(first, cnt) + hidx].astype(np.uint64)
+    row = np.searchsorted(starts, pos, side="right").astype(np.int64) - 1
+    o = np.lexsort((hidx, row, qid))
+    new = np.ones(total, dtype=bool)
+    new[1:] = (qid[o][1:] != qid[o][:-1]) | (row[o][1:] != row[o][:-1])
+    keep = np.sort(o[new])                       # (range, hit index) order: the order the hits were laid out in
+    kq, kr, kh = qid[keep], row[keep], hidx[keep]
+    nrows = np.bincount(kq, minlength=R)
+    take = np.minimum(nrows, min(int(k), int(starts.size)))
+    rank = np.arange(kq.size) - np.repeat(np.cumsum(nrows) - nrows, nrows)
+    sel = rank < take[kq]
+    cut = np.cumsum(take)[:-1]
+    rows = np.split(kr[sel], cut)
+    if with_first_hits:
+        return take, rows, np.split(kh[sel], cut)
+    return take, rows
+
+
+def marker(i):
+    """the i-th marker token: Q and three uppercase letters.  The texts below hold lowercase letters, newlines and markers, each
+    marker followed by a lowercase tag, so a marker occurs exactly where it was planted.  QZZZ is never planted (a miss)."""
+    assert 0 <= i < 26 ** 3 - 1
+    return b"Q" + bytes(65 + (i // 26 ** e) % 26 for e in (2, 1, 0))
+
+
+def _tag(j, width):
+    return bytes(97 + (j // 26 ** e) % 26 for e in range(width - 1, -1, -1))
+
+
+def planted_text(num_rows, plants, seed, start_marker=None, start_rows=()):
+    """Rows of random lowercase filler, each ending in a newline, with planted marker tokens.
+    plants: [(marker, rows)]: rows[j] is the row of the marker's j-th hit in suffix-array order -- the j-th token is followed by a
+    fixed-width lowercase tag that sorts as j, so the tags decide the hits' order whatever their order in the text.
+    start_rows: rows that begin with start_marker (the j-th of them tagged j): hits on a row's first byte; b"\\n" + start_marker hits
+    the last byte (the newline) of the row before.  -> (text uint8, row starts uint64: one row per line)"""
+    rng = np.random.default_rng(seed)
+    width = 4
+    per_row = [[] for _ in range(num_rows)]
+    for m, rows in plants:
+        assert len(rows) < 26 ** width
+        for j, r in enumerate(rows):
+            per_row[int(r)].append(m + _tag(j, width))
+    head = {}
+    for j, r in enumerate(start_rows):
+        assert int(r) not in head
+        head[int(r)] = start_marker + _tag(j, width)
+    letters = rng.integers(97, 123, 16 * num_rows + 64, dtype=np.uint8).tobytes()
+    fl = rng.integers(3, 11, 2 * num_rows + sum(len(t) for t in per_row) + 8)
+    li = fi = 0
+    out = []
+    for r in range(num_rows):
+        toks = per_row[r]
+        if len(toks) > 1:
+            toks = [toks[i] for i in rng.permutation(len(toks))]   # text order within a row is not the hits' order
+        parts = [head.get(r, b"")]
+        for t in toks + [b""]:
+            m = int(fl[fi]); fi += 1
+            if li + m > len(letters):
+                li = 0
+            parts.append(letters[li:li + m]); li += m
+            parts.append(t)
+        parts.append(b"\n")
+        out.append(b"".join(parts))
+    lens = np.fromiter((len(x) for x in out), dtype=np.int64, count=num_rows)
+    starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+    return np.frombuffer(b"".join(out), dtype=np.uint8), starts
+
+
+def _fresh(rng, pool, count):
+    """count distinct rows out of pool, in a random order"""
+    return rng.choice(np.asarray(pool), size=count, replace=False)
+
+
+def _few_then_new(rng, num_rows, first, few, new):
+    """first hits spread over exactly `few` rows (each of them at least once, the first `few` hits being those rows), then
+    `new` hits in rows of their own: where a walk stops, or a wave hands a range on, is set by `first` and `few`"""
+    rows = _fresh(rng, np.arange(num_rows), few + new)
+    head = np.concatenate([rows[:few], rng.choice(rows[:few], first - few)]) if first > few else rows[:few][:first]
+    return np.concatenate([head, rows[few:]])
+
+
+def rows_main_case(num_rows=70_001, seed=5):
+    """The main text of the record-retrieval sweep: num_rows rows (not a multiple of 256: the coarse table's last block is
+    partial) and one marker per cell.  -> (text, starts, {name: pattern}, {name: (hits, distinct rows)} as planted).
+    Names: h<count> (random rows, about half of them repeated), u<count> (every hit a row of its own), rep<...> (short ranges
+    with a row repeated after another one: the lanes' seen-test), fill64 / fill1536 / fill4096 (the k-th new row lands on the
+    last hit of a chunk: a wave / workgroup table holds k - 1 + chunk rows), mid64 (the 64th new row inside a wave chunk),
+    handoff<count> (the first 4096 hits in 10 rows, the rest in rows of their own), one<count> (every hit in one row), ends
+    (row 0 and the last row)."""
+    rng = np.random.default_rng(seed)
+    N = num_rows
+    allrows = np.arange(N)
+    spec = {}
+    for h in (1, 2, 3, 4, 5, 6, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097, 20_000):
+        d = max(1, (h + 1) // 2)
+        rows = _fresh(rng, allrows, d)
+        spec["h%d" % h] = rng.permutation(np.concatenate([rows, rng.choice(rows, h - d)]))
+    for h in (2, 3, 4, 5, 6, 63, 64, 65, 127, 128, 255, 256, 257, 320, 1535, 1536, 1537, 1792, 4095, 4096, 4097, 4352, 20_000):
+        spec["u%d" % h] = _fresh(rng, allrows, h)
+    a, b, c = (int(x) for x in _fresh(rng, allrows, 3))
+    spec["rep_aba"] = np.array([a, b, a])
+    spec["rep_abab"] = np.array([a, b, a, b])
+    spec["rep_abca"] = np.array([a, b, c, a])
+    spec["rep_aaba"] = np.array([a, a, b, a])
+    spec["rep_abcab"] = np.array([a, b, c, a, b])
+    spec["fill64"] = _few_then_new(rng, N, 64, 63, 100)
+    spec["mid64"] = _few_then_new(rng, N, 64, 30, 80)
+    spec["fill1536"] = _few_then_new(rng, N, 256, 255, 1600)
+    spec["fill4096"] = _few_then_new(rng, N, 256, 255, 4200)
+    spec["mid1536"] = _few_then_new(rng, N, 1280, 1223, 600)
+    for h in (4096, 4097, 4100, 5000):
+        spec["handoff%d" % h] = _few_then_new(rng, N, 4096, 10, h - 4096)
+    spec["one300"] = np.full(300, int(rng.integers(0, N)))
+    spec["one20000"] = np.full(20_000, int(rng.integers(0, N)))
+    spec["ends"] = np.array([N - 1, 0, N - 1, 0, int(rng.integers(1, N - 1)), N - 1])
+    plants = [(marker(i), rows) for i, rows in enumerate(spec.values())]
+    head_rows = np.concatenate([[0, N - 1], _fresh(rng, np.arange(1, N - 1), 3000)])
+    rng.shuffle(head_rows)
+    S = marker(len(plants))
+    text, starts = planted_text(N, plants, seed, S, head_rows)
+    pats = {name: m for name, (m, _) in zip(spec, plants)}
+    pats.update({"head": S, "nl_head": b"\n" + S, "nl": b"\n", "miss_end": b"~", "miss_mid": b"QZZZ",
+                 "miss_wrap": b"\x01"})
+    claim = {name: (len(r), len(set(int(x) for x in r))) for name, r in spec.items()}
+    claim["head"] = (len(head_rows), len(head_rows))
+    claim["nl_head"] = (len(head_rows) - 1, len(head_rows) - 1)   # (row 0 has no newline before it)
+    claim["nl"] = (N, N)
+    for m in ("miss_end", "miss_mid", "miss_wrap"):
+        claim[m] = (0, 0)
+    return text, starts, pats, claim
+
+
+def rows_small_case(num_rows, seed=9):
+    """A small text of num_rows rows (1, 255, 256, 257, 512, 513: around the coarse table's 256-row blocks) -> as rows_main_case.
+    every: one hit per row; twice: two per row; last: 70 hits in the last row and one in row 0; few: 5 hits over the ends."""
+    rng = np.random.default_rng(seed + num_rows)
+    N = num_rows
+    spec = {"every": rng.permutation(N), "twice": rng.permutation(np.repeat(np.arange(N), 2)),
+            "last": np.concatenate([np.full(70, N - 1), [0]]), "few": np.array([N - 1, 0, N - 1, N // 2, 0])}
+    spec["last"] = rng.permutation(spec["last"])
+    plants = [(marker(i), rows) for i, rows in enumerate(spec.values())]
+    S = marker(len(plants))
+    head_rows = rng.permutation(N)
+    text, starts = planted_text(N, plants, seed, S, head_rows)
+    pats = {name: m for name, (m, _) in zip(spec, plants)}
+    pats.update({"head": S, "nl_head": b"\n" + S, "nl": b"\n", "miss_end": b"~", "miss_mid": b"QZZZ", "miss_wrap": b"\x01"})
+    claim = {name: (len(r), len(set(int(x) for x in r))) for name, r in spec.items()}
+    claim.update({"head": (N, N), "nl_head": (N - 1, N - 1), "nl": (N, N)})
+    for m in ("miss_end", "miss_mid", "miss_wrap"):
+        claim[m] = (0, 0)
+    return text, starts, pats, claim
+
+
+def zero_length_rows(starts, seed=3):
+    """The same text under a row table with zero-length rows (equal consecutive starts, which sa_hip_index_set_rows accepts): row 0
+    is empty, and empty rows sit at the coarse table's block edges and at random places."""
+    rng = np.random.default_rng(seed)
+    n = starts.size
+    dup = {0, n - 1} | {i for i in (254, 255, 256, 511, 512) if i < n} | set(int(x) for x in rng.integers(0, n, max(n // 200, 3)))
+    extra = starts[sorted(dup)]
+    return np.sort(np.concatenate([starts, extra, starts[:1]])).astype(np.uint64)
