@@ -105,6 +105,58 @@ int sa_hip_last_call_breakdown(sa_hip_call_breakdown* out);
 /* Free the shared workspace (device buffers and pinned slabs); the next call allocates it again. */
 void sa_hip_release_workspace(void);
 
+/* ---- (1b) LCP arrays, libsais-call-compatible ------------------------------------------------
+ * PLCP[i] = length of the longest common prefix of suffix i and the suffix that precedes it in SA order (0 for SA[0]);
+ * LCP[r] = PLCP[SA[r]].  Computed on the device by the irreducible-LCP method (csrc/lcp.hpp): only positions whose
+ * BWT character differs from their predecessor's are compared against the text, the rest follow from an inclusive
+ * max-scan of i + PLCP[i] -- bounded work on highly repetitive texts, where a chunked Kasai pass is quadratic.
+ *
+ * Drop-ins (host pointers): same arguments, return codes and n <= 1 behaviour as the reference.  threads is validated
+ * (>= 0) and otherwise ignored.  LCP may be SA (libsais.h:351).  *_lcp gathers whatever PLCP it is given.  NULL
+ * pointers and n < 0 return -1 before any device call; every SA entry is range-checked on the device before it is used,
+ * an entry >= n (or < 0) returns -1 and leaves the output undefined.  An in-range SA that is not a suffix array gives
+ * unspecified (but bounded) output.  They share the process workspace of sa_hip_libsais* (its pinned slabs; the LCP
+ * scratch -- about 16 bytes per character, 32 for the 64-bit forms -- stays allocated until sa_hip_release_workspace)
+ * and report in sa_hip_last_call_breakdown (build_ms / build_device_ms = the device pass).  The 64-bit forms run with
+ * 64-bit indices on the device and accept every n the 64-bit build accepts, including n > 2^32 - 2. */
+/* replaces libsais_plcp (libsais.h:333, libsais.c:7869) */
+int32_t sa_hip_libsais_plcp(const uint8_t* T, const int32_t* SA, int32_t* PLCP, int32_t n);
+/* replaces libsais_plcp_omp (libsais.h:365, libsais.c:7924) */
+int32_t sa_hip_libsais_plcp_omp(const uint8_t* T, const int32_t* SA, int32_t* PLCP, int32_t n, int32_t threads);
+/* replaces libsais_lcp (libsais.h:353, libsais.c:7905) */
+int32_t sa_hip_libsais_lcp(const int32_t* PLCP, const int32_t* SA, int32_t* LCP, int32_t n);
+/* replaces libsais_lcp_omp (libsais.h:387, libsais.c:7964) */
+int32_t sa_hip_libsais_lcp_omp(const int32_t* PLCP, const int32_t* SA, int32_t* LCP, int32_t n, int32_t threads);
+/* replace libsais64_plcp / _omp and libsais64_lcp / _omp (libsais64.h:220-253) */
+int64_t sa_hip_libsais64_plcp(const uint8_t* T, const int64_t* SA, int64_t* PLCP, int64_t n);
+int64_t sa_hip_libsais64_plcp_omp(const uint8_t* T, const int64_t* SA, int64_t* PLCP, int64_t n, int64_t threads);
+int64_t sa_hip_libsais64_lcp(const int64_t* PLCP, const int64_t* SA, int64_t* LCP, int64_t n);
+int64_t sa_hip_libsais64_lcp_omp(const int64_t* PLCP, const int64_t* SA, int64_t* LCP, int64_t n, int64_t threads);
+
+/* Where the device time of an LCP call went (HIP events) and how much text it compared. */
+typedef struct sa_hip_lcp_stats {
+    uint64_t n;
+    uint64_t tied;                 /* ranks whose packed key equals the predecessor's (0 when the key shortcut is off)       */
+    uint64_t compared_positions;   /* irreducible positions compared against the text                                        */
+    uint64_t compared_bytes;       /* text bytes compared (pairs of bytes, counted once)                                      */
+    uint64_t wave_compares;        /* pairs longer than the per-lane budget, compared by one wave each                         */
+    uint64_t split_compares;       /* pairs longer than the per-wave budget, compared across workgroups                        */
+    uint32_t split_rounds;         /* rounds of doubling segments launched for them                                           */
+    uint32_t keys;                 /* 1: the key shortcut of an index handle was used                                         */
+    double   phi_ms;               /* range check, reducibility test, short comparisons, scatter                              */
+    double   wave_ms;
+    double   split_ms;
+    double   scan_ms;              /* max-scan of i + PLCP[i] over the text                                                   */
+    double   gather_ms;            /* LCP[r] = PLCP[SA[r]] (0 for a PLCP output)                                              */
+    double   total_ms;
+} sa_hip_lcp_stats;
+
+/* The 64-bit forms on device buffers (mirror sa_hip_libsais64_device; any n >= 0): text_dev n bytes, 8-byte aligned;
+ * sa_dev n int64 entries; out_dev n int64 entries (PLCP in text order, or LCP in SA order).  Synchronous; stats may be
+ * NULL.  An SA entry outside [0, n) returns -1. */
+int sa_hip_plcp64_device(const void* text_dev, const int64_t* sa_dev, int64_t* out_dev, int64_t n, int device, sa_hip_lcp_stats* stats);
+int sa_hip_lcp64_device(const void* text_dev, const int64_t* sa_dev, int64_t* out_dev, int64_t n, int device, sa_hip_lcp_stats* stats);
+
 /* ---- (2) truncated construction, engine.c-call-compatible ------------------------------- */
 
 /* replaces construct_truncated_suffix_array (engine.h:213, engine.c:837-866).
@@ -222,6 +274,14 @@ int sa_hip_index_get_sa_i64(sa_hip_index* idx, int64_t* out_host);
  * the same pass as one kernel, 12 bytes of HBM traffic per entry).  Asynchronous on the index's stream; its
  * HIP-event time is reported as sa_hip_build_stats.widen_ms. */
 int sa_hip_index_widen_device(sa_hip_index* idx, void* out_dev);
+/* PLCP (text order) or LCP (SA order) of a built or loaded index, u32[n] into out_dev, a device buffer of n * 4 bytes on
+ * the index's device.  Asynchronous on the index's stream when stats is NULL; with stats the call waits and fills it.
+ * The packed keys of the index answer every rank whose first k0 characters differ from its predecessor's without
+ * touching the text (the "key shortcut"; tied ranks are compared from depth k0).  Truncated indexes
+ * (max_suffix_length > 0) and handles without an index return -1 (sa_hip_last_error says why).  The index's scratch
+ * for the pass (about 12 bytes per character) stays with the handle. */
+int sa_hip_index_plcp_device(sa_hip_index* idx, void* out_dev, sa_hip_lcp_stats* stats);
+int sa_hip_index_lcp_device(sa_hip_index* idx, void* out_dev, sa_hip_lcp_stats* stats);
 /* 256-bin byte histogram of the indexed text (libsais `freq`). */
 int sa_hip_index_get_freq(sa_hip_index* idx, uint64_t* freq256);
 

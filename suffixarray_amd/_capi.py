@@ -19,6 +19,9 @@ UINT32_MAX = 0xFFFFFFFF
 EXPORTS = [
     "sa_hip_libsais", "sa_hip_libsais_omp", "sa_hip_libsais64", "sa_hip_libsais64_omp",
     "sa_hip_libsais64_device", "sa_hip_sufcheck64_device", "sa_hip_index_deep_keys",
+    "sa_hip_libsais_plcp", "sa_hip_libsais_plcp_omp", "sa_hip_libsais_lcp", "sa_hip_libsais_lcp_omp",
+    "sa_hip_libsais64_plcp", "sa_hip_libsais64_plcp_omp", "sa_hip_libsais64_lcp", "sa_hip_libsais64_lcp_omp",
+    "sa_hip_plcp64_device", "sa_hip_lcp64_device", "sa_hip_index_plcp_device", "sa_hip_index_lcp_device",
     "sa_hip_last_call_breakdown", "sa_hip_release_workspace",
     "sa_hip_construct_truncated_suffix_array", "sa_hip_get_substring_positions",
     "sa_hip_device_count", "sa_hip_index_create", "sa_hip_index_destroy", "sa_hip_index_build",
@@ -97,6 +100,17 @@ class CallBreakdown(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
 
 
+class LcpStats(C.Structure):
+    """sa_hip_lcp_stats: device time per phase and text work of one PLCP / LCP pass."""
+    _fields_ = [("n", C.c_uint64), ("tied", C.c_uint64), ("compared_positions", C.c_uint64), ("compared_bytes", C.c_uint64),
+                ("wave_compares", C.c_uint64), ("split_compares", C.c_uint64), ("split_rounds", C.c_uint32), ("keys", C.c_uint32),
+                ("phi_ms", C.c_double), ("wave_ms", C.c_double), ("split_ms", C.c_double), ("scan_ms", C.c_double),
+                ("gather_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class ReplicaLayout(C.Structure):
     """sa_hip_replica_layout: what a replica must know about the index it copies (travels as bytes)."""
     _fields_ = [("n", C.c_uint64), ("max_suffix_length", C.c_uint32), ("key_bytes", C.c_uint32), ("bits_per_symbol", C.c_uint32),
@@ -144,6 +158,22 @@ def lib():
     L.sa_hip_libsais64_device.argtypes = [vp, vp, i64, C.c_int, C.POINTER(BigStats)]
     L.sa_hip_sufcheck64_device.restype = C.c_int
     L.sa_hip_sufcheck64_device.argtypes = [vp, vp, i64, C.c_int, C.POINTER(u64)]
+    for name in ("sa_hip_libsais_plcp", "sa_hip_libsais_lcp"):
+        getattr(L, name).restype = i32
+        getattr(L, name).argtypes = [vp, vp, vp, i32]
+        getattr(L, name + "_omp").restype = i32
+        getattr(L, name + "_omp").argtypes = [vp, vp, vp, i32, i32]
+    for name in ("sa_hip_libsais64_plcp", "sa_hip_libsais64_lcp"):
+        getattr(L, name).restype = i64
+        getattr(L, name).argtypes = [vp, vp, vp, i64]
+        getattr(L, name + "_omp").restype = i64
+        getattr(L, name + "_omp").argtypes = [vp, vp, vp, i64, i64]
+    for name in ("sa_hip_plcp64_device", "sa_hip_lcp64_device"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [vp, vp, vp, i64, C.c_int, C.POINTER(LcpStats)]
+    for name in ("sa_hip_index_plcp_device", "sa_hip_index_lcp_device"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [vp, vp, C.POINTER(LcpStats)]
     L.sa_hip_index_deep_keys.restype = C.c_int
     L.sa_hip_index_deep_keys.argtypes = [vp, C.c_int]
     L.sa_hip_last_call_breakdown.restype = C.c_int
@@ -324,6 +354,7 @@ class DeviceIndex:
     def __init__(self, n_max, device=0):
         self._h = C.c_void_p()
         self._lib = lib()
+        self._device = int(device)
         check(self._lib.sa_hip_index_create(C.byref(self._h), int(n_max), int(device)))
 
     @classmethod
@@ -467,6 +498,31 @@ class DeviceIndex:
 
     def sync(self):
         check(self._lib.sa_hip_index_sync(self._h))
+
+    # -- LCP arrays (sa_hip_index_[p]lcp_device; full suffix arrays only) ------------------------
+    def plcp_device(self, out_dev_ptr, stats=False):
+        """PLCP (text order) as u32[n] into a device buffer of the index's device.  Asynchronous on the index's stream;
+        stats=True waits and returns the sa_hip_lcp_stats of the pass as a dict."""
+        st = LcpStats() if stats else None
+        check(self._lib.sa_hip_index_plcp_device(self._h, out_dev_ptr, C.byref(st) if st is not None else None))
+        return st.as_dict() if st is not None else None
+
+    def lcp_device(self, out_dev_ptr, stats=False):
+        """LCP (SA order: LCP[r] = PLCP[SA[r]]) as u32[n] into a device buffer, as plcp_device."""
+        st = LcpStats() if stats else None
+        check(self._lib.sa_hip_index_lcp_device(self._h, out_dev_ptr, C.byref(st) if st is not None else None))
+        return st.as_dict() if st is not None else None
+
+    def lcp(self, plcp=False):
+        """LCP (or, plcp=True, PLCP) of the index as a numpy uint32 array.  The device buffer comes from torch (a ROCm
+        build), which is how this package's callers hold device memory; nothing but its address reaches the C ABI."""
+        import torch
+        n = self.n
+        buf = torch.empty(max(n, 1), dtype=torch.int32, device=f"cuda:{getattr(self, '_device', 0)}")
+        torch.cuda.synchronize(buf.device)
+        (self.plcp_device if plcp else self.lcp_device)(buf.data_ptr())
+        self.sync()
+        return buf[:n].cpu().numpy().view(np.uint32)
 
     def deep_keys(self, mode=2):
         """Second-level keys for patterns longer than the key (sa_hip_index_deep_keys): 2 = build now, 1 = large batches build
@@ -643,6 +699,58 @@ def libsais64_device(text_ptr, sa_ptr, n, device=0):
     """The 64-bit-index build (csrc/big_build.hpp) on device buffers: text_ptr = n bytes, sa_ptr = n int64 entries.  Returns its stats."""
     st = BigStats()
     check(lib().sa_hip_libsais64_device(text_ptr, sa_ptr, n, device, C.byref(st)))
+    return st.as_dict()
+
+
+def libsais_plcp(text, sa):
+    """PLCP of (text, suffix array) through sa_hip_libsais_plcp: int32[n] in text order."""
+    t = as_u8(text)
+    s = np.ascontiguousarray(sa, dtype=np.int32)
+    assert s.size == t.size
+    out = np.empty(max(t.size, 1), dtype=np.int32)
+    check(lib().sa_hip_libsais_plcp(t.ctypes.data, s.ctypes.data, out.ctypes.data, t.size))
+    return out[:t.size]
+
+
+def libsais_lcp(plcp, sa):
+    """LCP from PLCP and the suffix array through sa_hip_libsais_lcp: int32[n] in SA order."""
+    p = np.ascontiguousarray(plcp, dtype=np.int32)
+    s = np.ascontiguousarray(sa, dtype=np.int32)
+    assert s.size == p.size
+    out = np.empty(max(p.size, 1), dtype=np.int32)
+    check(lib().sa_hip_libsais_lcp(p.ctypes.data, s.ctypes.data, out.ctypes.data, p.size))
+    return out[:p.size]
+
+
+def libsais64_plcp(text, sa):
+    t = as_u8(text)
+    s = np.ascontiguousarray(sa, dtype=np.int64)
+    assert s.size == t.size
+    out = np.empty(max(t.size, 1), dtype=np.int64)
+    check(int(lib().sa_hip_libsais64_plcp(t.ctypes.data, s.ctypes.data, out.ctypes.data, t.size)))
+    return out[:t.size]
+
+
+def libsais64_lcp(plcp, sa):
+    p = np.ascontiguousarray(plcp, dtype=np.int64)
+    s = np.ascontiguousarray(sa, dtype=np.int64)
+    assert s.size == p.size
+    out = np.empty(max(p.size, 1), dtype=np.int64)
+    check(int(lib().sa_hip_libsais64_lcp(p.ctypes.data, s.ctypes.data, out.ctypes.data, p.size)))
+    return out[:p.size]
+
+
+def plcp64_device(text_ptr, sa_ptr, out_ptr, n, device=0):
+    """PLCP with 64-bit indices on device buffers: text n bytes (8-byte aligned), sa / out n int64 entries.  Returns the stats."""
+    st = LcpStats()
+    check(lib().sa_hip_plcp64_device(text_ptr, sa_ptr, out_ptr, n, device, C.byref(st)))
+    return st.as_dict()
+
+
+def lcp64_device(text_ptr, sa_ptr, out_ptr, n, device=0):
+    """LCP (SA order) with 64-bit indices on device buffers, as plcp64_device."""
+    st = LcpStats()
+    check(lib().sa_hip_lcp64_device(text_ptr, sa_ptr, out_ptr, n, device, C.byref(st)))
     return st.as_dict()
 
 

@@ -17,6 +17,7 @@
 #include "rows_device.hpp"
 #include "host_index.hpp"
 #include "comm_rccl.hpp"
+#include "lcp.hpp"
 #include <memory>
 #include <chrono>
 
@@ -55,6 +56,7 @@ struct sa_hip_index {
     bool k2_auto = true;           // sa_hip_index_deep_keys: large batches build the second-level keys on their way
     DevBuf qc_hist, qc_off, qc_part, qc_tmp;   // clustering of a large batch over a wide-key index (sa_query.hpp: qcluster_*)
     sa_hip_replica_layout pending{};
+    lcp::Workspace lcp_ws;         // sa_hip_index_[p]lcp_device (lcp.hpp)
 };
 
 // multi-GPU lifecycle (comm_rccl.hpp): one communicator per process / GPU
@@ -256,6 +258,18 @@ struct OneShot {
     sa_hip_index* idx = nullptr;
     PinnedRing ring;
     sa_hip_call_breakdown last{};
+    // the LCP drop-ins (sa_hip_libsais[64]_plcp / _lcp): their own device buffers beside the cached index, same ring
+    lcp::Workspace lcp;
+    DevBuf l_text, l_sa, l_in, l_out;
+    hipStream_t l_stream = nullptr;
+    int l_device = -1;
+    void release_lcp() {
+        if (l_device >= 0) (void)hipSetDevice(l_device);
+        if (l_stream) (void)hipStreamDestroy(l_stream);
+        l_stream = nullptr;
+        lcp.release(); l_text.release(); l_sa.release(); l_in.release(); l_out.release();
+        l_device = -1;
+    }
 } g_oneshot;
 
 }  // namespace
@@ -318,6 +332,7 @@ void sa_hip_index_destroy(sa_hip_index* idx) {
     idx->q_pat.release(); idx->q_off.release(); idx->q_out.release(); idx->widen.release();
     idx->rows_dev.release(); idx->rows_coarse.release(); idx->r_rows.release(); idx->r_counts.release(); idx->r_pending.release();
     idx->qc_hist.release(); idx->qc_off.release(); idx->qc_part.release(); idx->qc_tmp.release();
+    idx->lcp_ws.release();
     if (idx->qh_host) (void)hipHostFree(idx->qh_host);
     for (int i = 0; i < sa_hip_index::QRING; ++i)
         for (int k = 0; k < 2; ++k) if (idx->q_ev[i][k]) (void)hipEventDestroy(idx->q_ev[i][k]);
@@ -1709,6 +1724,7 @@ int sa_hip_last_call_breakdown(sa_hip_call_breakdown* out) {
 void sa_hip_release_workspace(void) {
     std::lock_guard<std::mutex> lock(g_oneshot.mu);
     if (g_oneshot.idx) { (void)hipSetDevice(g_oneshot.idx->device); sa_hip_index_destroy(g_oneshot.idx); g_oneshot.idx = nullptr; }
+    g_oneshot.release_lcp();
     g_oneshot.ring.destroy();
 }
 
@@ -1892,6 +1908,187 @@ void sa_hip_synth_uniform27(uint8_t* out, uint64_t n, uint64_t seed) {
         const uint32_t v = (uint32_t)((s >> 33) % 27u);
         out[i] = (uint8_t)(v == 26 ? '\n' : 'a' + v);
     }
+}
+
+// ---- LCP arrays (lcp.hpp) ---------------------------------------------------------------------------------------------
+
+extern "C++" {
+namespace {
+// Host drop-ins: Idx = u32 (libsais layout, int32 on the host) or u64 (libsais64 layout).  PLCP_IN == nullptr: PLCP of
+// (T, SA) into out; else LCP = gather of PLCP_IN by SA into out.  n >= 2, arguments checked by the caller.
+template <class Idx>
+int oneshot_lcp(const uint8_t* T, const void* plcp_in, const void* SA, void* out, uint64_t n) {
+    OneShot& g = g_oneshot;
+    std::lock_guard<std::mutex> lock(g.mu);
+    const auto t_all = std::chrono::steady_clock::now();
+    sa_hip_call_breakdown bd{};
+    bd.n = n;
+    const size_t bytes = (size_t)n * sizeof(Idx);
+    auto t0 = std::chrono::steady_clock::now();
+    const int device = g.idx ? g.idx->device : 0;
+    int rc = set_device(device);
+    if (rc) return rc;
+    if (g.l_device >= 0 && g.l_device != device) g.release_lcp();
+    bd.workspace_reused = (g.l_stream && g.ring.ready && g.l_sa.cap >= bytes && g.l_out.cap >= bytes &&
+                           (plcp_in ? g.l_in.cap >= bytes : (g.l_text.cap >= n + 64 && g.lcp.w.cap >= bytes))) ? 1u : 0u;
+    if (!g.l_stream) SA_HIP_CHECK(hipStreamCreateWithFlags(&g.l_stream, hipStreamNonBlocking));
+    g.l_device = device;
+    if (g.ring.ready && g.ring.device != device) g.ring.destroy();
+    if ((rc = g.ring.init()) || (rc = g.l_sa.ensure(bytes + 64)) || (rc = g.l_out.ensure(bytes + 64))) return rc;
+    if (plcp_in) { if ((rc = g.l_in.ensure(bytes + 64))) return rc; }
+    else if ((rc = g.l_text.ensure(n + 64)) || (rc = g.lcp.ensure(n, sizeof(Idx)))) return rc;
+    bd.workspace_ms = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    if ((rc = ring_upload(g.ring, g.l_stream, device, g.l_sa.p, static_cast<const u8*>(SA), bytes))) return rc;
+    if (plcp_in) rc = ring_upload(g.ring, g.l_stream, device, g.l_in.p, static_cast<const u8*>(plcp_in), bytes);
+    else rc = ring_upload(g.ring, g.l_stream, device, g.l_text.p, T, (size_t)n);
+    if (rc) return rc;
+    bd.upload_ms = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    u32 error = 0;
+    if (plcp_in) {
+        const auto e0 = std::chrono::steady_clock::now();
+        if ((rc = lcp::gather_only<Idx>(g.lcp, g.l_stream, g.l_in.as<Idx>(), g.l_sa.as<Idx>(), n, g.l_out.as<Idx>(), &error))) return rc;
+        bd.build_device_ms = ms_since(e0);
+    } else {
+        lcp::Counters ctr{};
+        sa_hip_lcp_stats st{};
+        if ((rc = lcp::run<Idx>(g.lcp, g.l_stream, g.l_text.as<u8>(), g.l_sa.as<Idx>(), n, g.l_out.as<Idx>(), lcp::Out::PLCP, nullptr,
+                                lcp::Knobs::read(), &ctr, &st))) return rc;
+        error = ctr.error;
+        bd.build_device_ms = st.total_ms;
+    }
+    bd.build_ms = ms_since(t0);
+    if (error) return fail(SA_HIP_EINVAL, "suffix array entry out of range [0, n)");
+    t0 = std::chrono::steady_clock::now();
+    rc = ring_download_pieces(g.ring, device, g.l_out.as<u8>(), bytes, PinnedRing::SLAB_BYTES,
+                              [&](const u8* piece, size_t off, size_t len) { memcpy(static_cast<u8*>(out) + off, piece, len); });
+    if (rc) return rc;
+    bd.download_ms = ms_since(t0);
+    bd.total_ms = ms_since(t_all);
+    g.last = bd;
+    return 0;
+}
+
+int index_lcp(sa_hip_index* idx, void* out_dev, sa_hip_lcp_stats* stats, lcp::Out what, const char* name) {
+    if (!idx) return fail(SA_HIP_EINVAL, name, "NULL index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->host) return fail(SA_HIP_EINVAL, name, "the host path (no HIP device) has no device buffers");
+    if (!idx->has_index) return fail(SA_HIP_EINVAL, name, "no index (build or load one first)");
+    if (idx->b.max_suffix_length > 0)
+        return fail(SA_HIP_EINVAL, name, "truncated index (max_suffix_length > 0): its order is not the suffix order LCP needs");
+    const u64 n = idx->b.n;
+    if (!out_dev && n) return fail(SA_HIP_EINVAL, name, "NULL output");
+    int rc = set_device(idx->device);
+    if (rc) return rc;
+    if (n <= 1) {
+        if (n == 1) SA_HIP_CHECK(hipMemsetAsync(out_dev, 0, 4, idx->stream));
+        if (stats) { memset(stats, 0, sizeof *stats); stats->n = n; SA_HIP_CHECK(hipStreamSynchronize(idx->stream)); }
+        return 0;
+    }
+    const lcp::Knobs kn = lcp::Knobs::read();
+    const Builder& b = idx->b;
+    lcp::KeyView kv{};
+    const bool keys = kn.keys && (b.qkeys || (b.qkeys32 && b.q_bstart)) && b.q_b > 0 && b.q_k0 > 0;
+    if (keys) { kv.keys = b.qkeys; kv.keys32 = b.qkeys ? nullptr : b.qkeys32; kv.bstart = b.q_bstart; kv.lo_shift = b.q_lo_shift; kv.b = b.q_b; kv.k0 = b.q_k0; }
+    return lcp::run<u32>(idx->lcp_ws, idx->stream, b.text.as<u8>(), b.sa, n, static_cast<u32*>(out_dev), what, keys ? &kv : nullptr,
+                         kn, nullptr, stats);
+}
+
+int lcp64_device(const void* text_dev, const int64_t* sa_dev, int64_t* out_dev, int64_t n, int device, sa_hip_lcp_stats* stats,
+                 lcp::Out what, const char* name) {
+    if (n < 0) return fail(SA_HIP_EINVAL, name, "negative length");
+    if ((!text_dev || !sa_dev || !out_dev) && n) return fail(SA_HIP_EINVAL, name, "NULL argument");
+    if (((uintptr_t)text_dev & 7u) != 0) return fail(SA_HIP_EINVAL, name, "text_dev must be 8-byte aligned");
+    if (stats) { memset(stats, 0, sizeof *stats); stats->n = (u64)n; }
+    if (n == 0) return 0;
+    int rc = set_device(device);
+    if (rc) return rc;
+    hipStream_t stream = nullptr;
+    SA_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    lcp::Workspace ws;
+    auto body = [&]() -> int {
+        if (n == 1) {   // PLCP[0] = 0; LCP[0] = PLCP[SA[0]] with SA[0] range-checked
+            int64_t s0 = 0;
+            SA_HIP_CHECK(hipMemcpyAsync(&s0, sa_dev, 8, hipMemcpyDeviceToHost, stream));
+            SA_HIP_CHECK(hipStreamSynchronize(stream));
+            if (what == lcp::Out::LCP && s0 != 0) return fail(SA_HIP_EINVAL, name, "suffix array entry out of range [0, n)");
+            SA_HIP_CHECK(hipMemsetAsync(out_dev, 0, 8, stream));
+            SA_HIP_CHECK(hipStreamSynchronize(stream));
+            return 0;
+        }
+        lcp::Counters ctr{};
+        int r = lcp::run<u64>(ws, stream, static_cast<const u8*>(text_dev), reinterpret_cast<const u64*>(sa_dev), (u64)n,
+                              reinterpret_cast<u64*>(out_dev), what, nullptr, lcp::Knobs::read(), &ctr, stats);
+        if (r) return r;
+        if (ctr.error) return fail(SA_HIP_EINVAL, name, "suffix array entry out of range [0, n)");
+        return 0;
+    };
+    rc = body();
+    (void)hipStreamSynchronize(stream);
+    ws.release();
+    (void)hipStreamDestroy(stream);
+    return rc;
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t sa_hip_libsais_plcp_omp(const uint8_t* T, const int32_t* SA, int32_t* PLCP, int32_t n, int32_t threads) {
+    if (T == nullptr || SA == nullptr || PLCP == nullptr || n < 0 || threads < 0) return fail(SA_HIP_EINVAL, "sa_hip_libsais_plcp: invalid arguments");
+    if (n <= 1) { if (n == 1) PLCP[0] = 0; return 0; }
+    return oneshot_lcp<u32>(T, nullptr, SA, PLCP, (uint64_t)n);
+}
+int32_t sa_hip_libsais_plcp(const uint8_t* T, const int32_t* SA, int32_t* PLCP, int32_t n) {
+    return sa_hip_libsais_plcp_omp(T, SA, PLCP, n, 0);
+}
+int32_t sa_hip_libsais_lcp_omp(const int32_t* PLCP, const int32_t* SA, int32_t* LCP, int32_t n, int32_t threads) {
+    if (PLCP == nullptr || SA == nullptr || LCP == nullptr || n < 0 || threads < 0) return fail(SA_HIP_EINVAL, "sa_hip_libsais_lcp: invalid arguments");
+    if (n <= 1) {
+        if (n == 1) {
+            if (SA[0] != 0) return fail(SA_HIP_EINVAL, "sa_hip_libsais_lcp: suffix array entry out of range [0, n)");
+            LCP[0] = PLCP[0];
+        }
+        return 0;
+    }
+    return oneshot_lcp<u32>(nullptr, PLCP, SA, LCP, (uint64_t)n);
+}
+int32_t sa_hip_libsais_lcp(const int32_t* PLCP, const int32_t* SA, int32_t* LCP, int32_t n) {
+    return sa_hip_libsais_lcp_omp(PLCP, SA, LCP, n, 0);
+}
+int64_t sa_hip_libsais64_plcp_omp(const uint8_t* T, const int64_t* SA, int64_t* PLCP, int64_t n, int64_t threads) {
+    if (T == nullptr || SA == nullptr || PLCP == nullptr || n < 0 || threads < 0) return fail(SA_HIP_EINVAL, "sa_hip_libsais64_plcp: invalid arguments");
+    if (n <= 1) { if (n == 1) PLCP[0] = 0; return 0; }
+    return oneshot_lcp<u64>(T, nullptr, SA, PLCP, (uint64_t)n);
+}
+int64_t sa_hip_libsais64_plcp(const uint8_t* T, const int64_t* SA, int64_t* PLCP, int64_t n) {
+    return sa_hip_libsais64_plcp_omp(T, SA, PLCP, n, 0);
+}
+int64_t sa_hip_libsais64_lcp_omp(const int64_t* PLCP, const int64_t* SA, int64_t* LCP, int64_t n, int64_t threads) {
+    if (PLCP == nullptr || SA == nullptr || LCP == nullptr || n < 0 || threads < 0) return fail(SA_HIP_EINVAL, "sa_hip_libsais64_lcp: invalid arguments");
+    if (n <= 1) {
+        if (n == 1) {
+            if (SA[0] != 0) return fail(SA_HIP_EINVAL, "sa_hip_libsais64_lcp: suffix array entry out of range [0, n)");
+            LCP[0] = PLCP[0];
+        }
+        return 0;
+    }
+    return oneshot_lcp<u64>(nullptr, PLCP, SA, LCP, (uint64_t)n);
+}
+int64_t sa_hip_libsais64_lcp(const int64_t* PLCP, const int64_t* SA, int64_t* LCP, int64_t n) {
+    return sa_hip_libsais64_lcp_omp(PLCP, SA, LCP, n, 0);
+}
+
+int sa_hip_index_plcp_device(sa_hip_index* idx, void* out_dev, sa_hip_lcp_stats* stats) {
+    return index_lcp(idx, out_dev, stats, lcp::Out::PLCP, "sa_hip_index_plcp_device");
+}
+int sa_hip_index_lcp_device(sa_hip_index* idx, void* out_dev, sa_hip_lcp_stats* stats) {
+    return index_lcp(idx, out_dev, stats, lcp::Out::LCP, "sa_hip_index_lcp_device");
+}
+int sa_hip_plcp64_device(const void* text_dev, const int64_t* sa_dev, int64_t* out_dev, int64_t n, int device, sa_hip_lcp_stats* stats) {
+    return lcp64_device(text_dev, sa_dev, out_dev, n, device, stats, lcp::Out::PLCP, "sa_hip_plcp64_device");
+}
+int sa_hip_lcp64_device(const void* text_dev, const int64_t* sa_dev, int64_t* out_dev, int64_t n, int device, sa_hip_lcp_stats* stats) {
+    return lcp64_device(text_dev, sa_dev, out_dev, n, device, stats, lcp::Out::LCP, "sa_hip_lcp64_device");
 }
 
 }  // extern "C"
