@@ -157,6 +157,74 @@ typedef struct sa_hip_lcp_stats {
 int sa_hip_plcp64_device(const void* text_dev, const int64_t* sa_dev, int64_t* out_dev, int64_t n, int device, sa_hip_lcp_stats* stats);
 int sa_hip_lcp64_device(const void* text_dev, const int64_t* sa_dev, int64_t* out_dev, int64_t n, int device, sa_hip_lcp_stats* stats);
 
+/* ---- (1c) BWT / inverse BWT, libsais-call-compatible ------------------------------------------
+ * BWT with libsais' conventions: the primary index is ISA[0] + 1, U[0] = T[n-1], then T[SA[r]-1] for every rank r with
+ * SA[r] != 0 in rank order; the aux form writes I[t] = ISA[t*r] + 1 for t = 0..(n-1)/r (r a power of two >= 2).
+ * Forward: the suffix array is built on the device and only U (and I) travel back.  Inverse (csrc/bwt.hpp): psi by a
+ * stable counting sort of U, then bounded walks over ruler sets (at most B dependent steps per lane), the rulers ranked
+ * by pointer jumping on the device -- libsais_unbwt with r = n is sequential even in its _omp form.
+ *
+ * Drop-ins (host pointers): same arguments, return codes and n <= 1 behaviour as the reference.  threads is validated
+ * (>= 0) and otherwise ignored; A is validated (non-NULL) and not used; U may be T.  NULL pointers, n < 0, fs < 0, an r
+ * that is not a power of two >= 2 (unbwt: or n), an aux index outside (0, n], and n <= 1 with I[0] != n return -1 before
+ * any device call.  Difference: unbwt never reads freq -- the device computes the histogram of T itself, so a wrong
+ * table cannot misplace anything (the reference decodes garbage there).  Input that is not the BWT of any text returns
+ * 0 as in the reference, with unspecified (but bounded) output.  -2 means more walk rounds or rulers than the bounds
+ * allow (not expected).  They share the process workspace of sa_hip_libsais* and report in sa_hip_last_call_breakdown.
+ * The 64-bit forms take every n the 64-bit build takes, including n > 2^32 - 2 (64-bit indices on the device there). */
+/* replaces libsais_bwt (libsais.h:147, libsais.c:6665) */
+int32_t sa_hip_libsais_bwt(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, int32_t fs, int32_t* freq);
+/* replaces libsais_bwt_omp (libsais.h:203) */
+int32_t sa_hip_libsais_bwt_omp(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, int32_t fs, int32_t* freq, int32_t threads);
+/* replaces libsais_bwt_aux (libsais.h:161, libsais.c:6691) */
+int32_t sa_hip_libsais_bwt_aux(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, int32_t fs, int32_t* freq, int32_t r, int32_t* I);
+/* replaces libsais_bwt_aux_omp (libsais.h:218) */
+int32_t sa_hip_libsais_bwt_aux_omp(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, int32_t fs, int32_t* freq, int32_t r, int32_t* I, int32_t threads);
+/* replaces libsais_unbwt (libsais.h:254, libsais.c:7588) */
+int32_t sa_hip_libsais_unbwt(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, const int32_t* freq, int32_t i);
+/* replaces libsais_unbwt_omp (libsais.h:308) */
+int32_t sa_hip_libsais_unbwt_omp(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, const int32_t* freq, int32_t i, int32_t threads);
+/* replaces libsais_unbwt_aux (libsais.h:280, libsais.c:7598-7614) */
+int32_t sa_hip_libsais_unbwt_aux(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, const int32_t* freq, int32_t r, const int32_t* I);
+/* replaces libsais_unbwt_aux_omp (libsais.h:322) */
+int32_t sa_hip_libsais_unbwt_aux_omp(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, const int32_t* freq, int32_t r, const int32_t* I, int32_t threads);
+/* replace libsais64_bwt / _aux / _omp and libsais64_unbwt / _aux / _omp (libsais64.h:112-209) */
+int64_t sa_hip_libsais64_bwt(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, int64_t fs, int64_t* freq);
+int64_t sa_hip_libsais64_bwt_omp(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, int64_t fs, int64_t* freq, int64_t threads);
+int64_t sa_hip_libsais64_bwt_aux(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, int64_t fs, int64_t* freq, int64_t r, int64_t* I);
+int64_t sa_hip_libsais64_bwt_aux_omp(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, int64_t fs, int64_t* freq, int64_t r, int64_t* I, int64_t threads);
+int64_t sa_hip_libsais64_unbwt(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, const int64_t* freq, int64_t i);
+int64_t sa_hip_libsais64_unbwt_omp(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, const int64_t* freq, int64_t i, int64_t threads);
+int64_t sa_hip_libsais64_unbwt_aux(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, const int64_t* freq, int64_t r, const int64_t* I);
+int64_t sa_hip_libsais64_unbwt_aux_omp(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, const int64_t* freq, int64_t r, const int64_t* I, int64_t threads);
+
+/* Where the device time of a BWT or inverse BWT call went (HIP events) and how its walks ran. */
+typedef struct sa_hip_bwt_stats {
+    uint64_t n;
+    uint64_t rulers;               /* inverse: rulers walked (aux rows, hash-chosen rows, rows claimed by long walks)         */
+    uint64_t longest_walk;         /* inverse: most psi steps one lane ran in one launch (<= the walk bound B)                */
+    uint32_t ruler_rounds;         /* inverse: walk launches (1 + rounds started from claimed rulers)                         */
+    uint32_t rank_rounds;          /* inverse: pointer-jumping rounds (0 on the aux-only plan)                                */
+    uint32_t aux_only;             /* inverse: 1 = aux rows were the rulers, offsets known, no ranking                        */
+    uint32_t pad_;
+    double   psi_ms;               /* inverse: histogram, scan, psi                                                           */
+    double   walk_ms;              /* inverse: ruler placement and walks                                                      */
+    double   rank_ms;
+    double   copy_ms;              /* inverse: staging slots to the output                                                    */
+    double   gather_ms;            /* forward: range check, primary / aux rows, U                                             */
+    double   total_ms;
+} sa_hip_bwt_stats;
+
+/* On device buffers, 64-bit indices (mirror sa_hip_plcp64_device; any n >= 0; synchronous; stats may be NULL).
+ * bwt64: text_dev n bytes, sa_dev n int64 entries, U_dev n bytes (may be text_dev), I_dev NULL or (n-1)/r + 1 int64
+ * entries with r a power of two >= 2.  Returns the primary index (I_dev NULL) or 0 (I_dev given), -1 on bad arguments
+ * or an SA entry outside [0, n).
+ * unbwt64: U_dev n bytes (the BWT), out_dev n bytes (may be U_dev), I_dev (n-1)/r + 1 int64 entries with r == n or a
+ * power of two >= 2.  Returns 0, -1 (bad arguments, an I entry outside (0, n]), -2 (not expected). */
+int64_t sa_hip_bwt64_device(const void* text_dev, const int64_t* sa_dev, void* U_dev, int64_t n, int64_t r, int64_t* I_dev, int device,
+                            sa_hip_bwt_stats* stats);
+int sa_hip_unbwt64_device(const void* U_dev, void* out_dev, int64_t n, int64_t r, const int64_t* I_dev, int device, sa_hip_bwt_stats* stats);
+
 /* ---- (2) truncated construction, engine.c-call-compatible ------------------------------- */
 
 /* replaces construct_truncated_suffix_array (engine.h:213, engine.c:837-866).
@@ -282,6 +350,10 @@ int sa_hip_index_widen_device(sa_hip_index* idx, void* out_dev);
  * for the pass (about 12 bytes per character) stays with the handle. */
 int sa_hip_index_plcp_device(sa_hip_index* idx, void* out_dev, sa_hip_lcp_stats* stats);
 int sa_hip_index_lcp_device(sa_hip_index* idx, void* out_dev, sa_hip_lcp_stats* stats);
+/* BWT of a built or loaded index into U_dev (n bytes on the index's device), libsais conventions (section 1c).  I_dev
+ * NULL: *primary = ISA[0] + 1; else r is a power of two >= 2, I_dev holds (n-1)/r + 1 uint32 entries, I[t] =
+ * ISA[t*r] + 1, and *primary = I[0].  Synchronous.  Truncated indexes and handles without an index return -1. */
+int sa_hip_index_bwt_device(sa_hip_index* idx, void* U_dev, int64_t r, void* I_dev, int64_t* primary, sa_hip_bwt_stats* stats);
 /* 256-bin byte histogram of the indexed text (libsais `freq`). */
 int sa_hip_index_get_freq(sa_hip_index* idx, uint64_t* freq256);
 

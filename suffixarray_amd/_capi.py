@@ -22,6 +22,11 @@ EXPORTS = [
     "sa_hip_libsais_plcp", "sa_hip_libsais_plcp_omp", "sa_hip_libsais_lcp", "sa_hip_libsais_lcp_omp",
     "sa_hip_libsais64_plcp", "sa_hip_libsais64_plcp_omp", "sa_hip_libsais64_lcp", "sa_hip_libsais64_lcp_omp",
     "sa_hip_plcp64_device", "sa_hip_lcp64_device", "sa_hip_index_plcp_device", "sa_hip_index_lcp_device",
+    "sa_hip_libsais_bwt", "sa_hip_libsais_bwt_omp", "sa_hip_libsais_bwt_aux", "sa_hip_libsais_bwt_aux_omp",
+    "sa_hip_libsais_unbwt", "sa_hip_libsais_unbwt_omp", "sa_hip_libsais_unbwt_aux", "sa_hip_libsais_unbwt_aux_omp",
+    "sa_hip_libsais64_bwt", "sa_hip_libsais64_bwt_omp", "sa_hip_libsais64_bwt_aux", "sa_hip_libsais64_bwt_aux_omp",
+    "sa_hip_libsais64_unbwt", "sa_hip_libsais64_unbwt_omp", "sa_hip_libsais64_unbwt_aux", "sa_hip_libsais64_unbwt_aux_omp",
+    "sa_hip_bwt64_device", "sa_hip_unbwt64_device", "sa_hip_index_bwt_device",
     "sa_hip_last_call_breakdown", "sa_hip_release_workspace",
     "sa_hip_construct_truncated_suffix_array", "sa_hip_get_substring_positions",
     "sa_hip_device_count", "sa_hip_index_create", "sa_hip_index_destroy", "sa_hip_index_build",
@@ -111,6 +116,17 @@ class LcpStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BwtStats(C.Structure):
+    """sa_hip_bwt_stats: device time per phase and the walks of one BWT / inverse BWT pass."""
+    _fields_ = [("n", C.c_uint64), ("rulers", C.c_uint64), ("longest_walk", C.c_uint64), ("ruler_rounds", C.c_uint32),
+                ("rank_rounds", C.c_uint32), ("aux_only", C.c_uint32), ("pad_", C.c_uint32), ("psi_ms", C.c_double),
+                ("walk_ms", C.c_double), ("rank_ms", C.c_double), ("copy_ms", C.c_double), ("gather_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
 class ReplicaLayout(C.Structure):
     """sa_hip_replica_layout: what a replica must know about the index it copies (travels as bytes)."""
     _fields_ = [("n", C.c_uint64), ("max_suffix_length", C.c_uint32), ("key_bytes", C.c_uint32), ("bits_per_symbol", C.c_uint32),
@@ -171,6 +187,20 @@ def lib():
     for name in ("sa_hip_plcp64_device", "sa_hip_lcp64_device"):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = [vp, vp, vp, i64, C.c_int, C.POINTER(LcpStats)]
+    for bits, it in ((32, i32), (64, i64)):
+        pre = "sa_hip_libsais" if bits == 32 else "sa_hip_libsais64"
+        for sfx, args in (("_bwt", [vp, vp, vp, it, it, vp]), ("_bwt_aux", [vp, vp, vp, it, it, vp, it, vp]),
+                          ("_unbwt", [vp, vp, vp, it, vp, it]), ("_unbwt_aux", [vp, vp, vp, it, vp, it, vp])):
+            getattr(L, pre + sfx).restype = it
+            getattr(L, pre + sfx).argtypes = args
+            getattr(L, pre + sfx + "_omp").restype = it
+            getattr(L, pre + sfx + "_omp").argtypes = args + [it]
+    L.sa_hip_bwt64_device.restype = i64
+    L.sa_hip_bwt64_device.argtypes = [vp, vp, vp, i64, i64, vp, C.c_int, C.POINTER(BwtStats)]
+    L.sa_hip_unbwt64_device.restype = C.c_int
+    L.sa_hip_unbwt64_device.argtypes = [vp, vp, i64, i64, vp, C.c_int, C.POINTER(BwtStats)]
+    L.sa_hip_index_bwt_device.restype = C.c_int
+    L.sa_hip_index_bwt_device.argtypes = [vp, vp, i64, vp, C.POINTER(i64), C.POINTER(BwtStats)]
     for name in ("sa_hip_index_plcp_device", "sa_hip_index_lcp_device"):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = [vp, vp, C.POINTER(LcpStats)]
@@ -524,6 +554,32 @@ class DeviceIndex:
         self.sync()
         return buf[:n].cpu().numpy().view(np.uint32)
 
+    # -- BWT (sa_hip_index_bwt_device; full suffix arrays only) -----------------------------------
+    def bwt_device(self, U_dev_ptr, r=None, I_dev_ptr=None, stats=False):
+        """BWT of the index into a device buffer of n bytes (libsais conventions).  With r (a power of two >= 2) and
+        I_dev_ptr ((n-1)//r + 1 uint32 entries): the aux rows.  Synchronous.  Returns the primary index, or
+        (primary, stats dict) with stats=True."""
+        st = BwtStats() if stats else None
+        p = C.c_int64(0)
+        check(self._lib.sa_hip_index_bwt_device(self._h, U_dev_ptr, int(r or 0), I_dev_ptr, C.byref(p),
+                                                C.byref(st) if st is not None else None))
+        return (p.value, st.as_dict()) if st is not None else p.value
+
+    def bwt(self, r=None):
+        """(U: uint8[n], primary) -- or, with r, (U, I: int64[(n-1)//r + 1]) as libsais_bwt_aux -- through device buffers
+        taken from torch, as lcp() does."""
+        import torch
+        n = self.n
+        dev = f"cuda:{getattr(self, '_device', 0)}"
+        u = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        aux = torch.empty(max((n - 1) // r + 1, 1), dtype=torch.int32, device=dev) if r else None
+        torch.cuda.synchronize(u.device)
+        p = self.bwt_device(u.data_ptr(), r, aux.data_ptr() if aux is not None else None)
+        U = u[:n].cpu().numpy()
+        if r:
+            return U, aux[:max((n - 1) // r + 1, 1)].cpu().numpy().view(np.uint32).astype(np.int64)
+        return U, p
+
     def deep_keys(self, mode=2):
         """Second-level keys for patterns longer than the key (sa_hip_index_deep_keys): 2 = build now, 1 = large batches build
         them (default of a handle), 0 = drop and never build.  True when the index has them afterwards."""
@@ -751,6 +807,83 @@ def lcp64_device(text_ptr, sa_ptr, out_ptr, n, device=0):
     """LCP (SA order) with 64-bit indices on device buffers, as plcp64_device."""
     st = LcpStats()
     check(lib().sa_hip_lcp64_device(text_ptr, sa_ptr, out_ptr, n, device, C.byref(st)))
+    return st.as_dict()
+
+
+def libsais_bwt(text, r=None, freq=False, threads=0):
+    """BWT through sa_hip_libsais_bwt[_aux]_omp: (U: uint8[n], primary) or, with r, (U, I: int32[(n-1)//r + 1]);
+    freq=True appends the 256-bin int32 histogram."""
+    return _bwt(text, r, freq, threads, 32)
+
+
+def libsais64_bwt(text, r=None, freq=False, threads=0):
+    """As libsais_bwt through sa_hip_libsais64_bwt[_aux]_omp (int64 I and freq)."""
+    return _bwt(text, r, freq, threads, 64)
+
+
+def _bwt(text, r, freq, threads, bits):
+    t = as_u8(text)
+    n = t.size
+    it = np.int32 if bits == 32 else np.int64
+    L = lib()
+    pre = "sa_hip_libsais" if bits == 32 else "sa_hip_libsais64"
+    U = np.empty(max(n, 1), dtype=np.uint8)
+    A = np.empty(1, dtype=it)   # validated, never used
+    f = np.zeros(256, dtype=it)
+    fp = f.ctypes.data if freq else None
+    if r:
+        I = np.zeros((n - 1) // r + 1 if n else 1, dtype=it)
+        rc = int(getattr(L, pre + "_bwt_aux_omp")(t.ctypes.data, U.ctypes.data, A.ctypes.data, n, 0, fp, int(r), I.ctypes.data, threads))
+        check(rc)
+        out = (U[:n], I)
+    else:
+        rc = int(getattr(L, pre + "_bwt_omp")(t.ctypes.data, U.ctypes.data, A.ctypes.data, n, 0, fp, threads))
+        if rc < 0:
+            check(rc)
+        out = (U[:n], rc)
+    return out + (f,) if freq else out
+
+
+def libsais_unbwt(u, primary=None, I=None, r=None, freq=None, threads=0):
+    """Inverse BWT through sa_hip_libsais_unbwt[_aux]_omp: the text as uint8[n].  Either primary, or I with r."""
+    return _unbwt(u, primary, I, r, freq, threads, 32)
+
+
+def libsais64_unbwt(u, primary=None, I=None, r=None, freq=None, threads=0):
+    return _unbwt(u, primary, I, r, freq, threads, 64)
+
+
+def _unbwt(u, primary, I, r, freq, threads, bits):
+    b = as_u8(u)
+    n = b.size
+    it = np.int32 if bits == 32 else np.int64
+    L = lib()
+    pre = "sa_hip_libsais" if bits == 32 else "sa_hip_libsais64"
+    out = np.empty(max(n, 1), dtype=np.uint8)
+    A = np.empty(1, dtype=it)
+    fp = np.ascontiguousarray(freq, dtype=it).ctypes.data if freq is not None else None
+    if I is None:
+        rc = int(getattr(L, pre + "_unbwt_omp")(b.ctypes.data, out.ctypes.data, A.ctypes.data, n, fp, int(primary), threads))
+    else:
+        Ia = np.ascontiguousarray(I, dtype=it)
+        rc = int(getattr(L, pre + "_unbwt_aux_omp")(b.ctypes.data, out.ctypes.data, A.ctypes.data, n, fp, int(r), Ia.ctypes.data, threads))
+    check(rc)
+    return out[:n]
+
+
+def bwt64_device(text_ptr, sa_ptr, u_ptr, n, r=None, I_ptr=None, device=0):
+    """BWT with 64-bit indices on device buffers: (primary or 0, stats dict); I_ptr: (n-1)//r + 1 int64 entries."""
+    st = BwtStats()
+    rc = int(lib().sa_hip_bwt64_device(text_ptr, sa_ptr, u_ptr, n, int(r or 0), I_ptr, device, C.byref(st)))
+    if rc < 0:
+        check(rc)
+    return rc, st.as_dict()
+
+
+def unbwt64_device(u_ptr, out_ptr, n, r, I_ptr, device=0):
+    """Inverse BWT with 64-bit indices on device buffers (r = n for a single primary index in I_ptr[0]).  Returns the stats."""
+    st = BwtStats()
+    check(lib().sa_hip_unbwt64_device(u_ptr, out_ptr, n, int(r), I_ptr, device, C.byref(st)))
     return st.as_dict()
 
 

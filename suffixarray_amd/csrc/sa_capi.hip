@@ -18,6 +18,7 @@
 #include "host_index.hpp"
 #include "comm_rccl.hpp"
 #include "lcp.hpp"
+#include "bwt.hpp"
 #include <memory>
 #include <chrono>
 
@@ -57,6 +58,7 @@ struct sa_hip_index {
     DevBuf qc_hist, qc_off, qc_part, qc_tmp;   // clustering of a large batch over a wide-key index (sa_query.hpp: qcluster_*)
     sa_hip_replica_layout pending{};
     lcp::Workspace lcp_ws;         // sa_hip_index_[p]lcp_device (lcp.hpp)
+    bwt::Workspace bwt_ws;         // sa_hip_index_bwt_device (bwt.hpp)
 };
 
 // multi-GPU lifecycle (comm_rccl.hpp): one communicator per process / GPU
@@ -263,11 +265,15 @@ struct OneShot {
     DevBuf l_text, l_sa, l_in, l_out;
     hipStream_t l_stream = nullptr;
     int l_device = -1;
+    // the BWT drop-ins (sa_hip_libsais[64]_bwt / _unbwt): U / I on the device, the inverse's scratch; same stream
+    bwt::Workspace bwt;
+    DevBuf b_u, b_aux;
     void release_lcp() {
         if (l_device >= 0) (void)hipSetDevice(l_device);
         if (l_stream) (void)hipStreamDestroy(l_stream);
         l_stream = nullptr;
         lcp.release(); l_text.release(); l_sa.release(); l_in.release(); l_out.release();
+        bwt.release(); b_u.release(); b_aux.release();
         l_device = -1;
     }
 } g_oneshot;
@@ -333,6 +339,7 @@ void sa_hip_index_destroy(sa_hip_index* idx) {
     idx->rows_dev.release(); idx->rows_coarse.release(); idx->r_rows.release(); idx->r_counts.release(); idx->r_pending.release();
     idx->qc_hist.release(); idx->qc_off.release(); idx->qc_part.release(); idx->qc_tmp.release();
     idx->lcp_ws.release();
+    idx->bwt_ws.release();
     if (idx->qh_host) (void)hipHostFree(idx->qh_host);
     for (int i = 0; i < sa_hip_index::QRING; ++i)
         for (int k = 0; k < 2; ++k) if (idx->q_ev[i][k]) (void)hipEventDestroy(idx->q_ev[i][k]);
@@ -2089,6 +2096,315 @@ int sa_hip_plcp64_device(const void* text_dev, const int64_t* sa_dev, int64_t* o
 }
 int sa_hip_lcp64_device(const void* text_dev, const int64_t* sa_dev, int64_t* out_dev, int64_t n, int device, sa_hip_lcp_stats* stats) {
     return lcp64_device(text_dev, sa_dev, out_dev, n, device, stats, lcp::Out::LCP, "sa_hip_lcp64_device");
+}
+
+// ---- BWT / inverse BWT (bwt.hpp) ----------------------------------------------------------------------------------------
+
+extern "C++" {
+namespace {
+inline bool pow2_ge2(int64_t r) { return r >= 2 && (r & (r - 1)) == 0; }
+
+// Host drop-in, forward: the suffix array is built on the device (the cached index for n <= 2^32 - 2, big_build.hpp
+// beyond) and only U and I come back.  IO = int32_t / int64_t host entries of I and freq.  n >= 2, arguments checked.
+template <class IO>
+int oneshot_bwt(const uint8_t* T, uint8_t* U, uint64_t n, uint64_t r_aux, IO* I, IO* freq, uint64_t* primary) {
+    const uint64_t m = r_aux ? (n - 1) / r_aux + 1 : 0;
+    if (n > 0xFFFFFFFEull) {   // 64-bit suffix indices: plain device buffers, as big_oneshot
+        if (freq) {   // before U is written: U may be T
+            for (int c = 0; c < 256; ++c) freq[c] = 0;
+            for (uint64_t i = 0; i < n; ++i) ++freq[T[i]];
+        }
+        int rc = set_device(0);
+        if (rc) return rc;
+        DevBuf text, sa, u, aux;
+        bwt::Workspace ws;
+        hipStream_t stream = nullptr;
+        auto body = [&]() -> int {
+            int r;
+            if ((r = text.ensure(n + 64)) || (r = sa.ensure(n * 8 + 64)) || (r = u.ensure(n + 64)) || (m && (r = aux.ensure(m * 8 + 64)))) return r;
+            SA_HIP_CHECK(hipMemcpy(text.p, T, n, hipMemcpyHostToDevice));
+            if ((r = sa_hip_libsais64_device(text.p, sa.as<int64_t>(), (int64_t)n, 0, nullptr))) return r;
+            SA_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            if ((r = bwt::run_bwt<u64>(ws, stream, text.as<u8>(), sa.as<u64>(), n, r_aux, m ? aux.as<u64>() : nullptr, u.as<u8>(), primary, nullptr))) return r;
+            SA_HIP_CHECK(hipMemcpy(U, u.p, n, hipMemcpyDeviceToHost));
+            if (m) SA_HIP_CHECK(hipMemcpy(I, aux.p, m * 8, hipMemcpyDeviceToHost));   // IO = int64_t here
+            return 0;
+        };
+        rc = body();
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        ws.release(); text.release(); sa.release(); u.release(); aux.release();
+        return rc;
+    }
+    OneShot& g = g_oneshot;
+    std::lock_guard<std::mutex> lock(g.mu);
+    const auto t_all = std::chrono::steady_clock::now();
+    sa_hip_call_breakdown bd{};
+    bd.n = n;
+    int rc = 0;
+    auto t0 = std::chrono::steady_clock::now();
+    bd.workspace_reused = (g.idx && g.idx->b.n_max >= n && g.ring.ready && g.b_u.cap >= n + 64) ? 1u : 0u;
+    if (g.idx && g.idx->b.n_max < n) { sa_hip_index_destroy(g.idx); g.idx = nullptr; }
+    if (!g.idx && (rc = sa_hip_index_create(&g.idx, n, 0))) return rc;
+    sa_hip_index* idx = g.idx;
+    std::lock_guard<std::mutex> ilock(idx->mu);
+    if ((rc = set_device(idx->device))) return rc;
+    if (g.l_device >= 0 && g.l_device != idx->device) g.release_lcp();
+    g.l_device = idx->device;
+    if (g.ring.ready && g.ring.device != idx->device) g.ring.destroy();
+    if ((rc = g.ring.init()) || (rc = g.b_u.ensure(n + 64)) || (m && (rc = g.b_aux.ensure(m * 4 + 64)))) return rc;
+    bd.workspace_ms = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    if ((rc = ring_upload(g.ring, idx->stream, idx->device, idx->b.text.p, T, (size_t)n))) return rc;
+    bd.upload_ms = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    idx->has_index = false;
+    idx->widen_ms = 0.0;
+    rc = idx->b.build(n, 0);
+    idx->has_index = (rc == 0);
+    if (rc) return rc;
+    sa_hip_bwt_stats st{};
+    if ((rc = bwt::run_bwt<u32>(g.bwt, idx->stream, idx->b.text.as<u8>(), idx->b.sa, n, r_aux, m ? g.b_aux.as<u32>() : nullptr,
+                                g.b_u.as<u8>(), primary, &st))) return rc;
+    bd.build_ms = ms_since(t0);
+    bd.build_device_ms = idx->b.stats.total_ms + st.total_ms;
+    if (freq) for (int c = 0; c < 256; ++c) freq[c] = (IO)idx->b.freq[c];   // before U is written: U may be T
+    t0 = std::chrono::steady_clock::now();
+    rc = ring_download_pieces(g.ring, idx->device, g.b_u.as<u8>(), (size_t)n, PinnedRing::SLAB_BYTES,
+                              [&](const u8* piece, size_t off, size_t len) { memcpy(U + off, piece, len); });
+    if (rc) return rc;
+    if (m) {
+        std::vector<u32> h(m);
+        SA_HIP_CHECK(hipMemcpy(h.data(), g.b_aux.p, m * 4, hipMemcpyDeviceToHost));
+        for (uint64_t t = 0; t < m; ++t) I[t] = (IO)h[t];
+    }
+    bd.download_ms = ms_since(t0);
+    bd.total_ms = ms_since(t_all);
+    g.last = bd;
+    return 0;
+}
+
+// Host drop-in, inverse: T = the BWT (input), U = the text (output; may be T).  n >= 2, I checked on the host.
+template <class Idx, class IO>
+int oneshot_unbwt_idx(const uint8_t* T, uint8_t* U, uint64_t n, uint64_t r_aux, const IO* I) {
+    OneShot& g = g_oneshot;
+    std::lock_guard<std::mutex> lock(g.mu);
+    const auto t_all = std::chrono::steady_clock::now();
+    sa_hip_call_breakdown bd{};
+    bd.n = n;
+    const uint64_t m = (n - 1) / r_aux + 1;
+    auto t0 = std::chrono::steady_clock::now();
+    const int device = g.idx ? g.idx->device : 0;
+    int rc = set_device(device);
+    if (rc) return rc;
+    if (g.l_device >= 0 && g.l_device != device) g.release_lcp();
+    bd.workspace_reused = (g.l_stream && g.ring.ready && g.b_u.cap >= n + 64 && g.bwt.tmp.cap >= n + 64 &&
+                           g.bwt.psi.cap >= n * sizeof(Idx) + 64) ? 1u : 0u;
+    if (!g.l_stream) SA_HIP_CHECK(hipStreamCreateWithFlags(&g.l_stream, hipStreamNonBlocking));
+    g.l_device = device;
+    if (g.ring.ready && g.ring.device != device) g.ring.destroy();
+    if ((rc = g.ring.init()) || (rc = g.b_u.ensure(n + 64)) || (rc = g.bwt.tmp.ensure(n + 64)) || (rc = g.b_aux.ensure(m * sizeof(Idx) + 64))) return rc;
+    bd.workspace_ms = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    std::vector<Idx> h(m);
+    for (uint64_t t = 0; t < m; ++t) h[t] = (Idx)I[t];
+    SA_HIP_CHECK(hipMemcpy(g.b_aux.p, h.data(), m * sizeof(Idx), hipMemcpyHostToDevice));
+    if ((rc = ring_upload(g.ring, g.l_stream, device, g.b_u.p, T, (size_t)n))) return rc;
+    bd.upload_ms = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    sa_hip_bwt_stats st{};
+    if ((rc = bwt::run_unbwt<Idx>(g.bwt, g.l_stream, g.b_u.as<u8>(), n, g.b_aux.as<Idx>(), r_aux, g.bwt.tmp.as<u8>(), bwt::Knobs::read(), &st)))
+        return rc;
+    bd.build_ms = ms_since(t0);
+    bd.build_device_ms = st.total_ms;
+    t0 = std::chrono::steady_clock::now();
+    rc = ring_download_pieces(g.ring, device, g.bwt.tmp.as<u8>(), (size_t)n, PinnedRing::SLAB_BYTES,
+                              [&](const u8* piece, size_t off, size_t len) { memcpy(U + off, piece, len); });
+    if (rc) return rc;
+    bd.download_ms = ms_since(t0);
+    bd.total_ms = ms_since(t_all);
+    g.last = bd;
+    return 0;
+}
+
+// argument checks of libsais_unbwt_aux (libsais.c:7600-7614), then the device
+template <class IO>
+IO unbwt_dropin(const uint8_t* T, uint8_t* U, const IO* A, IO n, IO r, const IO* I, IO threads, const char* name) {
+    if (T == nullptr || U == nullptr || A == nullptr || n < 0 || (r != n && !pow2_ge2((int64_t)r)) || I == nullptr || threads < 0)
+        return (IO)fail(SA_HIP_EINVAL, name, "invalid arguments");
+    if (n <= 1) {
+        if (I[0] != n) return (IO)fail(SA_HIP_EINVAL, name, "n <= 1 needs I[0] == n");
+        if (n == 1) U[0] = T[0];
+        return 0;
+    }
+    for (IO t = 0; t <= (n - 1) / r; ++t)
+        if (I[t] <= 0 || I[t] > n) return (IO)fail(SA_HIP_EINVAL, name, "an aux index is outside (0, n]");
+    if ((uint64_t)n > 0xFFFFFFFEull) return (IO)oneshot_unbwt_idx<u64, IO>(T, U, (uint64_t)n, (uint64_t)r, I);
+    return (IO)oneshot_unbwt_idx<u32, IO>(T, U, (uint64_t)n, (uint64_t)r, I);
+}
+
+// argument checks and n <= 1 of libsais_bwt / libsais_bwt_aux (libsais.c:6665-6714); r == 0: the plain form
+template <class IO>
+IO bwt_dropin(const uint8_t* T, uint8_t* U, IO* A, IO n, IO fs, IO* freq, IO r, IO* I, IO threads, bool aux, const char* name) {
+    if (T == nullptr || U == nullptr || A == nullptr || n < 0 || fs < 0 || threads < 0 || (aux && (!pow2_ge2((int64_t)r) || I == nullptr)))
+        return (IO)fail(SA_HIP_EINVAL, name, "invalid arguments");
+    if (n <= 1) {
+        if (freq) for (int c = 0; c < 256; ++c) freq[c] = 0;
+        if (n == 1) { U[0] = T[0]; if (freq) ++freq[T[0]]; }
+        if (aux) { I[0] = n; return 0; }
+        return n;
+    }
+    uint64_t p = 0;
+    const int rc = oneshot_bwt<IO>(T, U, (uint64_t)n, aux ? (uint64_t)r : 0, aux ? I : nullptr, freq, &p);
+    if (rc) return (IO)rc;
+    return aux ? (IO)0 : (IO)p;
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t sa_hip_libsais_bwt_omp(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, int32_t fs, int32_t* freq, int32_t threads) {
+    return bwt_dropin<int32_t>(T, U, A, n, fs, freq, 0, nullptr, threads, false, "sa_hip_libsais_bwt");
+}
+int32_t sa_hip_libsais_bwt(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, int32_t fs, int32_t* freq) {
+    return sa_hip_libsais_bwt_omp(T, U, A, n, fs, freq, 0);
+}
+int32_t sa_hip_libsais_bwt_aux_omp(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, int32_t fs, int32_t* freq, int32_t r, int32_t* I, int32_t threads) {
+    return bwt_dropin<int32_t>(T, U, A, n, fs, freq, r, I, threads, true, "sa_hip_libsais_bwt_aux");
+}
+int32_t sa_hip_libsais_bwt_aux(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, int32_t fs, int32_t* freq, int32_t r, int32_t* I) {
+    return sa_hip_libsais_bwt_aux_omp(T, U, A, n, fs, freq, r, I, 0);
+}
+int32_t sa_hip_libsais_unbwt_aux_omp(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, const int32_t* freq, int32_t r, const int32_t* I, int32_t threads) {
+    (void)freq;   // never read: the device computes the histogram itself
+    return unbwt_dropin<int32_t>(T, U, A, n, r, I, threads, "sa_hip_libsais_unbwt_aux");
+}
+int32_t sa_hip_libsais_unbwt_aux(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, const int32_t* freq, int32_t r, const int32_t* I) {
+    return sa_hip_libsais_unbwt_aux_omp(T, U, A, n, freq, r, I, 0);
+}
+int32_t sa_hip_libsais_unbwt_omp(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, const int32_t* freq, int32_t i, int32_t threads) {
+    return sa_hip_libsais_unbwt_aux_omp(T, U, A, n, freq, n, &i, threads);
+}
+int32_t sa_hip_libsais_unbwt(const uint8_t* T, uint8_t* U, int32_t* A, int32_t n, const int32_t* freq, int32_t i) {
+    return sa_hip_libsais_unbwt_aux_omp(T, U, A, n, freq, n, &i, 0);
+}
+int64_t sa_hip_libsais64_bwt_omp(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, int64_t fs, int64_t* freq, int64_t threads) {
+    return bwt_dropin<int64_t>(T, U, A, n, fs, freq, 0, nullptr, threads, false, "sa_hip_libsais64_bwt");
+}
+int64_t sa_hip_libsais64_bwt(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, int64_t fs, int64_t* freq) {
+    return sa_hip_libsais64_bwt_omp(T, U, A, n, fs, freq, 0);
+}
+int64_t sa_hip_libsais64_bwt_aux_omp(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, int64_t fs, int64_t* freq, int64_t r, int64_t* I, int64_t threads) {
+    return bwt_dropin<int64_t>(T, U, A, n, fs, freq, r, I, threads, true, "sa_hip_libsais64_bwt_aux");
+}
+int64_t sa_hip_libsais64_bwt_aux(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, int64_t fs, int64_t* freq, int64_t r, int64_t* I) {
+    return sa_hip_libsais64_bwt_aux_omp(T, U, A, n, fs, freq, r, I, 0);
+}
+int64_t sa_hip_libsais64_unbwt_aux_omp(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, const int64_t* freq, int64_t r, const int64_t* I, int64_t threads) {
+    (void)freq;
+    return unbwt_dropin<int64_t>(T, U, A, n, r, I, threads, "sa_hip_libsais64_unbwt_aux");
+}
+int64_t sa_hip_libsais64_unbwt_aux(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, const int64_t* freq, int64_t r, const int64_t* I) {
+    return sa_hip_libsais64_unbwt_aux_omp(T, U, A, n, freq, r, I, 0);
+}
+int64_t sa_hip_libsais64_unbwt_omp(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, const int64_t* freq, int64_t i, int64_t threads) {
+    return sa_hip_libsais64_unbwt_aux_omp(T, U, A, n, freq, n, &i, threads);
+}
+int64_t sa_hip_libsais64_unbwt(const uint8_t* T, uint8_t* U, int64_t* A, int64_t n, const int64_t* freq, int64_t i) {
+    return sa_hip_libsais64_unbwt_aux_omp(T, U, A, n, freq, n, &i, 0);
+}
+
+int sa_hip_index_bwt_device(sa_hip_index* idx, void* U_dev, int64_t r, void* I_dev, int64_t* primary, sa_hip_bwt_stats* stats) {
+    const char* name = "sa_hip_index_bwt_device";
+    if (!idx) return fail(SA_HIP_EINVAL, name, "NULL index");
+    if (!primary) return fail(SA_HIP_EINVAL, name, "NULL primary");
+    if (I_dev && !pow2_ge2(r)) return fail(SA_HIP_EINVAL, name, "r must be a power of two >= 2");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->host) return fail(SA_HIP_EINVAL, name, "the host path (no HIP device) has no device buffers");
+    if (!idx->has_index) return fail(SA_HIP_EINVAL, name, "no index (build or load one first)");
+    if (idx->b.max_suffix_length > 0)
+        return fail(SA_HIP_EINVAL, name, "truncated index (max_suffix_length > 0): its order is not the suffix order the BWT needs");
+    const u64 n = idx->b.n;
+    if (!U_dev && n) return fail(SA_HIP_EINVAL, name, "NULL output");
+    int rc = set_device(idx->device);
+    if (rc) return rc;
+    if (n <= 1) {
+        if (n == 1) SA_HIP_CHECK(hipMemcpyAsync(U_dev, idx->b.text.p, 1, hipMemcpyDeviceToDevice, idx->stream));
+        if (I_dev) { const u32 v = (u32)n; SA_HIP_CHECK(hipMemcpyAsync(I_dev, &v, 4, hipMemcpyHostToDevice, idx->stream)); }
+        SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
+        if (stats) { memset(stats, 0, sizeof *stats); stats->n = n; }
+        *primary = (int64_t)n;
+        return 0;
+    }
+    u64 p = 0;
+    rc = bwt::run_bwt<u32>(idx->bwt_ws, idx->stream, idx->b.text.as<u8>(), idx->b.sa, n, I_dev ? (u64)r : 0ull, static_cast<u32*>(I_dev),
+                           static_cast<u8*>(U_dev), &p, stats);
+    if (rc) return rc;
+    *primary = (int64_t)p;
+    return 0;
+}
+
+int64_t sa_hip_bwt64_device(const void* text_dev, const int64_t* sa_dev, void* U_dev, int64_t n, int64_t r, int64_t* I_dev, int device,
+                            sa_hip_bwt_stats* stats) {
+    const char* name = "sa_hip_bwt64_device";
+    if (n < 0) return fail(SA_HIP_EINVAL, name, "negative length");
+    if ((!text_dev || !sa_dev || !U_dev) && n) return fail(SA_HIP_EINVAL, name, "NULL argument");
+    if (I_dev && !pow2_ge2(r)) return fail(SA_HIP_EINVAL, name, "r must be a power of two >= 2");
+    if (stats) { memset(stats, 0, sizeof *stats); stats->n = (u64)n; }
+    int rc = set_device(device);
+    if (rc) return rc;
+    if (n <= 1) {
+        if (n == 1 && U_dev != text_dev) SA_HIP_CHECK(hipMemcpy(U_dev, text_dev, 1, hipMemcpyDeviceToDevice));
+        if (I_dev) { const int64_t v = n; SA_HIP_CHECK(hipMemcpy(I_dev, &v, 8, hipMemcpyHostToDevice)); return 0; }
+        return n;
+    }
+    hipStream_t stream = nullptr;
+    SA_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    bwt::Workspace ws;
+    u64 p = 0;
+    auto body = [&]() -> int {
+        const u8* t = static_cast<const u8*>(text_dev);
+        u8* u = static_cast<u8*>(U_dev);
+        const bool overlap = u < t + n && t < u + n;   // U over the text: gather into scratch, then copy
+        u8* dst = u;
+        if (overlap) { int r2 = ws.tmp.ensure((size_t)n + 64); if (r2) return r2; dst = ws.tmp.as<u8>(); }
+        int r2 = bwt::run_bwt<u64>(ws, stream, t, reinterpret_cast<const u64*>(sa_dev), (u64)n, I_dev ? (u64)r : 0ull,
+                                   reinterpret_cast<u64*>(I_dev), dst, &p, stats);
+        if (r2) return r2;
+        if (overlap) { SA_HIP_CHECK(hipMemcpyAsync(u, dst, (size_t)n, hipMemcpyDeviceToDevice, stream)); SA_HIP_CHECK(hipStreamSynchronize(stream)); }
+        return 0;
+    };
+    rc = body();
+    (void)hipStreamSynchronize(stream);
+    ws.release();
+    (void)hipStreamDestroy(stream);
+    if (rc) return rc;
+    return I_dev ? 0 : (int64_t)p;
+}
+
+int sa_hip_unbwt64_device(const void* U_dev, void* out_dev, int64_t n, int64_t r, const int64_t* I_dev, int device, sa_hip_bwt_stats* stats) {
+    const char* name = "sa_hip_unbwt64_device";
+    if (n < 0) return fail(SA_HIP_EINVAL, name, "negative length");
+    if (!I_dev || ((!U_dev || !out_dev) && n)) return fail(SA_HIP_EINVAL, name, "NULL argument");
+    if (r != n && !pow2_ge2(r)) return fail(SA_HIP_EINVAL, name, "r must be n or a power of two >= 2");
+    if (stats) { memset(stats, 0, sizeof *stats); stats->n = (u64)n; }
+    int rc = set_device(device);
+    if (rc) return rc;
+    if (n <= 1) {
+        int64_t i0 = -1;
+        SA_HIP_CHECK(hipMemcpy(&i0, I_dev, 8, hipMemcpyDeviceToHost));
+        if (i0 != n) return fail(SA_HIP_EINVAL, name, "n <= 1 needs I[0] == n");
+        if (n == 1 && out_dev != U_dev) SA_HIP_CHECK(hipMemcpy(out_dev, U_dev, 1, hipMemcpyDeviceToDevice));
+        return 0;
+    }
+    hipStream_t stream = nullptr;
+    SA_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    bwt::Workspace ws;
+    // out may be U: U is read only while psi is built, before the walks write
+    rc = bwt::run_unbwt<u64>(ws, stream, static_cast<const u8*>(U_dev), (u64)n, reinterpret_cast<const u64*>(I_dev), (u64)r,
+                             static_cast<u8*>(out_dev), bwt::Knobs::read(), stats);
+    (void)hipStreamSynchronize(stream);
+    ws.release();
+    (void)hipStreamDestroy(stream);
+    return rc;
 }
 
 }  // extern "C"
