@@ -985,6 +985,23 @@ struct NarrowWorkspace {
     bool split_flags = true;       // SA_HIP_SPLIT_FLAGS=0: the first flags pass stays a pass of its own
     bool local_big = false;        // SA_HIP_LOCAL_BIG=1: always the large form of the local pass (tests, A/B)
     bool split_big = false;        // of the last sort: the local pass ran in its large form
+    bool local_persist = true;     // SA_HIP_LOCAL_PERSIST=0: the local pass as one workgroup per sub-bucket (A/B)
+    u32 local_grid_force = 0;      // SA_HIP_LOCAL_GRID=k: the persistent local pass on k workgroups (tests: one walks thousands of sub-buckets)
+    u32 local_grid[6] = {};        // per instantiation of local_persist_kernel: workgroups resident at once on the device (0: not asked yet)
+    // the persistent local pass's grid: as many workgroups as the device holds at once (occupancy x CUs), asked once per workspace
+    template <typename K>
+    int persist_grid(K kernel, int block, int slot, u32 nsub, u32* grid) {
+        if (!local_grid[slot]) {
+            int dev = 0, cus = 0, per_cu = 0;
+            SA_HIP_CHECK(hipGetDevice(&dev));
+            SA_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+            SA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), block, 0));
+            local_grid[slot] = (u32)((per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1));
+        }
+        const u32 g = local_grid_force ? local_grid_force : local_grid[slot];
+        *grid = g < nsub ? g : nsub;
+        return 0;
+    }
     bool split_flags_done = false; // of the last sort: the local pass has written the directory and staged the active records
     int split_items = 28;          // SA_HIP_SPLIT_ITEMS=24 / 28 / 32: tiles of 12288 / 14336 / 16384 records in the split pass (32 spills 33 registers)
     static size_t hist_bytes() { return (size_t)NARROW_MAX_PASSES * RADIX * RADIX * sizeof(u32); }
@@ -1006,6 +1023,8 @@ struct NarrowWorkspace {
         if (const char* e = diag_env("SA_HIP_TOP_CLAIMS")) top_claims = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_TOP_ARANKS")) top_atomic_ranks = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_LOCAL_BIG")) local_big = atoi(e) != 0;
+        if (const char* e = diag_env("SA_HIP_LOCAL_PERSIST")) local_persist = atoi(e) != 0;
+        if (const char* e = diag_env("SA_HIP_LOCAL_GRID")) { const int v = atoi(e); local_grid_force = v > 0 ? (u32)v : 0u; }
         if (const char* e = diag_env("SA_HIP_SPLIT_ATOMIC")) split_atomic = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_SPLIT_FLAGS")) split_flags = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_LOCAL_BINS")) local_bin_bits = (atoi(e) == 11) ? 11 : 12;
@@ -1261,8 +1280,23 @@ inline int radix_sort_narrow(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_
                 with_flags = (fr == 0) && l.dir.dir && l.dir.dbits >= 8 + rb && l.dir.dbits - 8 - rb <= bb && l.dir.dbits - 8 <= lo_bits;
             }
             if ((rc = ws.timer.start(stream, 3))) return rc;
-            const dim3 lgrid((u32)RADIX << rb), lblock(big ? LOCAL_BLOCK_BIG : LOCAL_BLOCK);
-            if (big) {
+            const u32 nsub = (u32)RADIX << rb;
+            const dim3 lgrid(nsub), lblock(big ? LOCAL_BLOCK_BIG : LOCAL_BLOCK);
+            if (nw.local_persist) {   // as many workgroups as are resident, walking runs of sub-buckets handed out per XCD
+                // (their tickets: the second row of nw.tickets, zeroed with the first at the start of the sort; the LSD passes that
+                //  would use it do not run when this plan is taken)
+                const int slot = big ? (with_flags ? 0 : 1) : 2 + (with_flags ? 0 : 1) + (bb == 12 ? 0 : 2);   // (local_grid[])
+                u32 pg = 0;
+                auto go = [&](auto kernel) -> int {
+                    if ((rc = nw.persist_grid(kernel, (int)lblock.x, slot, nsub, &pg))) return rc;
+                    hipLaunchKernelGGL(kernel, dim3(pg), lblock, 0, stream, l, (const u32*)nw.split_sub, nsub, nw.tickets + NCHUNK, LOCAL_RUN);
+                    return 0;
+                };
+                if (big) rc = with_flags ? go(local_persist_kernel<12, true, LOCAL_BLOCK_BIG>) : go(local_persist_kernel<12, false, LOCAL_BLOCK_BIG>);
+                else if (with_flags) rc = (bb == 12) ? go(local_persist_kernel<12, true>) : go(local_persist_kernel<11, true>);
+                else rc = (bb == 12) ? go(local_persist_kernel<12, false>) : go(local_persist_kernel<11, false>);
+                if (rc) return rc;
+            } else if (big) {
                 if (with_flags) hipLaunchKernelGGL((local_finish_kernel<12, true, LOCAL_BLOCK_BIG>), lgrid, lblock, 0, stream, l);
                 else hipLaunchKernelGGL((local_finish_kernel<12, false, LOCAL_BLOCK_BIG>), lgrid, lblock, 0, stream, l);
             } else if (with_flags) {

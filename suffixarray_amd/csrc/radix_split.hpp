@@ -54,6 +54,7 @@ constexpr int LOCAL_BLOCK = 512;
 constexpr int LOCAL_ITEMS = (int)(LOCAL_CAP / LOCAL_BLOCK);
 constexpr u32 LOCAL_CAP_BIG = 16384;            // ... or, when no level fits that: 1024 threads x 16, 139 KB of LDS, one workgroup per CU
 constexpr int LOCAL_BLOCK_BIG = 1024;
+constexpr u32 LOCAL_RUN = 8;                  // sub-buckets per hand-out of the persistent local pass (local_persist_kernel)
 constexpr int LOCAL_BIN_BITS = 11;            // the key bits below a sub-bucket's that the plan asks for at least (bins of the local pass: 11 or 12 bits)
 constexpr int SPLIT_HIST_COPIES = 4;
 
@@ -436,56 +437,24 @@ struct LocalFlagsRequest {
 // BB: bin bits (11 or 12).  The counters are 16 bits wide, two per LDS word (a sub-bucket holds <= 8192 records), so that
 // 4096 bins cost the 8 KB that 2048 32-bit counters did: 1.8 instead of 3.7 records per bin at n = 1e9, and it is the
 // LARGEST bin among a wave's 64 records that sets the trip count of the counting loop.
-template <int BB, bool FLAGS, int BLOCK = LOCAL_BLOCK>
-__global__ __launch_bounds__(BLOCK, 4) void local_finish_kernel(LocalArgs a) {
+//
+// local_finish_sub orders sub-bucket sb = [s, s + m) (m <= CAP; m >= 2, or m >= 1 under FLAGS) whose records the caller has
+// loaded into key / val (lane tid holds slots j * BLOCK + tid).  On entry s_cw is zero and s_rec free, both behind a barrier.
+// mid() is called once the records are in LDS in their final order and key / val are dead: the persistent form loads the next
+// sub-bucket's records there, and they arrive while this one is stored.  PERSIST: s_cw is zero again on return (cleared behind the last read of the bin starts), so that the next sub-bucket
+// needs no barrier round of its own before its atomics.
+template <int BB, bool FLAGS, int BLOCK, bool PERSIST, typename Mid>
+__device__ __forceinline__ void local_finish_sub(const LocalArgs& a, const u32 sb, const u32 s, const u32 m, u32 (&key)[LOCAL_ITEMS],
+                                                 u32 (&val)[LOCAL_ITEMS], u64* s_rec, u32* s_cw, u32* s_wsum, Mid&& mid) {
     constexpr int ITEMS = LOCAL_ITEMS;
-    constexpr u32 CAP = (u32)BLOCK * ITEMS;
-    constexpr int NB = 1 << BB, WORDS = NB / 2, WPT = WORDS / BLOCK;   // packed counter words, words per thread in the scan
-    static_assert(WPT >= 1 && WPT * BLOCK == WORDS, "the scan covers the counters exactly");
-    static_assert(CAP < 65536, "16-bit counters and starts");
-    __shared__ __attribute__((aligned(16))) u64 s_rec[CAP + 2];
-    __shared__ __attribute__((aligned(16))) u32 s_cw[WORDS + 4];   // counts, then starts, of bins 2w | 2w + 1 << 16; [WORDS] low half: start[NB] = m
-    __shared__ u32 s_wsum[BLOCK / WAVE];
+    constexpr int NB = 1 << BB, WORDS = NB / 2, WPT = WORDS / BLOCK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u32 s = a.sub[blockIdx.x];
-    const u32 m = a.sub[blockIdx.x + 1] - s;
-    // FLAGS: the directory buckets of this sub-bucket's key prefix are [dfirst, dfirst + nd)
     const int g2 = FLAGS ? a.dir.dbits - 8 - a.rb : 0;
-    const u32 dfirst = FLAGS ? (blockIdx.x << g2) : 0u;
-    const u32 nd = FLAGS ? (1u << g2) : 0u;   // directory buckets of this sub-bucket (<= WORDS: the host has checked)
-    if (FLAGS && tid == 0 && blockIdx.x == gridDim.x - 1) a.dir.dir[1u << a.dir.dbits] = a.n;   // the end marker
-    if (m == 0) {
-        if (FLAGS) {   // every bucket of an empty sub-bucket points at the next slot
-            if (!(SA_ABL & 8)) for (u32 e = tid; e < nd; e += BLOCK) a.dir.dir[dfirst + e] = s;
-        }
-        return;
-    }
-    if (m > CAP) {   // cannot happen: the host has seen the largest sub-bucket
-        if (tid == 0) __hip_atomic_store(&a.dstat->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    const u32* kin = a.keys_in + s;
-    const u32* vin = a.vals_in + s;
-    if (!FLAGS && m == 1) {
-        if (tid == 0) {
-            const u32 k = kin[0], v = vin[0];
-            a.keys_out[s] = k; a.vals_out[s] = v;
-            if (a.vals_out64) a.vals_out64[s] = (int64_t)v;
-        }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < WPT; ++i) s_cw[WPT * tid + i] = 0;
-    __syncthreads();
+    const u32 dfirst = FLAGS ? (sb << g2) : 0u;
+    const u32 nd = FLAGS ? (1u << g2) : 0u;
 
-    // 1. load; place inside the bin from one returning LDS atomic per record
-    u32 key[ITEMS], val[ITEMS], r[ITEMS];
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-        const u32 p = (u32)j * BLOCK + tid;
-        key[j] = 0; val[j] = 0;
-        if ((u32)j * BLOCK < m && p < m) { key[j] = kin[p]; val[j] = vin[p]; }
-    }
+    // 1. place inside the bin from one returning LDS atomic per record
+    u32 r[ITEMS];
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
         const u32 p = (u32)j * BLOCK + tid;
@@ -524,10 +493,6 @@ __global__ __launch_bounds__(BLOCK, 4) void local_finish_kernel(LocalArgs a) {
     }
     __syncthreads();
     const u16* s_st = reinterpret_cast<const u16*>(s_cw);   // start of bin b (little endian: the low half is the even bin)
-    // FLAGS: dir[bkt] = first slot whose key's top bits are >= bkt = s + the records of the sub-bucket in lower buckets.  The bins
-    // are the key bits right below the sub-bucket's and at least as fine as the directory (the host has checked g2 <= BB), so
-    // that count is the start of the bucket's first bin: the slice of the directory is the bin-start table, subsampled (written at
-    // the very end, behind the record stores: s_cw is not touched again)
 
     // 3. records -> LDS in bin order
 #pragma unroll
@@ -539,6 +504,11 @@ __global__ __launch_bounds__(BLOCK, 4) void local_finish_kernel(LocalArgs a) {
         }
     }
     __syncthreads();
+    // FLAGS: dir[bkt] = first slot whose key's top bits are >= bkt = s + the records of the sub-bucket in lower buckets.  The bins
+    // are the key bits right below the sub-bucket's and at least as fine as the directory (the host has checked g2 <= BB), so
+    // that count is the start of the bucket's first bin: the slice of the directory is the bin-start table, subsampled (written
+    // here, before the ranking's last read of the bin starts)
+    if (FLAGS && !(SA_ABL & 1)) for (u32 e = tid; e < nd; e += BLOCK) a.dir.dir[dfirst + e] = s + (u32)s_st[e << (BB - g2)];
 
     // 4. final place of slot p: its bin's start + the records of the bin that compare smaller (key, then suffix);
     //    two records of the bin per step (one ds_read2_b64)
@@ -562,13 +532,20 @@ __global__ __launch_bounds__(BLOCK, 4) void local_finish_kernel(LocalArgs a) {
         }
     }
     __syncthreads();
+    if (PERSIST) {   // the last read of the bin starts is behind us: the counters of the next sub-bucket (ordered by the barrier below)
+#pragma unroll
+        for (int i = 0; i < WPT; ++i) s_cw[WPT * tid + i] = 0;
+    }
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
         const u32 p = (u32)j * BLOCK + tid;
         if ((u32)j * BLOCK < m && p < m) s_rec[r[j]] = rec[j];
     }
-    if (FLAGS && tid == 0) s_rec[m] = ~0ull;   // (the slot after the last one: never equal to a key)
+    // (the slot after the last one: never equal to a key.  ~0 made from m -- which is < 2^31 -- in a scalar register: as a
+    //  constant the persistent form keeps it in a register pair across its walk, and spills it)
+    if (FLAGS && tid == 0) { const u64 ones = ~(u64)(m >> 31); s_rec[m] = ones; }
     __syncthreads();
+    mid();   // (here, ahead of the stores: beside the ranking's registers -- after step 3, or above this barrier -- they spill)
 
     // 5. out, coalesced: nothing but the loads and stores, unrolled -- this loop is what the pass's bandwidth hangs on (as a rolled
     //    loop over the slots: 4.9 -> 7.5 ms at n = 1e9; with a per-slot flags body inside its sixteen copies: 6.8-7.3 ms; a second
@@ -584,23 +561,22 @@ __global__ __launch_bounds__(BLOCK, 4) void local_finish_kernel(LocalArgs a) {
         const bool starts = (p == 0) || ((u32)(s_rec[p - 1] >> 32) != (u32)(x >> 32));
         // (the sub-bucket's {active, heads} pair lives in global memory, zeroed by the host: the few threads that get here add to
         //  it, and the kernel needs neither a counter in LDS nor a barrier at its end)
-        u32 at = atomicAdd(&a.counts[blockIdx.x].x, starts ? 2u : 1u);
+        u32 at = atomicAdd(&a.counts[sb].x, starts ? 2u : 1u);
         if (at + (starts ? 2u : 1u) > LITE_CAP) __hip_atomic_store(a.lite.overflow, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (starts) {
-            atomicAdd(&a.counts[blockIdx.x].y, 1u);
+            atomicAdd(&a.counts[sb].y, 1u);
             if (at < LITE_CAP) {
-                const u64 row = (u64)blockIdx.x * LITE_CAP + at;
+                const u64 row = (u64)sb * LITE_CAP + at;
                 a.lite.st_pos[row] = s + p; a.lite.st_idx[row] = (u32)x; a.lite.st_head[row] = 1;
             }
             ++at;
         }
         if (at < LITE_CAP) {
-            const u64 row = (u64)blockIdx.x * LITE_CAP + at;
+            const u64 row = (u64)sb * LITE_CAP + at;
             a.lite.st_pos[row] = s + p + 1; a.lite.st_idx[row] = (u32)xn; a.lite.st_head[row] = 0;
         }
     };
     if (FLAGS) {
-        if (!(SA_ABL & 1)) for (u32 e = tid; e < nd; e += BLOCK) a.dir.dir[dfirst + e] = s + (u32)s_st[e << (BB - g2)];
         // the pairs across a row of 16 lanes (slots 16 t + 15 | 16 t + 16)
         if (!(SA_ABL & 4))
         for (u32 p = (u32)tid * 16u + 15u; p + 1 < m; p += (u32)BLOCK * 16u)
@@ -632,6 +608,168 @@ __global__ __launch_bounds__(BLOCK, 4) void local_finish_kernel(LocalArgs a) {
             tmask &= tmask - 1u;
             stage_pair(j * BLOCK + (u32)tid);
         }
+    }
+}
+
+// the records of sub-bucket [s, s + m) into registers: lane tid takes slots j * BLOCK + tid
+template <int BLOCK>
+__device__ __forceinline__ void local_load(const LocalArgs& a, const u32 s, const u32 m, u32 (&key)[LOCAL_ITEMS], u32 (&val)[LOCAL_ITEMS]) {
+    const u32* kin = a.keys_in + s;
+    const u32* vin = a.vals_in + s;
+#pragma unroll
+    for (int j = 0; j < LOCAL_ITEMS; ++j) {
+        const u32 p = (u32)j * BLOCK + threadIdx.x;
+        key[j] = 0; val[j] = 0;
+        if ((u32)j * BLOCK < m && p < m) { key[j] = kin[p]; val[j] = vin[p]; }
+    }
+}
+
+// What a sub-bucket that takes no barrier round needs: an empty one its directory entries (every bucket of it points at the next
+// slot), a single record (without FLAGS) its copy, one beyond CAP the error (cannot happen: the host has seen the largest
+// sub-bucket).  Returns false for the sub-buckets that local_finish_sub orders.
+template <bool FLAGS, int BLOCK>
+__device__ __forceinline__ bool local_short_sub(const LocalArgs& a, const u32 sb, const u32 s, const u32 m, const u32 cap) {
+    if (m == 0) {
+        if (FLAGS && !(SA_ABL & 8)) {
+            const int g2 = a.dir.dbits - 8 - a.rb;
+            const u32 dfirst = sb << g2, nd = 1u << g2;
+            for (u32 e = threadIdx.x; e < nd; e += BLOCK) a.dir.dir[dfirst + e] = s;
+        }
+        return true;
+    }
+    if (m > cap) {
+        if (threadIdx.x == 0) __hip_atomic_store(&a.dstat->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return true;
+    }
+    if (!FLAGS && m == 1) {
+        if (threadIdx.x == 0) {
+            const u32 k = a.keys_in[s], v = a.vals_in[s];
+            a.keys_out[s] = k; a.vals_out[s] = v;
+            if (a.vals_out64) a.vals_out64[s] = (int64_t)v;
+        }
+        return true;
+    }
+    return false;
+}
+
+// One sub-bucket per workgroup (SA_HIP_LOCAL_PERSIST=0: the A/B form; 137 781 non-empty workgroups at n = 1e9)
+template <int BB, bool FLAGS, int BLOCK = LOCAL_BLOCK>
+__global__ __launch_bounds__(BLOCK, 4) void local_finish_kernel(LocalArgs a) {
+    constexpr u32 CAP = (u32)BLOCK * LOCAL_ITEMS;
+    constexpr int NB = 1 << BB, WORDS = NB / 2, WPT = WORDS / BLOCK;   // packed counter words, words per thread in the scan
+    static_assert(WPT >= 1 && WPT * BLOCK == WORDS, "the scan covers the counters exactly");
+    static_assert(CAP < 65536, "16-bit counters and starts");
+    __shared__ __attribute__((aligned(16))) u64 s_rec[CAP + 2];
+    __shared__ __attribute__((aligned(16))) u32 s_cw[WORDS + 4];   // counts, then starts, of bins 2w | 2w + 1 << 16; [WORDS] low half: start[NB] = m
+    __shared__ u32 s_wsum[BLOCK / WAVE];
+    const u32 sb = blockIdx.x;
+    const u32 s = a.sub[sb];
+    const u32 m = a.sub[sb + 1] - s;
+    if (FLAGS && threadIdx.x == 0 && sb == gridDim.x - 1) a.dir.dir[1u << a.dir.dbits] = a.n;   // the end marker
+    if (local_short_sub<FLAGS, BLOCK>(a, sb, s, m, CAP)) return;
+#pragma unroll
+    for (int i = 0; i < WPT; ++i) s_cw[WPT * threadIdx.x + i] = 0;
+    __syncthreads();
+    u32 key[LOCAL_ITEMS], val[LOCAL_ITEMS];
+    local_load<BLOCK>(a, s, m, key, val);
+    local_finish_sub<BB, FLAGS, BLOCK, false>(a, sb, s, m, key, val, s_rec, s_cw, s_wsum, [] {});
+}
+
+// first i in [0, nsub] with i == nsub or sub[i] >= t, by one wave: a 64-way search (three rounds of loads for 2^18 sub-buckets)
+__device__ __forceinline__ u32 wave_lower_bound(const u32* __restrict__ sub, const u32 nsub, const u64 t) {
+    const u32 lane = threadIdx.x & 63u;
+    u32 lo = 0, hi = nsub;   // the answer lies in [lo, hi]; sub[< lo] < t, sub[>= hi] >= t
+    while (lo < hi) {
+        const u32 step = (hi - lo + 63u) / 64u;
+        const u32 i = lo + lane * step;
+        const u32 c = (u32)__popcll(__ballot(i < hi && (u64)sub[i] < t));   // the lanes below the answer: a prefix
+        if (c == 0) break;                                                  // sub[lo] >= t
+        const u32 nlo = lo + (c - 1u) * step + 1u;
+        hi = (lo + c * step < hi) ? lo + c * step : hi;
+        lo = nlo;
+    }
+    return lo;
+}
+
+// Persistent form: a grid of as many workgroups as are resident at once (the host's occupancy figure, or SA_HIP_LOCAL_GRID), each
+// ordering one sub-bucket after the other, the next one's records loaded while the current one is stored (local_finish_sub's
+// mid()), so that a workgroup's own loads overlap its stores, not only the other workgroup's on the CU.  Sub-buckets that take
+// no barrier round (empty; one record) are done in passing while the next one to order is looked for.
+// The work is handed out in RUNS of `run` consecutive sub-buckets, one ticket word per XCD: region x = the sub-buckets that start
+// in [x n / NCHUNK, (x + 1) n / NCHUNK) (balanced by records), its runs in order to the workgroups of XCD x, then to any other
+// XCD's once x's are gone.  So the workgroups of an XCD work side by side in one window of the arrays, as one workgroup per
+// sub-bucket in dispatch order did (measured: a fixed contiguous range of n / G records per workgroup -- 512 far-apart streams
+// -- took the pass from 5.9 to 10.4 ms at n = 1e9).
+template <int BB, bool FLAGS, int BLOCK = LOCAL_BLOCK>
+__global__ __launch_bounds__(BLOCK, 4) void local_persist_kernel(LocalArgs a, const u32* __restrict__ sub, u32 nsub, u32* ticket, u32 run) {
+    constexpr u32 CAP = (u32)BLOCK * LOCAL_ITEMS;
+    constexpr int NB = 1 << BB, WORDS = NB / 2, WPT = WORDS / BLOCK;
+    static_assert(WPT >= 1 && WPT * BLOCK == WORDS, "the scan covers the counters exactly");
+    static_assert(CAP < 65536, "16-bit counters and starts");
+    static_assert(BLOCK >= (NCHUNK - 1) * WAVE, "a wave per region bound");
+    __shared__ __attribute__((aligned(16))) u64 s_rec[CAP + 2];
+    __shared__ __attribute__((aligned(16))) u32 s_cw[WORDS + 4];
+    __shared__ u32 s_wsum[BLOCK / WAVE];
+    __shared__ u32 s_reg[NCHUNK + 1];   // first sub-bucket of every region, [NCHUNK] = nsub
+    __shared__ u32 s_run[2];
+    const int tid = threadIdx.x;
+    {   // wave v finds the first sub-bucket of region v + 1
+        const u32 v = (u32)(tid >> 6);
+        if (v + 1 < (u32)NCHUNK) {
+            const u32 b = wave_lower_bound(sub, nsub, (u64)(v + 1) * sub[nsub] / NCHUNK);
+            if ((tid & 63) == 0) s_reg[v + 1] = b;
+        }
+        if (tid == 0) { s_reg[0] = 0; s_reg[NCHUNK] = nsub; }
+    }
+#pragma unroll
+    for (int i = 0; i < WPT; ++i) s_cw[WPT * tid + i] = 0;
+    __syncthreads();
+    const u32 home = xcc_id() & (NCHUNK - 1);
+    // (the walk's indices in scalar registers, and sub[] a restrict argument that nothing here writes: its reads are then scalar
+    //  loads, which no wait for the vector memory counter -- the prefetched records, the stores in flight -- has to cover)
+    u32 lo = 0, hi = 0;   // the run in hand
+    auto grab = [&] {     // workgroup-uniform: the next run, from the home region first; lo == hi: none is left
+        if (tid == 0) {
+            u32 r0 = 0, r1 = 0;
+            for (int k = 0; k < NCHUNK; ++k) {
+                const u32 c = (home + (u32)k) & (NCHUNK - 1);
+                const u32 b0 = s_reg[c], b1 = s_reg[c + 1];
+                if (b0 >= b1) continue;
+                const u64 st = (u64)b0 + (u64)atomicAdd(&ticket[c], 1u) * run;
+                if (st < b1) { r0 = (u32)st; r1 = (st + run < b1) ? (u32)(st + run) : b1; break; }
+            }
+            s_run[0] = r0; s_run[1] = r1;
+        }
+        __syncthreads();
+        lo = __builtin_amdgcn_readfirstlane(s_run[0]);
+        hi = __builtin_amdgcn_readfirstlane(s_run[1]);
+        __syncthreads();   // (read by all before the next grab writes it)
+    };
+    // the next sub-bucket from i on that local_finish_sub orders, the ones before it done in passing; its start and size.
+    // nsub: the work is done.
+    auto next = [&](u32 i, u32& s, u32& m) -> u32 {
+        for (;; ++i) {
+            if (i >= hi) {
+                grab();
+                if (lo >= hi) return nsub;
+                i = lo;
+            }
+            s = sub[i]; m = sub[i + 1] - s;
+            if (FLAGS && tid == 0 && i == nsub - 1) a.dir.dir[1u << a.dir.dbits] = a.n;   // the end marker
+            if (!local_short_sub<FLAGS, BLOCK>(a, i, s, m, CAP)) return i;
+        }
+    };
+    u32 key[LOCAL_ITEMS], val[LOCAL_ITEMS];
+    u32 s = 0, m = 0;
+    u32 i = next(0, s, m);
+    if (i < nsub) local_load<BLOCK>(a, s, m, key, val);
+    while (i < nsub) {
+        u32 ns = 0, nm = 0;
+        const u32 nx = next(i + 1, ns, nm);   // (scalar loads and the short sub-buckets' stores, ahead of this one's barriers)
+        local_finish_sub<BB, FLAGS, BLOCK, true>(a, i, s, m, key, val, s_rec, s_cw, s_wsum, [&] {
+            if (nx < nsub) local_load<BLOCK>(a, ns, nm, key, val);
+        });
+        i = nx; s = ns; m = nm;
     }
 }
 
