@@ -225,6 +225,66 @@ int64_t sa_hip_bwt64_device(const void* text_dev, const int64_t* sa_dev, void* U
                             sa_hip_bwt_stats* stats);
 int sa_hip_unbwt64_device(const void* U_dev, void* out_dev, int64_t n, int64_t r, const int64_t* I_dev, int device, sa_hip_bwt_stats* stats);
 
+/* ---- (1d) integer alphabets, libsais-call-compatible --------------------------------------------
+ * Suffix arrays of texts of int32 / int64 symbols in [0, k) (token ids, remapped byte texts, reduced strings), bit for bit
+ * the reference's: a suffix that ends sorts before every suffix that continues.  On the device (csrc/int_build.hpp): one
+ * alphabet pass (min, max; with max + 1 <= 2^24 a presence table and its scan give dense codes 1 + rank and sigma), then
+ *   route A (sigma <= 256, n <= 2^32 - 2): the rank of every symbol as a byte, and the byte build of sa_hip_libsais;
+ *   route B (everything else): floor(64 / b) codes of b bits per suffix as the initial key, the radix sort and prefix doubling
+ *   of the 64-bit build (sa_hip_libsais64_device), narrowed to int32 for libsais_int.  About 40 bytes of HBM per symbol plus
+ *   the text; -2 beyond what the device holds.
+ * Cases answered on the host before any HIP call: NULL T or SA, n < 0, fs < 0, threads < 0 -> -1; n == 0 -> 0; n == 1 ->
+ * SA[0] = 0 and 0 (T[0] not looked at, libsais.c:6640); k < 1 with n >= 2 -> -1.  T is never written (the reference may
+ * modify and restore it); SA[n .. n+fs) is never touched; threads is validated and otherwise ignored.
+ * Deliberate deviation: a symbol outside [0, k) (undefined behaviour in the reference) is found by the alphabet pass and
+ * returns -1, with sa_hip_last_error() naming the first such position and value; SA[0..n) is then undefined and the next
+ * call works normally.  -2: out of device memory; -3: no usable HIP device.  The drop-ins share the process workspace of
+ * sa_hip_libsais* (the pinned slabs; route A: the cached index) and report in sa_hip_last_call_breakdown. */
+/* replaces libsais_int (libsais.h:96, libsais.c:6634) */
+int32_t sa_hip_libsais_int(int32_t* T, int32_t* SA, int32_t n, int32_t k, int32_t fs);
+/* replaces libsais_int_omp (libsais.h:134, libsais.c:6809) */
+int32_t sa_hip_libsais_int_omp(int32_t* T, int32_t* SA, int32_t n, int32_t k, int32_t fs, int32_t threads);
+/* replaces libsais64_long (libsais64.h:73, libsais64.c:6687); any n the device holds, including n > 2^32 - 2 (route B) */
+int64_t sa_hip_libsais64_long(int64_t* T, int64_t* SA, int64_t n, int64_t k, int64_t fs);
+/* replaces libsais64_long_omp (libsais64.h:99, libsais64.c:6815) */
+int64_t sa_hip_libsais64_long_omp(int64_t* T, int64_t* SA, int64_t n, int64_t k, int64_t fs, int64_t threads);
+/* replaces libsais_plcp_int (libsais.h:343, libsais.c:7887): PLCP over int32 symbols by the irreducible method of (1b); every
+ * SA entry is range-checked on the device, an entry outside [0, n) returns -1.  n == 1 gives PLCP[0] = 0 on the host.
+ * sa_hip_libsais_lcp turns its result into LCP unchanged. */
+int32_t sa_hip_libsais_plcp_int(const int32_t* T, const int32_t* SA, int32_t* PLCP, int32_t n);
+/* replaces libsais_plcp_int_omp (libsais.h:376, libsais.c:7944) */
+int32_t sa_hip_libsais_plcp_int_omp(const int32_t* T, const int32_t* SA, int32_t* PLCP, int32_t n, int32_t threads);
+
+/* How an integer build ran (device forms below). */
+typedef struct sa_hip_int_stats {
+    uint64_t n;
+    uint32_t plan;                 /* 0 = byte pipeline (route A), 1 = integer keys (route B)                                 */
+    uint32_t sigma;                /* distinct symbols; 0 = not counted (max + 1 > 2^24, or compaction off)                   */
+    uint32_t compacted;            /* 1: codes are 1 + the rank of the symbol; 0: raw v + 1                                   */
+    uint32_t bits_per_symbol;      /* code width in the initial key                                                           */
+    uint32_t symbols_per_key;      /* symbols in the initial key (route B: the first doubling step)                           */
+    uint32_t sort_passes;          /* radix passes (route A: onesweep launches; route B: 8-bit passes over (u64, u64) records) */
+    uint32_t rounds;               /* refinement (route A) or prefix-doubling (route B) rounds                                */
+    uint32_t pad_;
+    uint64_t tied_after_sort;      /* route B: suffixes still tied after the initial sort                                     */
+    uint64_t tied_total;           /* sum over the rounds of the tied suffixes they looked at                                 */
+    int64_t  min_symbol;
+    int64_t  max_symbol;
+    double   alphabet_ms;          /* device time of the alphabet pass                                                        */
+    double   total_ms;             /* device time of the whole call (allocation excluded)                                     */
+} sa_hip_int_stats;
+
+/* On device buffers, synchronous, stats may be NULL; same results and error codes as the drop-ins (n == 1 writes SA_dev[0] = 0).
+ * T_dev is only read.  libsais64_long_device writes SA_dev as the 64-bit build's sort buffer. */
+int sa_hip_libsais_int_device(const int32_t* T_dev, int32_t* SA_dev, int32_t n, int32_t k, int device, sa_hip_int_stats* stats);
+int sa_hip_libsais64_long_device(const int64_t* T_dev, int64_t* SA_dev, int64_t n, int64_t k, int device, sa_hip_int_stats* stats);
+/* PLCP of an int32 text on device buffers (a T_dev that is not 8-byte aligned, or of odd n, is copied into a padded buffer
+ * first); an SA entry outside [0, n) returns -1. */
+int sa_hip_plcp_int_device(const int32_t* T_dev, const int32_t* SA_dev, int32_t* PLCP_dev, int32_t n, int device, sa_hip_lcp_stats* stats);
+/* sufcheck of an int64 text: *violations = slots at which SA_dev is not a permutation of [0, n) in suffix order (0 <=> it is
+ * THE suffix array of T_dev; 8 n bytes of scratch) */
+int sa_hip_sufcheck_long_device(const int64_t* T_dev, const int64_t* SA_dev, int64_t n, int device, uint64_t* violations);
+
 /* ---- (2) truncated construction, engine.c-call-compatible ------------------------------- */
 
 /* replaces construct_truncated_suffix_array (engine.h:213, engine.c:837-866).

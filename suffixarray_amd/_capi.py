@@ -27,6 +27,9 @@ EXPORTS = [
     "sa_hip_libsais64_bwt", "sa_hip_libsais64_bwt_omp", "sa_hip_libsais64_bwt_aux", "sa_hip_libsais64_bwt_aux_omp",
     "sa_hip_libsais64_unbwt", "sa_hip_libsais64_unbwt_omp", "sa_hip_libsais64_unbwt_aux", "sa_hip_libsais64_unbwt_aux_omp",
     "sa_hip_bwt64_device", "sa_hip_unbwt64_device", "sa_hip_index_bwt_device",
+    "sa_hip_libsais_int", "sa_hip_libsais_int_omp", "sa_hip_libsais64_long", "sa_hip_libsais64_long_omp",
+    "sa_hip_libsais_plcp_int", "sa_hip_libsais_plcp_int_omp", "sa_hip_libsais_int_device", "sa_hip_libsais64_long_device",
+    "sa_hip_plcp_int_device", "sa_hip_sufcheck_long_device",
     "sa_hip_last_call_breakdown", "sa_hip_release_workspace",
     "sa_hip_construct_truncated_suffix_array", "sa_hip_get_substring_positions",
     "sa_hip_device_count", "sa_hip_index_create", "sa_hip_index_destroy", "sa_hip_index_build",
@@ -127,6 +130,17 @@ class BwtStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
 
 
+class IntStats(C.Structure):
+    """sa_hip_int_stats: the route and the work of one integer-alphabet build."""
+    _fields_ = [("n", C.c_uint64), ("plan", C.c_uint32), ("sigma", C.c_uint32), ("compacted", C.c_uint32), ("bits_per_symbol", C.c_uint32),
+                ("symbols_per_key", C.c_uint32), ("sort_passes", C.c_uint32), ("rounds", C.c_uint32), ("pad_", C.c_uint32),
+                ("tied_after_sort", C.c_uint64), ("tied_total", C.c_uint64), ("min_symbol", C.c_int64), ("max_symbol", C.c_int64),
+                ("alphabet_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
 class ReplicaLayout(C.Structure):
     """sa_hip_replica_layout: what a replica must know about the index it copies (travels as bytes)."""
     _fields_ = [("n", C.c_uint64), ("max_suffix_length", C.c_uint32), ("key_bytes", C.c_uint32), ("bits_per_symbol", C.c_uint32),
@@ -200,6 +214,26 @@ def lib():
     L.sa_hip_unbwt64_device.restype = C.c_int
     L.sa_hip_unbwt64_device.argtypes = [vp, vp, i64, i64, vp, C.c_int, C.POINTER(BwtStats)]
     L.sa_hip_index_bwt_device.restype = C.c_int
+    L.sa_hip_libsais_int.restype = i32
+    L.sa_hip_libsais_int.argtypes = [vp, vp, i32, i32, i32]
+    L.sa_hip_libsais_int_omp.restype = i32
+    L.sa_hip_libsais_int_omp.argtypes = [vp, vp, i32, i32, i32, i32]
+    L.sa_hip_libsais64_long.restype = i64
+    L.sa_hip_libsais64_long.argtypes = [vp, vp, i64, i64, i64]
+    L.sa_hip_libsais64_long_omp.restype = i64
+    L.sa_hip_libsais64_long_omp.argtypes = [vp, vp, i64, i64, i64, i64]
+    L.sa_hip_libsais_plcp_int.restype = i32
+    L.sa_hip_libsais_plcp_int.argtypes = [vp, vp, vp, i32]
+    L.sa_hip_libsais_plcp_int_omp.restype = i32
+    L.sa_hip_libsais_plcp_int_omp.argtypes = [vp, vp, vp, i32, i32]
+    L.sa_hip_libsais_int_device.restype = C.c_int
+    L.sa_hip_libsais_int_device.argtypes = [vp, vp, i32, i32, C.c_int, C.POINTER(IntStats)]
+    L.sa_hip_libsais64_long_device.restype = C.c_int
+    L.sa_hip_libsais64_long_device.argtypes = [vp, vp, i64, i64, C.c_int, C.POINTER(IntStats)]
+    L.sa_hip_plcp_int_device.restype = C.c_int
+    L.sa_hip_plcp_int_device.argtypes = [vp, vp, vp, i32, C.c_int, C.POINTER(LcpStats)]
+    L.sa_hip_sufcheck_long_device.restype = C.c_int
+    L.sa_hip_sufcheck_long_device.argtypes = [vp, vp, i64, C.c_int, C.POINTER(u64)]
     L.sa_hip_index_bwt_device.argtypes = [vp, vp, i64, vp, C.POINTER(i64), C.POINTER(BwtStats)]
     for name in ("sa_hip_index_plcp_device", "sa_hip_index_lcp_device"):
         getattr(L, name).restype = C.c_int
@@ -891,6 +925,74 @@ def sufcheck64_device(text_ptr, sa_ptr, n, device=0):
     """Slots at which the int64 array on the device is not the suffix array of the text (0 = it is)."""
     v = C.c_uint64(0)
     check(lib().sa_hip_sufcheck64_device(text_ptr, sa_ptr, n, device, C.byref(v)))
+    return int(v.value)
+
+
+def _int_text(T, dtype):
+    t = np.asarray(T)
+    if t.dtype != dtype:
+        if t.size and (int(t.min()) < np.iinfo(dtype).min or int(t.max()) > np.iinfo(dtype).max):
+            raise ValueError("symbol does not fit %s" % np.dtype(dtype).name)
+        t = t.astype(dtype)
+    return np.ascontiguousarray(t)
+
+
+def _int_k(t, k):
+    return int(t.max()) + 1 if (k is None and t.size) else (1 if k is None else int(k))
+
+
+def libsais_int(T, k=None, threads=0):
+    """Suffix array of an int32 text with symbols in [0, k) through sa_hip_libsais_int_omp (k defaults to max + 1): int32[n].
+    T is not modified."""
+    t = _int_text(T, np.int32)
+    sa = np.empty(max(t.size, 1), dtype=np.int32)
+    check(int(lib().sa_hip_libsais_int_omp(t.ctypes.data, sa.ctypes.data, t.size, _int_k(t, k), 0, threads)))
+    return sa[:t.size]
+
+
+def libsais64_long(T, k=None, threads=0):
+    """As libsais_int for int64 texts through sa_hip_libsais64_long_omp: int64[n]."""
+    t = _int_text(T, np.int64)
+    sa = np.empty(max(t.size, 1), dtype=np.int64)
+    check(int(lib().sa_hip_libsais64_long_omp(t.ctypes.data, sa.ctypes.data, t.size, _int_k(t, k), 0, threads)))
+    return sa[:t.size]
+
+
+def libsais_plcp_int(T, SA):
+    """PLCP of (int32 text, suffix array) through sa_hip_libsais_plcp_int: int32[n] in text order."""
+    t = _int_text(T, np.int32)
+    s = np.ascontiguousarray(SA, dtype=np.int32)
+    assert s.size == t.size
+    out = np.empty(max(t.size, 1), dtype=np.int32)
+    check(int(lib().sa_hip_libsais_plcp_int(t.ctypes.data, s.ctypes.data, out.ctypes.data, t.size)))
+    return out[:t.size]
+
+
+def libsais_int_device(T_ptr, SA_ptr, n, k, device=0):
+    """The int32 build on device buffers: T_ptr n int32 symbols in [0, k), SA_ptr n int32 entries.  Returns the stats."""
+    st = IntStats()
+    check(lib().sa_hip_libsais_int_device(T_ptr, SA_ptr, n, k, device, C.byref(st)))
+    return st.as_dict()
+
+
+def libsais64_long_device(T_ptr, SA_ptr, n, k, device=0):
+    """The int64 build on device buffers: T_ptr n int64 symbols in [0, k), SA_ptr n int64 entries.  Returns the stats."""
+    st = IntStats()
+    check(lib().sa_hip_libsais64_long_device(T_ptr, SA_ptr, n, k, device, C.byref(st)))
+    return st.as_dict()
+
+
+def plcp_int_device(T_ptr, SA_ptr, out_ptr, n, device=0):
+    """PLCP of an int32 text on device buffers (T, SA, out: n int32 entries each).  Returns the stats."""
+    st = LcpStats()
+    check(lib().sa_hip_plcp_int_device(T_ptr, SA_ptr, out_ptr, n, device, C.byref(st)))
+    return st.as_dict()
+
+
+def sufcheck_long_device(T_ptr, SA_ptr, n, device=0):
+    """Slots at which the int64 array on the device is not the suffix array of the int64 text (0 = it is)."""
+    v = C.c_uint64(0)
+    check(lib().sa_hip_sufcheck_long_device(T_ptr, SA_ptr, n, device, C.byref(v)))
     return int(v.value)
 
 

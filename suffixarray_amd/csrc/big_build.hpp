@@ -384,7 +384,8 @@ __global__ __launch_bounds__(256) void bg_inverse_kernel(const u64* __restrict__
         if (s < n) inv[s] = j; else atomicAdd(bad, 1ull);
     }
 }
-__global__ __launch_bounds__(256) void bg_order_kernel(const u8* __restrict__ text, const u64* __restrict__ sa, u64 n, const u64* __restrict__ inv,
+template <class S>   // symbol type: u8 (bytes), int64_t (sa_hip_sufcheck_long_device)
+__global__ __launch_bounds__(256) void bg_order_kernel(const S* __restrict__ text, const u64* __restrict__ sa, u64 n, const u64* __restrict__ inv,
                                                        unsigned long long* __restrict__ bad) {
     const u64 stride = (u64)gridDim.x * blockDim.x;
     for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
@@ -394,7 +395,7 @@ __global__ __launch_bounds__(256) void bg_order_kernel(const u8* __restrict__ te
         if (ok && j > 0) {
             const u64 a = sa[j - 1];
             if (a >= n) continue;
-            const u8 ta = text[a], tb = text[b];
+            const S ta = text[a], tb = text[b];
             if (ta != tb) ok = ta < tb;
             else {
                 // equal first characters: the order of the suffixes one further on decides; the one that ends there sorts first
@@ -483,6 +484,38 @@ struct BigBuilder {
     // text_dev: n bytes (16-byte aligned); sa_out: n entries of 8 bytes on the device (the libsais64 layout: the suffix indices are
     // below 2^63, u64 and int64 are the same bits)
     int build(const u8* text_dev, u64 n, u64* sa_out) {
+        return build_with(n, sa_out, [&](u64* keys, u64* idx, int* key_bits, u64* h0) -> int {
+            // 1. alphabet
+            u64* dh = small.as<u64>();
+            SA_HIP_CHECK(hipMemsetAsync(dh, 0, 256 * sizeof(u64), stream));
+            hipLaunchKernelGGL(byte_hist_kernel, dim3(stream_grid(n, 256 * 64)), dim3(256), 0, stream, text_dev, n, dh);
+            u64 freq[256];
+            SA_HIP_CHECK(hipMemcpyAsync(freq, dh, sizeof freq, hipMemcpyDeviceToHost, stream));
+            SA_HIP_CHECK(hipStreamSynchronize(stream));
+            CodeMap map;
+            memset(&map, 0, sizeof map);
+            u32 sigma = 0;
+            for (int c = 0; c < 256; ++c) if (freq[c]) map.code[c] = (u16)(++sigma);
+            int b = bits_for((u64)sigma + 1);
+            if (b == 0) b = 1;
+            int k = 64 / b;
+            if ((u64)k > n) k = (int)n;   // (a key longer than the text adds nothing)
+            if (k < 1) k = 1;
+            stats.sigma = sigma; stats.bits_per_symbol = (u32)b; stats.initial_chars = (u32)k;
+            // 2. keys; the caller's array is one of the two suffix buffers
+            hipLaunchKernelGGL(bg_keygen_kernel, dim3((u32)((n + 4095) / 4096)), dim3(256), 0, stream, text_dev, n, map, b, k, keys, idx);
+            *key_bits = k * b;
+            *h0 = (u64)k;
+            return 0;
+        });
+    }
+
+    // The text-independent part of the build: `keygen(keys, idx, &key_bits, &h0)` runs on `stream` once the large buffers exist and
+    // the timer has started; it writes keys[p] = the initial key of suffix p (0 past the end sorts first) and idx[p] = p for every
+    // p < n, and reports the bits the initial sort looks at and the symbols every key covers (the first doubling step).  The byte
+    // build above and the integer-alphabet build (int_build.hpp) differ only there.
+    template <class KeyGen>
+    int build_with(u64 n, u64* sa_out, KeyGen&& keygen) {
         stats = BigStats{};
         if (n == 0) return 0;
         int rc;
@@ -502,27 +535,13 @@ struct BigBuilder {
                 (rc = fpart.ensure((ntiles + 1) * sizeof(FlagAgg) + 64))) return rc;
         }
         SA_HIP_CHECK(hipEventRecord(e0, stream));
-        // 1. alphabet
-        u64* dh = small.as<u64>();
-        SA_HIP_CHECK(hipMemsetAsync(dh, 0, 256 * sizeof(u64), stream));
-        hipLaunchKernelGGL(byte_hist_kernel, dim3(stream_grid(n, 256 * 64)), dim3(256), 0, stream, text_dev, n, dh);
-        u64 freq[256];
-        SA_HIP_CHECK(hipMemcpyAsync(freq, dh, sizeof freq, hipMemcpyDeviceToHost, stream));
-        SA_HIP_CHECK(hipStreamSynchronize(stream));
-        CodeMap map;
-        memset(&map, 0, sizeof map);
-        u32 sigma = 0;
-        for (int c = 0; c < 256; ++c) if (freq[c]) map.code[c] = (u16)(++sigma);
-        int b = bits_for((u64)sigma + 1);
-        if (b == 0) b = 1;
-        int k = 64 / b;
-        if ((u64)k > n) k = (int)n;   // (a key longer than the text adds nothing)
-        if (k < 1) k = 1;
-        stats.sigma = sigma; stats.bits_per_symbol = (u32)b; stats.initial_chars = (u32)k;
-        // 2. keys + initial sort; the caller's array is one of the two suffix buffers
-        hipLaunchKernelGGL(bg_keygen_kernel, dim3((u32)((n + 4095) / 4096)), dim3(256), 0, stream, text_dev, n, map, b, k, keysA.as<u64>(), sa_out);
+        int key_bits = 0;
+        u64 h0 = 1;
+        if ((rc = keygen(keysA.as<u64>(), sa_out, &key_bits, &h0))) return rc;
+        if (h0 < 1) h0 = 1;
+        // 2. initial sort
         u64 *kres, *vres;
-        if ((rc = sort_pairs(keysA.as<u64>(), sa_out, keysB.as<u64>(), idxB.as<u64>(), n, k * b, &kres, &vres))) return rc;
+        if ((rc = sort_pairs(keysA.as<u64>(), sa_out, keysB.as<u64>(), idxB.as<u64>(), n, key_bits, &kres, &vres))) return rc;
         if (vres != sa_out) SA_HIP_CHECK(hipMemcpyAsync(sa_out, vres, n * 8, hipMemcpyDeviceToDevice, stream));
         // 3. heads, ranks, the tied records
         u64 M = 0, G = 0;
@@ -532,7 +551,7 @@ struct BigBuilder {
         keysA.release(); keysB.release(); idxB.release(); th.release(); off.release();   // the rounds allocate by the size of the tied set
         // 4. prefix doubling on the lists
         const int rbits = bits_for(n + 2);
-        for (u64 h = (u64)k; M > 0; h *= 2) {
+        for (u64 h = h0; M > 0; h *= 2) {
             stats.tied_total += M;
             ++stats.rounds;
             if ((rc = r_key2.ensure(M * 8 + 64)) || (rc = r_perm.ensure(M * 8 + 64)) || (rc = r_k1.ensure(M * 8 + 64)) || (rc = r_p1.ensure(M * 8 + 64)) ||
@@ -571,7 +590,8 @@ struct BigBuilder {
     }
 
     // sufcheck: number of slots that violate "permutation in suffix order" (0 = the array is THE suffix array)
-    int verify(const u8* text_dev, const u64* sa, u64 n, u64* violations) {
+    template <class S>
+    int verify(const S* text_dev, const u64* sa, u64 n, u64* violations) {
         *violations = 0;
         if (n == 0) return 0;
         int rc;
@@ -582,7 +602,7 @@ struct BigBuilder {
         SA_HIP_CHECK(hipMemsetAsync(isa.p, 0xFF, n * 8, stream));
         const u32 grid = stream_grid(n, 1024);
         hipLaunchKernelGGL(bg_inverse_kernel, dim3(grid), dim3(256), 0, stream, sa, n, isa.as<u64>(), bad);
-        hipLaunchKernelGGL(bg_order_kernel, dim3(grid), dim3(256), 0, stream, text_dev, sa, n, (const u64*)isa.as<u64>(), bad);
+        hipLaunchKernelGGL((bg_order_kernel<S>), dim3(grid), dim3(256), 0, stream, text_dev, sa, n, (const u64*)isa.as<u64>(), bad);
         unsigned long long v = 0;
         SA_HIP_CHECK(hipMemcpyAsync(&v, bad, 8, hipMemcpyDeviceToHost, stream));
         SA_HIP_CHECK(hipStreamSynchronize(stream));

@@ -92,8 +92,13 @@ __device__ __forceinline__ u64 key_at(const KeyView& kv, const u32* s_b, u64 r) 
     return ((u64)lo << 56) | ((u64)kv.keys32[r] << kv.lo_shift);
 }
 
-// phase 1: one thread per rank.  KEYS: key shortcut; LCP_OUT (with KEYS): untied ranks written to lcp_out directly.
-template <class Idx, bool KEYS, bool LCP_OUT>
+// Symbols: S = u8 (byte texts) or u32 (integer texts, sa_hip_libsais_plcp_int).  A text of S symbols is compared as the
+// bytes of its words: suffix i starts at byte i * sizeof(S), a pair of m symbols spans m * sizeof(S) bytes, and the first
+// differing byte o gives LCP o / sizeof(S) -- the same first mismatch whatever the byte order inside a symbol.  Depths,
+// budgets and chunks below are in bytes; PLCP values in symbols.
+
+// phase 1: one thread per rank.  KEYS: key shortcut (u8 only); LCP_OUT (with KEYS): untied ranks written to lcp_out directly.
+template <class Idx, class S, bool KEYS, bool LCP_OUT>
 __global__ __launch_bounds__(BLOCK) void lcp_phi_kernel(const u8* __restrict__ T, u64 nw, const Idx* __restrict__ SA, u64 n,
                                                          Idx* __restrict__ W, Idx* __restrict__ queue, u32* __restrict__ lcp_out,
                                                          KeyView kv, u32 lane_bytes, Counters* __restrict__ c) {
@@ -102,7 +107,10 @@ __global__ __launch_bounds__(BLOCK) void lcp_phi_kernel(const u8* __restrict__ T
         for (u32 j = threadIdx.x; j <= 256; j += BLOCK) s_b[j] = kv.bstart[j];
         __syncthreads();
     }
+    static_assert(!KEYS || sizeof(S) == 1, "the key shortcut is byte-only");
+    constexpr u64 SB = sizeof(S);
     const u64* T64 = reinterpret_cast<const u64*>(T);
+    const S* Ts = reinterpret_cast<const S*>(T);
     u64 positions = 0, bytes = 0, tied = 0;
     u32 bad = 0;
     const u64 stride = (u64)gridDim.x * BLOCK;
@@ -135,17 +143,18 @@ __global__ __launch_bounds__(BLOCK) void lcp_phi_kernel(const u8* __restrict__ T
                             ++tied;
                         }
                     }
-                    if (go && (i == 0 || k == 0 || T[i - 1] != T[k - 1])) {   // irreducible
+                    if (go && (i == 0 || k == 0 || Ts[i - 1] != Ts[k - 1])) {   // irreducible
                         ++positions;
-                        const u64 lim = (d0 + lane_bytes < m) ? d0 + lane_bytes : m;
+                        const u64 mb = m * SB;
+                        const u64 lim = (d0 + lane_bytes < mb) ? d0 + lane_bytes : mb;
                         u64 d = d0, l = lim;
                         while (d < lim) {
-                            const u64 x = tload8(T64, i + d, nw) ^ tload8(T64, k + d, nw);
+                            const u64 x = tload8(T64, i * SB + d, nw) ^ tload8(T64, k * SB + d, nw);
                             bytes += 8;
                             if (x) { const u64 p = d + ((u32)__builtin_ctzll(x) >> 3); l = p < lim ? p : lim; break; }
                             d += 8;
                         }
-                        if (l < lim || l == m) W[i] = (Idx)(i + l);
+                        if (l < lim || l == mb) W[i] = (Idx)(i + l / SB);
                         else push = true;
                     }
                 }
@@ -168,10 +177,11 @@ __global__ __launch_bounds__(BLOCK) void lcp_phi_kernel(const u8* __restrict__ T
 
 // phase 2: one wave per queued pair, comparison from depth d_start (uniform: every queued pair ran out of the same
 // lane budget), 1 KB per step, up to wave_bytes; pairs still equal then are queued for the split phase with W[i] open.
-template <class Idx>
+template <class Idx, class S>
 __global__ __launch_bounds__(BLOCK) void lcp_wave_kernel(const u8* __restrict__ T, u64 nw, const Idx* __restrict__ SA, u64 n,
                                                           Idx* __restrict__ W, const Idx* __restrict__ queue, Idx* __restrict__ split,
                                                           u64 d_start, u64 wave_bytes, Counters* __restrict__ c) {
+    constexpr u64 SB = sizeof(S);
     const u64* T64 = reinterpret_cast<const u64*>(T);
     const u64 nq = c->waves;
     const u32 lane = threadIdx.x & 63;
@@ -180,15 +190,15 @@ __global__ __launch_bounds__(BLOCK) void lcp_wave_kernel(const u8* __restrict__ 
     for (u64 e = (u64)blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6); e < nq; e += nwaves) {
         const u64 r = (u64)queue[e];
         const u64 i = (u64)SA[r], k = (u64)SA[r - 1];   // both range-checked by the phi kernel
-        const u64 m = n - (i > k ? i : k);
-        u64 d = d_start < m ? d_start : m;
-        const u64 end = (d + wave_bytes < m) ? d + wave_bytes : m;
+        const u64 m = n - (i > k ? i : k), mb = m * SB;
+        u64 d = d_start < mb ? d_start : mb;
+        const u64 end = (d + wave_bytes < mb) ? d + wave_bytes : mb;
         u64 res = ~0ull;
         while (d < end) {
             const u64 p = d + (u64)lane * 16;
             u32 off = 16;
             if (p < end) {
-                off = mismatch16(T64, nw, i + p, k + p);
+                off = mismatch16(T64, nw, i * SB + p, k * SB + p);
                 if (off < 16 && p + off >= end) off = 16;
                 const u64 span = end - p;
                 bytes += (off < 16) ? off + 1 : (span < 16 ? span : 16);
@@ -202,8 +212,8 @@ __global__ __launch_bounds__(BLOCK) void lcp_wave_kernel(const u8* __restrict__ 
             d += WAVE_STEP;
         }
         if (lane == 0) {
-            if (res != ~0ull) W[i] = (Idx)(i + res);
-            else if (end >= m) W[i] = (Idx)(i + m);
+            if (res != ~0ull) W[i] = (Idx)(i + res / SB);
+            else if (end >= mb) W[i] = (Idx)(i + m);
             else {
                 W[i] = (Idx)~(Idx)0;                  // open: the split phase takes the minimum into it
                 split[atomicAdd(&c->splits, 1ull)] = (Idx)r;
@@ -214,12 +224,13 @@ __global__ __launch_bounds__(BLOCK) void lcp_wave_kernel(const u8* __restrict__ 
 }
 
 // phase 3, round j: [d_lo, d_lo + seg) of every open pair, 4 KB chunks spread over all workgroups.
-template <class Idx>
+template <class Idx, class S>
 __global__ __launch_bounds__(BLOCK) void lcp_split_kernel(const u8* __restrict__ T, u64 nw, const Idx* __restrict__ SA, u64 n,
                                                            Idx* __restrict__ W, const Idx* __restrict__ split, u32 round,
                                                            u64 d_lo, u64 seg, Counters* __restrict__ c) {
     const u64 ns = c->splits;
     if (ns == 0 || (round > 0 && c->remaining[round - 1] == 0)) return;
+    constexpr u64 SB = sizeof(S);
     const u64* T64 = reinterpret_cast<const u64*>(T);
     const Idx OPEN = (Idx)~(Idx)0;
     const u64 cpe = (seg + SPLIT_CHUNK - 1) / SPLIT_CHUNK;
@@ -229,26 +240,26 @@ __global__ __launch_bounds__(BLOCK) void lcp_split_kernel(const u8* __restrict__
         const u64 e = t / cpe, ch = t - e * cpe;
         const u64 r = (u64)split[e];
         const u64 i = (u64)SA[r], k = (u64)SA[r - 1];
-        const u64 m = n - (i > k ? i : k);
+        const u64 mb = (n - (i > k ? i : k)) * SB;
         const u64 lo = d_lo + ch * SPLIT_CHUNK;
-        u64 hi = d_lo + seg < m ? d_lo + seg : m;
+        u64 hi = d_lo + seg < mb ? d_lo + seg : mb;
         if (lo + SPLIT_CHUNK < hi) hi = lo + SPLIT_CHUNK;
         if (lo >= hi) continue;
         const Idx cur = __atomic_load_n(&W[i], __ATOMIC_RELAXED);
-        if (cur != OPEN && (u64)cur < i + lo) continue;   // a mismatch before this chunk is known
+        if (cur != OPEN && (u64)cur < i + lo / SB) continue;   // a mismatch before this chunk is known (its symbol ends before lo)
         const u64 p = lo + (u64)threadIdx.x * 16;
         if (p < hi) {
-            u32 off = mismatch16(T64, nw, i + p, k + p);
+            u32 off = mismatch16(T64, nw, i * SB + p, k * SB + p);
             const u64 span = hi - p;
             bytes += span < 16 ? span : 16;
-            if (off < 16 && p + off < hi) atomicMin(&W[i], (Idx)(i + p + off));
+            if (off < 16 && p + off < hi) atomicMin(&W[i], (Idx)(i + (p + off) / SB));
         }
     }
     wave_add<Idx>(&c->bytes, bytes);
 }
 
 // end of round j: pairs without a mismatch in [.., d_hi) that reached n - max(i, k) are closed with that length
-template <class Idx>
+template <class Idx, class S>
 __global__ __launch_bounds__(BLOCK) void lcp_split_advance_kernel(const Idx* __restrict__ SA, u64 n, Idx* __restrict__ W,
                                                                    const Idx* __restrict__ split, u32 round, u64 d_hi,
                                                                    Counters* __restrict__ c) {
@@ -261,7 +272,7 @@ __global__ __launch_bounds__(BLOCK) void lcp_split_advance_kernel(const Idx* __r
         const u64 i = (u64)SA[r], k = (u64)SA[r - 1];
         const u64 m = n - (i > k ? i : k);
         if (W[i] == OPEN) {
-            if (d_hi >= m) W[i] = (Idx)(i + m);
+            if (d_hi >= m * sizeof(S)) W[i] = (Idx)(i + m);
             else ++open;
         }
     }
@@ -419,15 +430,16 @@ inline u32 lcp_grid(u64 items) {   // grid-stride kernels: 8 workgroups per CU a
     return g ? (u32)g : 1u;
 }
 
-// PLCP or LCP of (text, SA) on `stream`; n >= 2.  text: n bytes, 8-byte aligned (readable up to the 8-byte word that
-// holds byte n-1).  out: n entries of Idx.  keys: nullptr = no key shortcut (LCP with keys: Idx = u32).  When
-// counters_host is non-NULL the call waits and copies the counters there; otherwise it only enqueues.
-template <class Idx>
+// PLCP or LCP of (text, SA) on `stream`; n >= 2.  text: n symbols of S, 8-byte aligned (readable up to the 8-byte word
+// that holds its last byte).  out: n entries of Idx.  keys: nullptr = no key shortcut (LCP with keys: Idx = u32, S = u8).
+// When counters_host is non-NULL the call waits and copies the counters there; otherwise it only enqueues.
+template <class Idx, class S = u8>
 int run(Workspace& ws, hipStream_t stream, const u8* text, const Idx* sa, u64 n, Idx* out, Out what, const KeyView* keys,
         const Knobs& kn, Counters* counters_host, sa_hip_lcp_stats* stats) {
     int rc = ws.ensure(n, sizeof(Idx));
     if (rc) return rc;
-    const u64 nw = (n + 7) / 8;
+    constexpr u64 SB = sizeof(S);
+    const u64 nw = (n * SB + 7) / 8;
     Idx* W = ws.w.as<Idx>();
     Idx* queue = ws.queue.as<Idx>();
     Idx* split = ws.split.as<Idx>();
@@ -440,27 +452,27 @@ int run(Workspace& ws, hipStream_t stream, const u8* text, const Idx* sa, u64 n,
     const u32 g = lcp_grid(n);
     KeyView kv = use_keys ? *keys : KeyView{};
     u32* lcp32 = reinterpret_cast<u32*>(out);
-    if constexpr (sizeof(Idx) == 4) {   // the key shortcut exists for index handles (32-bit) only
+    if constexpr (sizeof(Idx) == 4 && SB == 1) {   // the key shortcut exists for index handles (32-bit, bytes) only
         if (use_keys && what == Out::LCP)
-            hipLaunchKernelGGL((lcp_phi_kernel<Idx, true, true>), dim3(g), dim3(BLOCK), 0, stream, text, nw, sa, n, W, queue, lcp32, kv, kn.lane_bytes, c);
+            hipLaunchKernelGGL((lcp_phi_kernel<Idx, S, true, true>), dim3(g), dim3(BLOCK), 0, stream, text, nw, sa, n, W, queue, lcp32, kv, kn.lane_bytes, c);
         else if (use_keys)
-            hipLaunchKernelGGL((lcp_phi_kernel<Idx, true, false>), dim3(g), dim3(BLOCK), 0, stream, text, nw, sa, n, W, queue, lcp32, kv, kn.lane_bytes, c);
-    } else if (use_keys) return fail(SA_HIP_EINTERNAL, "lcp: key shortcut with 64-bit indices");
+            hipLaunchKernelGGL((lcp_phi_kernel<Idx, S, true, false>), dim3(g), dim3(BLOCK), 0, stream, text, nw, sa, n, W, queue, lcp32, kv, kn.lane_bytes, c);
+    } else if (use_keys) return fail(SA_HIP_EINTERNAL, "lcp: key shortcut with 64-bit indices or integer symbols");
     if (!use_keys)
-        hipLaunchKernelGGL((lcp_phi_kernel<Idx, false, false>), dim3(g), dim3(BLOCK), 0, stream, text, nw, sa, n, W, queue, lcp32, kv, kn.lane_bytes, c);
+        hipLaunchKernelGGL((lcp_phi_kernel<Idx, S, false, false>), dim3(g), dim3(BLOCK), 0, stream, text, nw, sa, n, W, queue, lcp32, kv, kn.lane_bytes, c);
     SA_HIP_CHECK(hipGetLastError());
     SA_HIP_CHECK(hipEventRecord(ws.ev[1], stream));
     const u64 d_wave = (use_keys ? (u64)kv.k0 : 0ull) + kn.lane_bytes;
-    hipLaunchKernelGGL((lcp_wave_kernel<Idx>), dim3(2048), dim3(BLOCK), 0, stream, text, nw, sa, n, W, queue, split, d_wave, kn.wave_bytes, c);
+    hipLaunchKernelGGL((lcp_wave_kernel<Idx, S>), dim3(2048), dim3(BLOCK), 0, stream, text, nw, sa, n, W, queue, split, d_wave, kn.wave_bytes, c);
     SA_HIP_CHECK(hipGetLastError());
     SA_HIP_CHECK(hipEventRecord(ws.ev[2], stream));
-    // split rounds: segment lengths double; round j covers [d_lo, d_lo + seg); no pair is longer than n
+    // split rounds: segment lengths double; round j covers [d_lo, d_lo + seg); no pair is longer than n symbols
     u64 d_lo = d_wave + kn.wave_bytes;
     u64 seg = ((kn.wave_bytes + SPLIT_CHUNK - 1) / SPLIT_CHUNK) * SPLIT_CHUNK;
     u32 rounds = 0;
-    for (u32 j = 0; j < MAX_ROUNDS && d_lo < n; ++j) {
-        hipLaunchKernelGGL((lcp_split_kernel<Idx>), dim3(2048), dim3(BLOCK), 0, stream, text, nw, sa, n, W, split, j, d_lo, seg, c);
-        hipLaunchKernelGGL((lcp_split_advance_kernel<Idx>), dim3(256), dim3(BLOCK), 0, stream, sa, n, W, split, j, d_lo + seg, c);
+    for (u32 j = 0; j < MAX_ROUNDS && d_lo < n * SB; ++j) {
+        hipLaunchKernelGGL((lcp_split_kernel<Idx, S>), dim3(2048), dim3(BLOCK), 0, stream, text, nw, sa, n, W, split, j, d_lo, seg, c);
+        hipLaunchKernelGGL((lcp_split_advance_kernel<Idx, S>), dim3(256), dim3(BLOCK), 0, stream, sa, n, W, split, j, d_lo + seg, c);
         SA_HIP_CHECK(hipGetLastError());
         d_lo += seg;
         seg *= 2;

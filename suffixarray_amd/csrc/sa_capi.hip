@@ -19,6 +19,7 @@
 #include "comm_rccl.hpp"
 #include "lcp.hpp"
 #include "bwt.hpp"
+#include "int_build.hpp"
 #include <memory>
 #include <chrono>
 
@@ -268,12 +269,17 @@ struct OneShot {
     // the BWT drop-ins (sa_hip_libsais[64]_bwt / _unbwt): U / I on the device, the inverse's scratch; same stream
     bwt::Workspace bwt;
     DevBuf b_u, b_aux;
+    // the integer-alphabet drop-ins (sa_hip_libsais_int, sa_hip_libsais64_long): the text (4 or 8 bytes per symbol), the alphabet
+    // tables; the 64-bit build's buffers are given back after every call.  Same stream.
+    ints::Workspace ints;
+    DevBuf i_text;
     void release_lcp() {
         if (l_device >= 0) (void)hipSetDevice(l_device);
         if (l_stream) (void)hipStreamDestroy(l_stream);
         l_stream = nullptr;
         lcp.release(); l_text.release(); l_sa.release(); l_in.release(); l_out.release();
         bwt.release(); b_u.release(); b_aux.release();
+        ints.release(); i_text.release();
         l_device = -1;
     }
 } g_oneshot;
@@ -1771,7 +1777,7 @@ int sa_hip_sufcheck64_device(const void* text_dev, const int64_t* sa_dev, int64_
     big::BigBuilder b;
     SA_HIP_CHECK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
     u64 v = 0;
-    rc = b.verify(static_cast<const u8*>(text_dev), reinterpret_cast<const u64*>(sa_dev), (u64)n, &v);
+    rc = b.verify<u8>(static_cast<const u8*>(text_dev), reinterpret_cast<const u64*>(sa_dev), (u64)n, &v);
     *violations = v;
     b.destroy();
     (void)hipStreamDestroy(b.stream);
@@ -1921,34 +1927,35 @@ void sa_hip_synth_uniform27(uint8_t* out, uint64_t n, uint64_t seed) {
 
 extern "C++" {
 namespace {
-// Host drop-ins: Idx = u32 (libsais layout, int32 on the host) or u64 (libsais64 layout).  PLCP_IN == nullptr: PLCP of
-// (T, SA) into out; else LCP = gather of PLCP_IN by SA into out.  n >= 2, arguments checked by the caller.
-template <class Idx>
-int oneshot_lcp(const uint8_t* T, const void* plcp_in, const void* SA, void* out, uint64_t n) {
+// Host drop-ins: Idx = u32 (libsais layout, int32 on the host) or u64 (libsais64 layout); S = the symbol type of T (u8, or u32
+// for sa_hip_libsais_plcp_int).  PLCP_IN == nullptr: PLCP of (T, SA) into out; else LCP = gather of PLCP_IN by SA into out.
+// n >= 2, arguments checked by the caller.
+template <class Idx, class S = u8>
+int oneshot_lcp(const void* T, const void* plcp_in, const void* SA, void* out, uint64_t n) {
     OneShot& g = g_oneshot;
     std::lock_guard<std::mutex> lock(g.mu);
     const auto t_all = std::chrono::steady_clock::now();
     sa_hip_call_breakdown bd{};
     bd.n = n;
-    const size_t bytes = (size_t)n * sizeof(Idx);
+    const size_t bytes = (size_t)n * sizeof(Idx), tbytes = (size_t)n * sizeof(S);
     auto t0 = std::chrono::steady_clock::now();
     const int device = g.idx ? g.idx->device : 0;
     int rc = set_device(device);
     if (rc) return rc;
     if (g.l_device >= 0 && g.l_device != device) g.release_lcp();
     bd.workspace_reused = (g.l_stream && g.ring.ready && g.l_sa.cap >= bytes && g.l_out.cap >= bytes &&
-                           (plcp_in ? g.l_in.cap >= bytes : (g.l_text.cap >= n + 64 && g.lcp.w.cap >= bytes))) ? 1u : 0u;
+                           (plcp_in ? g.l_in.cap >= bytes : (g.l_text.cap >= tbytes + 64 && g.lcp.w.cap >= bytes))) ? 1u : 0u;
     if (!g.l_stream) SA_HIP_CHECK(hipStreamCreateWithFlags(&g.l_stream, hipStreamNonBlocking));
     g.l_device = device;
     if (g.ring.ready && g.ring.device != device) g.ring.destroy();
     if ((rc = g.ring.init()) || (rc = g.l_sa.ensure(bytes + 64)) || (rc = g.l_out.ensure(bytes + 64))) return rc;
     if (plcp_in) { if ((rc = g.l_in.ensure(bytes + 64))) return rc; }
-    else if ((rc = g.l_text.ensure(n + 64)) || (rc = g.lcp.ensure(n, sizeof(Idx)))) return rc;
+    else if ((rc = g.l_text.ensure(tbytes + 64)) || (rc = g.lcp.ensure(n, sizeof(Idx)))) return rc;
     bd.workspace_ms = ms_since(t0);
     t0 = std::chrono::steady_clock::now();
     if ((rc = ring_upload(g.ring, g.l_stream, device, g.l_sa.p, static_cast<const u8*>(SA), bytes))) return rc;
     if (plcp_in) rc = ring_upload(g.ring, g.l_stream, device, g.l_in.p, static_cast<const u8*>(plcp_in), bytes);
-    else rc = ring_upload(g.ring, g.l_stream, device, g.l_text.p, T, (size_t)n);
+    else rc = ring_upload(g.ring, g.l_stream, device, g.l_text.p, static_cast<const u8*>(T), tbytes);
     if (rc) return rc;
     bd.upload_ms = ms_since(t0);
     t0 = std::chrono::steady_clock::now();
@@ -1960,7 +1967,7 @@ int oneshot_lcp(const uint8_t* T, const void* plcp_in, const void* SA, void* out
     } else {
         lcp::Counters ctr{};
         sa_hip_lcp_stats st{};
-        if ((rc = lcp::run<Idx>(g.lcp, g.l_stream, g.l_text.as<u8>(), g.l_sa.as<Idx>(), n, g.l_out.as<Idx>(), lcp::Out::PLCP, nullptr,
+        if ((rc = lcp::run<Idx, S>(g.lcp, g.l_stream, g.l_text.as<u8>(), g.l_sa.as<Idx>(), n, g.l_out.as<Idx>(), lcp::Out::PLCP, nullptr,
                                 lcp::Knobs::read(), &ctr, &st))) return rc;
         error = ctr.error;
         bd.build_device_ms = st.total_ms;
@@ -2404,6 +2411,279 @@ int sa_hip_unbwt64_device(const void* U_dev, void* out_dev, int64_t n, int64_t r
     (void)hipStreamSynchronize(stream);
     ws.release();
     (void)hipStreamDestroy(stream);
+    return rc;
+}
+
+// ---- integer alphabets (int_build.hpp) -----------------------------------------------------------------------------------
+
+}  // extern "C"
+
+extern "C++" {
+namespace {
+// Where a finished integer build left its suffix array.
+enum class IntRes { INDEX_U32, DEV_I32, DEV_U64 };
+
+// The build of T[0..n) (n >= 2, on the device, k >= 1) on `stream`, synchronous.  get_idx(n, &idx) hands route A an index
+// handle with n_max >= n (locked for the caller).  out32 / out64: where the caller wants the result on the device (at most one);
+// to_index: route A may leave it in idx->b.sa (the host drop-ins download from there).  *res / *res_ptr: where it is.
+template <class S, class GetIdx>
+int int_core(ints::Workspace& ws, hipStream_t stream, const S* T, u64 n, int64_t k, GetIdx&& get_idx, int32_t* out32, int64_t* out64,
+             bool to_index, sa_hip_int_stats* st, IntRes* res, const void** res_ptr, sa_hip_index** idx_used) {
+    const ints::Knobs kn = ints::Knobs::read();
+    ints::Alphabet a;
+    float alpha_ms = 0.f, route_ms = 0.f;
+    int rc = ints::alphabet<S>(ws, stream, T, n, k, kn, &a, &alpha_ms);
+    if (rc) return rc;
+    sa_hip_int_stats t{};
+    t.n = n;
+    t.sigma = a.sigma;
+    t.compacted = a.dense ? 1u : 0u;
+    t.min_symbol = a.min;
+    t.max_symbol = a.max;
+    t.alphabet_ms = alpha_ms;
+    if (ints::route_bytes(a, n, kn)) {   // route A: rank bytes into an index's text, the product's byte build
+        sa_hip_index* idx = nullptr;
+        if ((rc = get_idx(n, &idx))) return rc;
+        *idx_used = idx;
+        t.plan = 0;
+        idx->has_index = false;
+        idx->widen_ms = 0.0;
+        SA_HIP_CHECK(hipEventRecord(ws.ev[0], idx->stream));
+        if ((rc = ints::map_bytes<S>(ws, idx->stream, T, n, idx->b.text.as<u8>()))) return rc;
+        if ((rc = idx->b.build(n, 0))) return rc;
+        idx->has_index = true;
+        *res = IntRes::INDEX_U32; *res_ptr = idx->b.sa;
+        if (out32 && !to_index) {
+            SA_HIP_CHECK(hipMemcpyAsync(out32, idx->b.sa, n * 4, hipMemcpyDeviceToDevice, idx->stream));
+            *res = IntRes::DEV_I32; *res_ptr = out32;
+        } else if (out64 && !to_index) {
+            if ((rc = ints::widen(idx->stream, idx->b.sa, n, out64))) return rc;
+            *res = IntRes::DEV_U64; *res_ptr = out64;
+        }
+        SA_HIP_CHECK(hipEventRecord(ws.ev[1], idx->stream));
+        SA_HIP_CHECK(hipEventSynchronize(ws.ev[1]));
+        SA_HIP_CHECK(hipEventElapsedTime(&route_ms, ws.ev[0], ws.ev[1]));
+        const sa_hip_build_stats& bs = idx->b.stats;
+        t.bits_per_symbol = bs.bits_per_symbol;
+        t.symbols_per_key = bs.initial_chars;
+        t.sort_passes = bs.radix_passes;
+        t.rounds = bs.rounds;
+        t.tied_total = bs.active_total;
+    } else {                             // route B: integer keys, the 64-bit build's sort and doubling
+        t.plan = 1;
+        u64* sa64 = reinterpret_cast<u64*>(out64);
+        if (!sa64) { if ((rc = ws.sa64.ensure(n * 8 + 64))) return rc; sa64 = ws.sa64.as<u64>(); }
+        rc = ints::build_keys<S>(ws, stream, T, n, a, sa64);
+        if (rc) return rc;
+        float narrow_ms = 0.f;
+        *res = IntRes::DEV_U64; *res_ptr = sa64;
+        if (out32) {
+            SA_HIP_CHECK(hipEventRecord(ws.ev[0], stream));
+            if ((rc = ints::narrow(stream, sa64, n, out32))) return rc;
+            SA_HIP_CHECK(hipEventRecord(ws.ev[1], stream));
+            SA_HIP_CHECK(hipEventSynchronize(ws.ev[1]));
+            SA_HIP_CHECK(hipEventElapsedTime(&narrow_ms, ws.ev[0], ws.ev[1]));
+            *res = IntRes::DEV_I32; *res_ptr = out32;
+        }
+        SA_HIP_CHECK(hipStreamSynchronize(stream));
+        const big::BigStats& bs = ws.big.stats;
+        t.bits_per_symbol = bs.bits_per_symbol;
+        t.symbols_per_key = bs.initial_chars;
+        t.sort_passes = bs.sort_passes;
+        t.rounds = bs.rounds;
+        t.tied_after_sort = bs.tied_after_sort;
+        t.tied_total = bs.tied_total;
+        route_ms = bs.total_ms + narrow_ms;
+    }
+    t.total_ms = (double)alpha_ms + (double)route_ms;
+    if (st) *st = t;
+    return 0;
+}
+
+// Host drop-ins: T (n >= 2 symbols of S) up through the shared ring into a scratch buffer, the build, SA down.  OUT = int32_t or
+// int64_t.  Arguments checked by the caller.
+template <class S, class OUT>
+int oneshot_int(const S* T, OUT* SA, uint64_t n, int64_t k) {
+    OneShot& g = g_oneshot;
+    std::lock_guard<std::mutex> lock(g.mu);
+    const auto t_all = std::chrono::steady_clock::now();
+    sa_hip_call_breakdown bd{};
+    bd.n = n;
+    const size_t tbytes = (size_t)n * sizeof(S);
+    auto t0 = std::chrono::steady_clock::now();
+    const int device = g.idx ? g.idx->device : 0;
+    int rc = set_device(device);
+    if (rc) return rc;
+    if (g.l_device >= 0 && g.l_device != device) g.release_lcp();
+    bd.workspace_reused = (g.l_stream && g.ring.ready && g.i_text.cap >= tbytes + 64) ? 1u : 0u;
+    if (!g.l_stream) SA_HIP_CHECK(hipStreamCreateWithFlags(&g.l_stream, hipStreamNonBlocking));
+    g.l_device = device;
+    if (g.ring.ready && g.ring.device != device) g.ring.destroy();
+    if ((rc = g.ring.init()) || (rc = g.i_text.ensure(tbytes + 64))) return rc;
+    bd.workspace_ms = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    if ((rc = ring_upload(g.ring, g.l_stream, device, g.i_text.p, reinterpret_cast<const u8*>(T), tbytes))) return rc;
+    bd.upload_ms = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    std::unique_lock<std::mutex> ilock;
+    auto get_idx = [&](u64 need, sa_hip_index** out) -> int {   // the cached index handle of sa_hip_libsais (lock order: g.mu, then idx->mu)
+        if (g.idx && g.idx->b.n_max < need) { sa_hip_index_destroy(g.idx); g.idx = nullptr; }
+        int r2;
+        if (!g.idx && (r2 = sa_hip_index_create(&g.idx, need, device))) return r2;
+        ilock = std::unique_lock<std::mutex>(g.idx->mu);
+        *out = g.idx;
+        return 0;
+    };
+    // route B narrows an int32 result into the text's own buffer (the text is not read after the keys are built)
+    int32_t* out32 = sizeof(OUT) == 4 ? g.i_text.as<int32_t>() : nullptr;
+    IntRes res;
+    const void* res_ptr = nullptr;
+    sa_hip_index* idx = nullptr;
+    sa_hip_int_stats st{};
+    rc = int_core<S>(g.ints, g.l_stream, g.i_text.as<S>(), n, k, get_idx, out32, nullptr, true, &st, &res, &res_ptr, &idx);
+    g.ints.big.destroy();
+    if (rc) { g.ints.sa64.release(); return rc; }
+    bd.build_ms = ms_since(t0);
+    bd.build_device_ms = st.total_ms;
+    t0 = std::chrono::steady_clock::now();
+    if (res == IntRes::INDEX_U32 || res == IntRes::DEV_I32) rc = ring_download<OUT>(g.ring, device, static_cast<const u32*>(res_ptr), SA, (size_t)n);
+    else rc = ring_download_pieces(g.ring, device, static_cast<const u8*>(res_ptr), (size_t)n * 8, PinnedRing::SLAB_BYTES,
+                                   [&](const u8* piece, size_t off, size_t len) {
+                                       if (sizeof(OUT) == 8) { memcpy(reinterpret_cast<u8*>(SA) + off, piece, len); return; }
+                                       const u64* in = reinterpret_cast<const u64*>(piece);
+                                       for (size_t i = 0; i < len / 8; ++i) SA[off / 8 + i] = (OUT)in[i];
+                                   });
+    g.ints.sa64.release();
+    if (rc) return rc;
+    bd.download_ms = ms_since(t0);
+    bd.total_ms = ms_since(t_all);
+    g.last = bd;
+    return 0;
+}
+
+template <class S, class OUT>
+OUT int_dropin(const S* T, OUT* SA, OUT n, OUT k, OUT fs, OUT threads, const char* name) {
+    if (T == nullptr || SA == nullptr || n < 0 || fs < 0 || threads < 0) return fail(SA_HIP_EINVAL, name, "invalid arguments");
+    if (n < 2) { if (n == 1) SA[0] = 0; return 0; }   // libsais.c:6640-6644: T[0] not looked at
+    if (k < 1) return fail(SA_HIP_EINVAL, name, "k < 1");
+    return (OUT)oneshot_int<S, OUT>(T, SA, (uint64_t)n, (int64_t)k);
+}
+
+// Device forms: one stream, one workspace and (route A) one index handle per call.
+template <class S, class OUT>
+int int_device(const S* T_dev, OUT* SA_dev, int64_t n, int64_t k, int device, sa_hip_int_stats* stats, const char* name) {
+    if (n < 0) return fail(SA_HIP_EINVAL, name, "negative length");
+    if ((!T_dev || !SA_dev) && n) return fail(SA_HIP_EINVAL, name, "NULL argument");
+    if (stats) { memset(stats, 0, sizeof *stats); stats->n = (u64)n; }
+    if (n >= 2 && k < 1) return fail(SA_HIP_EINVAL, name, "k < 1");
+    if (n == 0) return 0;
+    int rc = set_device(device);
+    if (rc) return rc;
+    if (n == 1) { SA_HIP_CHECK(hipMemset(SA_dev, 0, sizeof(OUT))); SA_HIP_CHECK(hipDeviceSynchronize()); return 0; }
+    hipStream_t stream = nullptr;
+    SA_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    ints::Workspace ws;
+    TempIndex tmp;
+    auto get_idx = [&](u64 need, sa_hip_index** out) -> int {
+        int r2 = sa_hip_index_create(&tmp.idx, need, device);
+        if (r2) return r2;
+        *out = tmp.idx;
+        return 0;
+    };
+    IntRes res;
+    const void* res_ptr = nullptr;
+    sa_hip_index* idx = nullptr;
+    int32_t* out32 = nullptr;
+    int64_t* out64 = nullptr;
+    if constexpr (sizeof(OUT) == 4) out32 = reinterpret_cast<int32_t*>(SA_dev); else out64 = reinterpret_cast<int64_t*>(SA_dev);
+    rc = int_core<S>(ws, stream, T_dev, (u64)n, k, get_idx, out32, out64, false, stats, &res, &res_ptr, &idx);
+    (void)hipStreamSynchronize(stream);
+    ws.release();
+    (void)hipStreamDestroy(stream);
+    return rc;
+}
+}  // namespace
+}  // extern "C++"
+
+extern "C" {
+
+int32_t sa_hip_libsais_int_omp(int32_t* T, int32_t* SA, int32_t n, int32_t k, int32_t fs, int32_t threads) {
+    return int_dropin<int32_t, int32_t>(T, SA, n, k, fs, threads, "sa_hip_libsais_int");
+}
+int32_t sa_hip_libsais_int(int32_t* T, int32_t* SA, int32_t n, int32_t k, int32_t fs) {
+    return sa_hip_libsais_int_omp(T, SA, n, k, fs, 0);
+}
+int64_t sa_hip_libsais64_long_omp(int64_t* T, int64_t* SA, int64_t n, int64_t k, int64_t fs, int64_t threads) {
+    return int_dropin<int64_t, int64_t>(T, SA, n, k, fs, threads, "sa_hip_libsais64_long");
+}
+int64_t sa_hip_libsais64_long(int64_t* T, int64_t* SA, int64_t n, int64_t k, int64_t fs) {
+    return sa_hip_libsais64_long_omp(T, SA, n, k, fs, 0);
+}
+int sa_hip_libsais_int_device(const int32_t* T_dev, int32_t* SA_dev, int32_t n, int32_t k, int device, sa_hip_int_stats* stats) {
+    return int_device<int32_t, int32_t>(T_dev, SA_dev, n, k, device, stats, "sa_hip_libsais_int_device");
+}
+int sa_hip_libsais64_long_device(const int64_t* T_dev, int64_t* SA_dev, int64_t n, int64_t k, int device, sa_hip_int_stats* stats) {
+    return int_device<int64_t, int64_t>(T_dev, SA_dev, n, k, device, stats, "sa_hip_libsais64_long_device");
+}
+
+int32_t sa_hip_libsais_plcp_int_omp(const int32_t* T, const int32_t* SA, int32_t* PLCP, int32_t n, int32_t threads) {
+    if (T == nullptr || SA == nullptr || PLCP == nullptr || n < 0 || threads < 0) return fail(SA_HIP_EINVAL, "sa_hip_libsais_plcp_int: invalid arguments");
+    if (n <= 1) { if (n == 1) PLCP[0] = 0; return 0; }
+    return oneshot_lcp<u32, u32>(T, nullptr, SA, PLCP, (uint64_t)n);
+}
+int32_t sa_hip_libsais_plcp_int(const int32_t* T, const int32_t* SA, int32_t* PLCP, int32_t n) {
+    return sa_hip_libsais_plcp_int_omp(T, SA, PLCP, n, 0);
+}
+
+int sa_hip_plcp_int_device(const int32_t* T_dev, const int32_t* SA_dev, int32_t* PLCP_dev, int32_t n, int device, sa_hip_lcp_stats* stats) {
+    const char* name = "sa_hip_plcp_int_device";
+    if (n < 0) return fail(SA_HIP_EINVAL, name, "negative length");
+    if ((!T_dev || !SA_dev || !PLCP_dev) && n) return fail(SA_HIP_EINVAL, name, "NULL argument");
+    if (stats) { memset(stats, 0, sizeof *stats); stats->n = (u64)n; }
+    if (n == 0) return 0;
+    int rc = set_device(device);
+    if (rc) return rc;
+    if (n == 1) { SA_HIP_CHECK(hipMemset(PLCP_dev, 0, 4)); SA_HIP_CHECK(hipDeviceSynchronize()); return 0; }
+    hipStream_t stream = nullptr;
+    SA_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    lcp::Workspace ws;
+    DevBuf pad;
+    auto body = [&]() -> int {
+        // the kernels read the text as aligned 8-byte words up to the one that holds its last byte: a text that is not 8-byte
+        // aligned or ends inside a word is copied into a padded buffer first
+        const u8* t = reinterpret_cast<const u8*>(T_dev);
+        if (((uintptr_t)t & 7u) != 0 || (n & 1) != 0) {
+            int r2 = pad.ensure((size_t)n * 4 + 64);
+            if (r2) return r2;
+            SA_HIP_CHECK(hipMemcpyAsync(pad.p, T_dev, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+            t = pad.as<u8>();
+        }
+        lcp::Counters ctr{};
+        int r2 = lcp::run<u32, u32>(ws, stream, t, reinterpret_cast<const u32*>(SA_dev), (u64)n, reinterpret_cast<u32*>(PLCP_dev), lcp::Out::PLCP,
+                                    nullptr, lcp::Knobs::read(), &ctr, stats);
+        if (r2) return r2;
+        if (ctr.error) return fail(SA_HIP_EINVAL, name, "suffix array entry out of range [0, n)");
+        return 0;
+    };
+    rc = body();
+    (void)hipStreamSynchronize(stream);
+    ws.release();
+    pad.release();
+    (void)hipStreamDestroy(stream);
+    return rc;
+}
+
+int sa_hip_sufcheck_long_device(const int64_t* T_dev, const int64_t* SA_dev, int64_t n, int device, uint64_t* violations) {
+    if (!violations || ((!T_dev || !SA_dev) && n) || n < 0) return fail(SA_HIP_EINVAL, "sa_hip_sufcheck_long_device: invalid arguments");
+    int rc = set_device(device);
+    if (rc) return rc;
+    big::BigBuilder b;
+    SA_HIP_CHECK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    u64 v = 0;
+    rc = b.verify<int64_t>(T_dev, reinterpret_cast<const u64*>(SA_dev), (u64)n, &v);
+    *violations = v;
+    b.destroy();
+    (void)hipStreamDestroy(b.stream);
     return rc;
 }
 
