@@ -490,3 +490,98 @@ def zero_length_rows(starts, seed=3):
     dup = {0, n - 1} | {i for i in (254, 255, 256, 511, 512) if i < n} | set(int(x) for x in rng.integers(0, n, max(n // 200, 3)))
     extra = starts[sorted(dup)]
     return np.sort(np.concatenate([starts, extra, starts[:1]])).astype(np.uint64)
+
+
+# -- planted repeats with an exact tie model (the 64-bit-index build's flags pass and rounds) -----------------------------------
+# csrc/big_build.hpp sorts the suffixes by a key of k symbols and hands every record whose key is not unique to the doubling
+# rounds; BigStats.tied_after_sort is their number.  A random text with one planted copy of R symbols has exactly
+# 2 (R - k + 1) of them (as long as the random part has no k-symbol tie of its own): the model below counts them, whatever they are.
+def plant_copy(t, A, B, R, symbols):
+    """t[B:B+R] = t[A:A+R] in place, then the guard symbols: the copies must not match one symbol further to the left or to
+    the right (A >= 1, A + R <= B, B + R < n).  The left guard is t[B-1], or t[A-1] where B - 1 is the first copy's last symbol."""
+    n = int(t.size)
+    symbols = np.asarray(symbols)
+    assert 1 <= A and A + R <= B and B + R < n and R >= 1 and symbols.size >= 2
+
+    def other(v):
+        return symbols[(int(np.flatnonzero(symbols == v)[0]) + 1) % symbols.size]
+    t[B:B + R] = t[A:A + R]
+    if t[B - 1] == t[A - 1]:
+        g = B - 1 if B - 1 >= A + R else A - 1
+        t[g] = other(t[g])
+    if t[B + R] == t[A + R]:
+        t[B + R] = other(t[B + R])
+    assert t[A - 1] != t[B - 1] and t[A + R] != t[B + R] and np.array_equal(t[A:A + R], t[B:B + R])
+
+
+def planted_repeat(n, R, A, B, seed, symbols):
+    """Random text of n symbols over `symbols` (an array of values; its dtype is the text's) with t[B:B+R] = t[A:A+R] and guard
+    symbols (plant_copy): the copies match on exactly R symbols, so LCP(suffix A+i, suffix B+i) = R - i for every i in [0, R)."""
+    symbols = np.asarray(symbols)
+    t = symbols[np.random.default_rng(seed).integers(0, symbols.size, n)]
+    plant_copy(t, A, B, R, symbols)
+    return np.ascontiguousarray(t)
+
+
+def tied_after_keys(T, k):
+    """The number of positions of T whose k-symbol key (symbols T[p .. p+k), 'nothing' past the end, which differs from every
+    symbol) is shared with another position: the model of tied_after_sort.  Plain NumPy: the keys, np.unique with counts."""
+    T = np.asarray(T)
+    n = int(T.size)
+    k = int(k)
+    assert k >= 1
+    if n == 0:
+        return 0
+    u, inv = np.unique(T, return_inverse=True)
+    code = np.concatenate([inv.reshape(-1).astype(np.uint64) + np.uint64(1), np.zeros(k - 1, np.uint64)])   # 0 past the end
+    b = max(1, int(u.size).bit_length())
+    if k * b <= 64:
+        keys = np.zeros(n, np.uint64)
+        for c in range(k):
+            keys = (keys << np.uint64(b)) | code[c:c + n]
+        counts = np.unique(keys, return_counts=True)[1]
+    else:
+        counts = np.unique(np.lib.stride_tricks.sliding_window_view(code, k), axis=0, return_counts=True)[1]
+    return int(counts[counts > 1].sum())
+
+
+def pair_samples(R, k, count, seed, extra=()):
+    """offsets i into a planted copy: 0, R - k (the last pair that shares a key), R - 1, `extra` and `count` random ones"""
+    rng = np.random.default_rng(seed)
+    return sorted({0, R - k, R - 1} | set(int(x) for x in extra) | set(int(x) for x in rng.integers(0, R, count)))
+
+
+def check_planted_pairs(sa_d, A, B, R, k, a_first, samples):
+    """Independent of the build's own checker: the slot j of suffix A+i is looked up in the device array (a torch tensor) by
+    comparing every entry with A+i, in pieces of 2^30 entries; exactly one slot holds it, and for i <= R - k the slot next to it
+    holds suffix B+i -- j + 1 where the first copy sorts first (a_first), j - 1 otherwise, the same side for every i.
+    -> {i: j}"""
+    import torch
+    n = int(sa_d.numel())
+    piece = 1 << 30
+    slots = {}
+    for i in samples:
+        found = []
+        for lo in range(0, n, piece):
+            hit = torch.nonzero(sa_d[lo:lo + piece] == A + i).reshape(-1)
+            found += [lo + int(x) for x in hit.cpu().numpy()]
+        assert len(found) == 1, (i, found)
+        j = found[0]
+        if i <= R - k:
+            jb = j + 1 if a_first else j - 1
+            assert 0 <= jb < n and int(sa_d[jb].item()) == B + i, (i, j, a_first, sa_d[max(j - 1, 0):j + 2].cpu().numpy(), B + i)
+        slots[i] = j
+    return slots
+
+
+def plant_copy_device(t, A, B, R, k):
+    """plant_copy on a torch device tensor of integer symbols in [0, k): t[B:B+R] = t[A:A+R], guards to v + 1 mod k.
+    -> a_first: the suffixes of the first copy sort before their partners (t[A+R] < t[B+R])"""
+    n = int(t.numel())
+    assert 1 <= A and A + R < B and B + R < n and k >= 2
+    t[B:B + R] = t[A:A + R].clone()
+    if int(t[B - 1].item()) == int(t[A - 1].item()):
+        t[B - 1] = (int(t[B - 1].item()) + 1) % k
+    if int(t[B + R].item()) == int(t[A + R].item()):
+        t[B + R] = (int(t[B + R].item()) + 1) % k
+    return int(t[A + R].item()) < int(t[B + R].item())

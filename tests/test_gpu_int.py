@@ -243,14 +243,29 @@ def test_1e9_zipf_tokens_device(gpu):
 
 
 def test_long_beyond_2_32_device(gpu):
-    """n = 2^32 + 2^20 int64 symbols, k = 1000 (route B).  HBM: text 8 n + SA 8 n + the 64-bit build's 32 n during its
-    initial sort = 48 n bytes, about 207 GB of the MI355X's 288 GB; the sufcheck afterwards needs 8 n of scratch."""
+    """n = 2^32 + 2^24 int64 symbols, k = 1000 (route B), with a copy of R = 1e7 symbols planted from A = 1e9 + 7 to
+    B = 2^32 + 12345: of every tied pair one suffix index lies below 2^32 and one above, their SA slots and ranks are spread
+    over all of [0, n), and the rounds need log2(1e7 / 6) = 20.7 doublings.  (B > 2^32 and B + R < n need n > 2^32 + 1e7: the
+    text is 2^24 symbols longer than 2^32, not 2^20.)  HBM: text 8 n + SA 8 n + the 64-bit build's 32 n during its initial sort
+    = 48 n bytes, about 207 GB of the MI355X's 288 GB; the sufcheck afterwards needs 8 n of scratch."""
     import torch
-    n = (1 << 32) + (1 << 20)
+    n = (1 << 32) + (1 << 24)
+    R, A, B = 10_000_000, 1_000_000_007, (1 << 32) + 12345
+    gpu.release_workspace()
+    torch.cuda.empty_cache()
+    free, _ = torch.cuda.mem_get_info(0)
+    if free < 56 * n:
+        pytest.skip("needs %d GB of free HBM" % (56 * n >> 30))
     g = torch.Generator(device="cuda:0").manual_seed(3)
     t = torch.randint(0, 1000, (n,), device="cuda:0", dtype=torch.int64, generator=g)
+    a_first = cases.plant_copy_device(t, A, B, R, 1000)
     sa = torch.empty(n, dtype=torch.int64, device="cuda:0")
     torch.cuda.synchronize()
     st = gpu.libsais64_long_device(t.data_ptr(), sa.data_ptr(), n, 1000)
+    print("int64 text beyond 2^32 with a planted repeat of 1e7:", st)
     assert st["plan"] == 1 and st["sigma"] == 1000, st
+    assert st["tied_after_sort"] >= 2 * (R - st["symbols_per_key"] + 1) and st["rounds"] >= 20, st
     assert gpu.sufcheck_long_device(t.data_ptr(), sa.data_ptr(), n) == 0, st
+    s = st["symbols_per_key"]
+    slots = cases.check_planted_pairs(sa, A, B, R, s, a_first, cases.pair_samples(R, s, 200, 4))
+    assert len(slots) >= 200
