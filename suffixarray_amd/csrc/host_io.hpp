@@ -93,62 +93,18 @@ inline int ring_upload(PinnedRing& r, hipStream_t stream, int device, void* dst_
     return 0;
 }
 
-// sa_dev[0..n) (u32, device) -> out[0..n) on the host as OUT (u32 / int32: copy; int64: widened).  The DMA of slab k
-// runs on the ring's copy stream while workers convert the slabs that have arrived.  The caller has synchronised
-// the stream that produced sa_dev.
-template <typename OUT>
-inline int ring_download(PinnedRing& r, int device, const u32* sa_dev, OUT* out, size_t n) {
-    if (n == 0) return 0;
-    constexpr size_t PER = PinnedRing::SLAB_BYTES / 4;   // entries per slab
-    const size_t nslab = (n + PER - 1) / PER;
-    unsigned W = (unsigned)std::min<size_t>(std::min<size_t>(host_workers(), PinnedRing::SLABS), nslab);
-    while (PinnedRing::SLABS % W) --W;
-    std::atomic<int> err{0};
-    auto issue = [&](size_t k) -> bool {
-        const int s = (int)(k % PinnedRing::SLABS);
-        const size_t off = k * PER;
-        const size_t len = std::min(PER, n - off);
-        return hipMemcpyAsync(r.slab[s], sa_dev + off, len * 4, hipMemcpyDeviceToHost, r.copy_stream) == hipSuccess &&
-               hipEventRecord(r.ev[s], r.copy_stream) == hipSuccess;
-    };
-    // the first SLABS copies are issued in order up front; afterwards the worker that has emptied a slab issues the copy
-    // that refills it
-    for (size_t k = 0; k < nslab && k < (size_t)PinnedRing::SLABS; ++k)
-        if (!issue(k)) return fail(SA_HIP_EHIP, "ring_download: device-to-host copy failed");
-    auto work = [&](unsigned w) {
-        if (hipSetDevice(device) != hipSuccess) { err = 1; return; }
-        for (size_t k = w; k < nslab && !err; k += W) {
-            const int s = (int)(k % PinnedRing::SLABS);
-            const size_t off = k * PER;
-            const size_t len = std::min(PER, n - off);
-            if (hipEventSynchronize(r.ev[s]) != hipSuccess) { err = 1; return; }
-            const u32* in = reinterpret_cast<const u32*>(r.slab[s]);
-            OUT* o = out + off;
-            if (sizeof(OUT) == 4) memcpy(o, in, len * 4);
-            else for (size_t i = 0; i < len; ++i) o[i] = (OUT)in[i];
-            if (k + PinnedRing::SLABS < nslab && !issue(k + PinnedRing::SLABS)) { err = 1; return; }
-        }
-    };
-    std::vector<std::thread> th;
-    try {
-        for (unsigned w = 1; w < W; ++w) th.emplace_back(work, w);
-    } catch (...) { err = 1; }
-    work(0);
-    for (auto& t : th) t.join();
-    if (err) return fail(SA_HIP_EHIP, "ring_download: device-to-host copy failed");
-    return 0;
-}
-
 // src_dev[0..bytes) -> consume(piece, byte offset, byte length) for consecutive pieces of `piece_bytes` (<= SLAB_BYTES; the
-// caller picks a multiple of its record size so that no record straddles two pieces).  Same pipeline as ring_download: the
-// DMA of piece k + SLABS is issued by the worker that has consumed piece k; consume() runs on up to 16 worker threads at once,
+// caller picks a multiple of its record size so that no record straddles two pieces).  The DMA of piece k runs on the ring's
+// copy stream while workers consume the pieces that have arrived: the first SLABS copies are issued in order up front, the
+// DMA of piece k + SLABS by the worker that has consumed piece k; consume() runs on up to 16 worker threads at once,
 // on disjoint pieces, and must only write what belongs to its piece.  The caller has synchronised the stream that produced
 // src_dev.  (The batched record retrieval, sa_hip_index_query_rows_batch: Q x k row ids come down as u32 and are widened
 // into the caller's uint64[Q][k] -- its first-touch page faults spread over the workers instead of one thread.)
 template <typename FN>
-inline int ring_download_pieces(PinnedRing& r, int device, const u8* src_dev, size_t bytes, size_t piece_bytes, FN consume) {
+inline int ring_download_pieces(PinnedRing& r, int device, const u8* src_dev, size_t bytes, size_t piece_bytes, FN consume,
+                                const char* who = "ring_download_pieces") {
     if (bytes == 0) return 0;
-    if (piece_bytes == 0 || piece_bytes > PinnedRing::SLAB_BYTES) return fail(SA_HIP_EINVAL, "ring_download_pieces: piece size");
+    if (piece_bytes == 0 || piece_bytes > PinnedRing::SLAB_BYTES) return fail(SA_HIP_EINVAL, who, "piece size");
     const size_t npiece = (bytes + piece_bytes - 1) / piece_bytes;
     unsigned W = (unsigned)std::min<size_t>(std::min<size_t>(host_workers(), PinnedRing::SLABS), npiece);
     while (PinnedRing::SLABS % W) --W;
@@ -161,7 +117,7 @@ inline int ring_download_pieces(PinnedRing& r, int device, const u8* src_dev, si
                hipEventRecord(r.ev[s], r.copy_stream) == hipSuccess;
     };
     for (size_t k = 0; k < npiece && k < (size_t)PinnedRing::SLABS; ++k)
-        if (!issue(k)) return fail(SA_HIP_EHIP, "ring_download_pieces: device-to-host copy failed");
+        if (!issue(k)) return fail(SA_HIP_EHIP, who, "device-to-host copy failed");
     auto work = [&](unsigned w) {
         if (hipSetDevice(device) != hipSuccess) { err = 1; return; }
         for (size_t k = w; k < npiece && !err; k += W) {
@@ -179,8 +135,21 @@ inline int ring_download_pieces(PinnedRing& r, int device, const u8* src_dev, si
     } catch (...) { err = 1; }
     work(0);
     for (auto& t : th) t.join();
-    if (err) return fail(SA_HIP_EHIP, "ring_download_pieces: device-to-host copy failed");
+    if (err) return fail(SA_HIP_EHIP, who, "device-to-host copy failed");
     return 0;
+}
+
+// src_dev[0..n) (device) -> out[0..n) on the host, slab by slab: copied where IN and OUT have the same size (u32 -> int32, bytes),
+// converted entry by entry otherwise (u32 -> int64: the libsais64 layout, libsais64.c:6248-6259)
+template <typename OUT, typename IN>
+inline int ring_download(PinnedRing& r, int device, const IN* src_dev, OUT* out, size_t n) {
+    return ring_download_pieces(r, device, reinterpret_cast<const u8*>(src_dev), n * sizeof(IN), PinnedRing::SLAB_BYTES,
+                                [out](const u8* piece, size_t off, size_t len) {
+                                    const IN* in = reinterpret_cast<const IN*>(piece);
+                                    OUT* o = out + off / sizeof(IN);
+                                    if (sizeof(OUT) == sizeof(IN)) memcpy(o, in, len);
+                                    else for (size_t i = 0; i < len / sizeof(IN); ++i) o[i] = (OUT)in[i];
+                                }, "ring_download");
 }
 
 }  // namespace sa

@@ -71,6 +71,12 @@ def test_bwt_dropins_match_reference(gpu, expected, bits):
         for r in RS:
             aU, aI = fwd(t, r=r)
             assert np.array_equal(aU, U) and np.array_equal(aI, aux[r]), (bits, name, r)
+    bd = gpu.last_call_breakdown()
+    assert bd["n"] == t.size and bd["workspace_reused"] in (0, 1), bd
+    assert bd["total_ms"] >= bd["build_ms"] >= 0, bd
+    with pytest.raises(gpu.SaHipError):
+        fwd(t, r=3)                       # r is not a power of two: rejected for its arguments
+    assert gpu.last_call_breakdown() == bd
 
 
 @pytest.mark.parametrize("plan", list(PLANS))
@@ -90,6 +96,13 @@ def test_unbwt_dropins_match_reference(gpu, ref, expected, monkeypatch, plan, bi
             rc, back = ref_unbwt(ref, U, I=aux[r], r=r, bits=bits)
             assert rc == 0 and np.array_equal(back, t)
             assert np.array_equal(inv(U, I=aux[r], r=r), t), (plan, bits, name, r)
+    bd = gpu.last_call_breakdown()
+    assert bd["n"] == t.size and bd["workspace_reused"] in (0, 1), bd
+    assert bd["total_ms"] >= bd["build_ms"] >= 0, bd
+    for bad in (0, t.size + 1):           # an aux index outside (0, n]: rejected for its arguments
+        with pytest.raises(gpu.SaHipError):
+            inv(U, primary=bad)
+        assert gpu.last_call_breakdown() == bd
 
 
 def test_aliasing_u_is_t(gpu, expected):

@@ -139,12 +139,19 @@ def test_fs_sentinel_and_bad_symbols(gpu, expected):
         sa = np.full(t.size + 5, -123, it)
         assert f(tt.ctypes.data, sa.ctypes.data, t.size, k, 5) == 0
         assert np.array_equal(sa[:t.size], expected["rand_k1000"]) and (sa[t.size:] == -123).all()
+        bd = gpu.last_call_breakdown()
+        assert bd["n"] == t.size and bd["workspace_reused"] in (0, 1), bd
+        assert bd["total_ms"] >= bd["build_ms"] >= 0, bd
+        assert f(tt.ctypes.data, sa.ctypes.data, t.size, 0, 0) == -1          # k < 1: rejected for its arguments
+        assert gpu.last_call_breakdown() == bd
         for bad_at, bad in ((777, -1), (4000, k)):
             b = tt.copy()
             b[bad_at] = bad
+            bd = gpu.last_call_breakdown()
             assert f(b.ctypes.data, sa.ctypes.data, t.size, k, 0) == -1, (it, bad)
             msg = lib.sa_hip_last_error().decode()
             assert ("T[%d] = %d" % (bad_at, bad)) in msg, msg
+            assert gpu.last_call_breakdown() == bd                               # a failed call leaves the breakdown alone
             sa[:] = -123
             assert f(tt.ctypes.data, sa.ctypes.data, t.size, k, 0) == 0          # the next call works
             assert np.array_equal(sa[:t.size], expected["rand_k1000"])
