@@ -53,58 +53,38 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_hist_kernel(const u64* __restrict
 
 // exclusive scan u32 -> u64 in three steps (reduce per 8192 elements, scan of the partial sums by one workgroup, apply)
 constexpr u32 SC_BLOCK = 1024, SC_ITEMS = 8, SC_TILE = SC_BLOCK * SC_ITEMS;
-__device__ __forceinline__ u64 bg_block_excl_scan(u64 v, u64* s_w, u64* total) {   // SC_BLOCK threads; returns the exclusive prefix of v
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    u64 off = 0, tot = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {
-        const u64 t = s_w[w];
-        if (w < wave) off += t;
-        tot += t;
-    }
-    __syncthreads();
-    *total = tot;
-    return off + incl - v;
-}
+constexpr int SC_WAVES = SC_BLOCK / WAVE;
 __global__ __launch_bounds__(SC_BLOCK) void bg_scan_reduce_kernel(const u32* __restrict__ in, u64 len, u64* __restrict__ part) {
-    __shared__ u64 s_w[SC_BLOCK / 64];
+    __shared__ u64 s_w[SC_WAVES];
     const u64 base = (u64)blockIdx.x * SC_TILE + (u64)threadIdx.x * SC_ITEMS;
     u64 s = 0;
 #pragma unroll
     for (u32 e = 0; e < SC_ITEMS; ++e) if (base + e < len) s += in[base + e];
     u64 tot;
-    (void)bg_block_excl_scan(s, s_w, &tot);
+    (void)block_scan_excl<SC_WAVES>(s, (u64)0, ScanSum{}, s_w, &tot);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(SC_BLOCK) void bg_scan_parts_kernel(u64* __restrict__ part, u64 nparts) {   // in place, exclusive; part[nparts] = total
-    __shared__ u64 s_w[SC_BLOCK / 64];
+    __shared__ u64 s_w[SC_WAVES];
     u64 carry = 0;
     for (u64 base = 0; base < nparts; base += SC_BLOCK) {
         const u64 i = base + threadIdx.x;
         const u64 v = i < nparts ? part[i] : 0;
         u64 tot;
-        const u64 ex = bg_block_excl_scan(v, s_w, &tot);
+        const u64 ex = block_scan_excl<SC_WAVES>(v, (u64)0, ScanSum{}, s_w, &tot);
         if (i < nparts) part[i] = carry + ex;
         carry += tot;
     }
     if (threadIdx.x == 0) part[nparts] = carry;
 }
 __global__ __launch_bounds__(SC_BLOCK) void bg_scan_apply_kernel(const u32* __restrict__ in, u64 len, const u64* __restrict__ part, u64* __restrict__ out) {
-    __shared__ u64 s_w[SC_BLOCK / 64];
+    __shared__ u64 s_w[SC_WAVES];
     const u64 base = (u64)blockIdx.x * SC_TILE + (u64)threadIdx.x * SC_ITEMS;
     u32 v[SC_ITEMS];
     u64 s = 0;
 #pragma unroll
     for (u32 e = 0; e < SC_ITEMS; ++e) { v[e] = (base + e < len) ? in[base + e] : 0u; s += v[e]; }
-    u64 tot;
-    u64 run = bg_block_excl_scan(s, s_w, &tot) + part[blockIdx.x];
+    u64 run = block_scan_excl<SC_WAVES>(s, (u64)0, ScanSum{}, s_w) + part[blockIdx.x];
 #pragma unroll
     for (u32 e = 0; e < SC_ITEMS; ++e) { if (base + e < len) out[base + e] = run; run += v[e]; }
 }
@@ -135,12 +115,7 @@ __device__ __forceinline__ void bg_scatter_tile(const u64* __restrict__ kin, con
             s_wh[w * RADIX + tid] = c;
             c += t;
         }
-        u32 incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
+        const u32 incl = wave_scan_incl(c, ScanSum{});
         if (lane == 63) s_wsum[wave] = incl;
         excl = incl - c;
     }
@@ -255,31 +230,12 @@ __device__ __forceinline__ FlagAgg bg_combine(const FlagAgg& x, const FlagAgg& y
     r.nhead = x.nhead + y.nhead;
     return r;
 }
-// exclusive scan of one aggregate per thread over the workgroup (BG_BLOCK threads); *total = the workgroup's aggregate
-__device__ __forceinline__ FlagAgg bg_block_scan_agg(FlagAgg v, FlagAgg* s_w, FlagAgg* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    FlagAgg incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        FlagAgg t;
-        t.lasthead = __shfl_up(incl.lasthead, o); t.nact = __shfl_up(incl.nact, o); t.nhead = __shfl_up(incl.nhead, o);
-        if (lane >= o) incl = bg_combine(t, incl);
-    }
-    FlagAgg excl;   // exclusive inside the wave
-    excl.lasthead = __shfl_up(incl.lasthead, 1); excl.nact = __shfl_up(incl.nact, 1); excl.nhead = __shfl_up(incl.nhead, 1);
-    if (lane == 0) { excl.lasthead = 0; excl.nact = 0; excl.nhead = 0; }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    FlagAgg off{0, 0, 0}, tot{0, 0, 0};
-    for (int w = 0; w < BG_WAVES; ++w) {
-        const FlagAgg t = s_w[w];
-        if (w < wave) off = bg_combine(off, t);
-        tot = bg_combine(tot, t);
-    }
-    __syncthreads();
-    *total = tot;
-    return bg_combine(off, excl);
+__device__ __forceinline__ FlagAgg lane_shift_up(const FlagAgg& v, int o) {   // found by the scans of scan.hpp through its argument: whole 64-bit members (word by word, the default, costs bg_flags_apply_kernel a wave of occupancy)
+    return FlagAgg{sa::lane_shift_up(v.lasthead, o), sa::lane_shift_up(v.nact, o), sa::lane_shift_up(v.nhead, o)};
 }
+struct FlagCombine {   // the op of block_scan_excl over FlagAgg (identity: FlagAgg{0, 0, 0})
+    __device__ __forceinline__ FlagAgg operator()(const FlagAgg& x, const FlagAgg& y) const { return bg_combine(x, y); }
+};
 // a thread looks at BG_ITEMS CONSECUTIVE positions (head / tied bits of them in two masks)
 __device__ __forceinline__ FlagAgg bg_thread_flags(const FlagArgs& a, u64 q0, u32& hmask, u32& amask) {
     FlagAgg g{0, 0, 0};
@@ -304,7 +260,7 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_flags_reduce_kernel(FlagArgs a, F
     u32 hm, am;
     const FlagAgg g = bg_thread_flags(a, (u64)blockIdx.x * BG_TILE + (u64)threadIdx.x * BG_ITEMS, hm, am);
     FlagAgg tot;
-    (void)bg_block_scan_agg(g, s_w, &tot);
+    (void)block_scan_excl<BG_WAVES>(g, FlagAgg{0, 0, 0}, FlagCombine{}, s_w, &tot);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(BG_BLOCK) void bg_flags_scan_kernel(FlagAgg* __restrict__ part, u64 nparts) {   // in place, exclusive; part[nparts] = total
@@ -315,7 +271,7 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_flags_scan_kernel(FlagAgg* __rest
         FlagAgg v{0, 0, 0};
         if (i < nparts) v = part[i];
         FlagAgg tot;
-        const FlagAgg ex = bg_block_scan_agg(v, s_w, &tot);
+        const FlagAgg ex = block_scan_excl<BG_WAVES>(v, FlagAgg{0, 0, 0}, FlagCombine{}, s_w, &tot);
         if (i < nparts) part[i] = bg_combine(carry, ex);
         carry = bg_combine(carry, tot);
     }
@@ -326,8 +282,7 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_flags_apply_kernel(FlagArgs a, co
     const u64 q0 = (u64)blockIdx.x * BG_TILE + (u64)threadIdx.x * BG_ITEMS;
     u32 hm, am;
     const FlagAgg g = bg_thread_flags(a, q0, hm, am);
-    FlagAgg tot;
-    FlagAgg run = bg_combine(part[blockIdx.x], bg_block_scan_agg(g, s_w, &tot));   // everything before q0
+    FlagAgg run = bg_combine(part[blockIdx.x], block_scan_excl<BG_WAVES>(g, FlagAgg{0, 0, 0}, FlagCombine{}, s_w));   // everything before q0
     if (q0 >= a.m) return;
 #pragma unroll
     for (int e = 0; e < BG_ITEMS; ++e) {

@@ -341,12 +341,7 @@ __global__ __launch_bounds__(FIN_BLOCK, FIN_BLOCK == 512 ? 4 : 2) void group_fin
                         s_whist[w * RADIX + tid] = c;
                         c += t;
                     }
-                    incl = c;
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const u32 t = __shfl_up(incl, o);
-                        if (lane >= o) incl += t;
-                    }
+                    incl = wave_scan_incl(c, ScanSum{});
                     if (lane == 63) s_wsum[wave] = incl;
                 }
                 __syncthreads();
@@ -405,13 +400,9 @@ __global__ __launch_bounds__(FIN_BLOCK, FIN_BLOCK == 512 ? 4 : 2) void group_fin
             }
         }
         __syncthreads();   // every read of s_key / s_idx / s_lgid / s_gq / s_gpos of this round is done
-        u32 ia = s_rowa[lane], ih = s_rowh[lane];   // every wave scans the 64 row counts
-        const u32 ca = ia, ch = ih;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 ta = __shfl_up(ia, o), th = __shfl_up(ih, o);
-            if (lane >= o) { ia += ta; ih += th; }
-        }
+        const u32 ca = s_rowa[lane], ch = s_rowh[lane];   // every wave scans the 64 row counts
+        const uint2 irow = wave_scan_incl(make_uint2(ca, ch), ScanSum{});
+        const u32 ia = irow.x, ih = irow.y;
         const u32 tot_a = (u32)__builtin_amdgcn_readlane((int)ia, 63), tot_h = (u32)__builtin_amdgcn_readlane((int)ih, 63);
         const u32 ea = ia - ca, eh = ih - ch;
         const u64 lt_mask = lanemask_lt();
@@ -497,31 +488,10 @@ __global__ __launch_bounds__(FIN_BLOCK, FIN_BLOCK == 512 ? 4 : 2) void group_fin
 // compaction over them.  left_scan_kernel: exclusive prefixes of the ranges' sizes (into LocTile::big_off) and of the non-empty
 // ranges (the next dense group ids), totals {records, groups}; left_copy_kernel: the ranges to the next lists.
 __global__ __launch_bounds__(1024) void left_scan_kernel(LocTile* __restrict__ tiles, u32 ntiles, u32* __restrict__ next_gid, u32* __restrict__ totals) {
-    __shared__ u32 s_a[16], s_b[16];
-    __shared__ u32 s_ca, s_cb;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) { s_ca = 0; s_cb = 0; }
-    __syncthreads();
-    for (u32 base = 0; base < ntiles; base += 1024) {
-        const u32 t = base + threadIdx.x;
-        const u32 va = (t < ntiles) ? tiles[t].end - tiles[t].local_end : 0u;
-        const u32 vb = va ? 1u : 0u;
-        u32 ia = va, ib = vb;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 xa = __shfl_up(ia, o), xb = __shfl_up(ib, o);
-            if (lane >= o) { ia += xa; ib += xb; }
-        }
-        if (lane == 63) { s_a[wave] = ia; s_b[wave] = ib; }
-        __syncthreads();
-        u32 oa = s_ca, ob = s_cb;
-        for (int w = 0; w < wave; ++w) { oa += s_a[w]; ob += s_b[w]; }
-        if (t < ntiles) { tiles[t].big_off = oa + ia - va; next_gid[t] = ob + ib - vb; }
-        __syncthreads();
-        if (threadIdx.x == 1023) { s_ca = oa + ia; s_cb = ob + ib; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { totals[0] = s_ca; totals[1] = s_cb; }
+    const uint2 sum = tiles_scan_excl<uint2>(
+        ntiles, [&](u32 t) { const u32 va = tiles[t].end - tiles[t].local_end; return make_uint2(va, va ? 1u : 0u); },
+        [&](u32 t, uint2 ex) { tiles[t].big_off = ex.x; next_gid[t] = ex.y; });
+    if (threadIdx.x == 0) { totals[0] = sum.x; totals[1] = sum.y; }
 }
 __global__ __launch_bounds__(256) void left_copy_kernel(const LocTile* __restrict__ tiles, u32 ntiles, const u32* __restrict__ next_gid,
                                                         const u32* __restrict__ apos, const u32* __restrict__ aidx, u32* __restrict__ out_apos,
@@ -882,12 +852,7 @@ __global__ __launch_bounds__(FIN_BLOCK, 4) void group_finish2_kernel(FinArgs a, 
                         v[e] = (e < per && bin < bins) ? (u32)wh[bin] : 0u;
                         sum += v[e];
                     }
-                    u32 incl = sum;
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const u32 t = __shfl_up(incl, o);
-                        if (lane >= o) incl += t;
-                    }
+                    const u32 incl = wave_scan_incl(sum, ScanSum{});
                     u32 run = incl - sum;
                     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -984,13 +949,9 @@ __global__ __launch_bounds__(FIN_BLOCK, 4) void group_finish2_kernel(FinArgs a, 
             if (j < R && ((finmask >> j) & 1u)) slotv[j] = a.apos[begin + (r_ph[j] & 0xFFFFu)];
         }
         __syncthreads();   // every read of s_key / s_idx / s_lgid / s_gqp / s_gh / s_gsig of this round is done
-        u32 ia = s_rowa[lane], ih = s_rowh[lane];   // every wave scans the 64 row counts
-        const u32 ca = ia, ch = ih;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 ta = __shfl_up(ia, o), th = __shfl_up(ih, o);
-            if (lane >= o) { ia += ta; ih += th; }
-        }
+        const u32 ca = s_rowa[lane], ch = s_rowh[lane];   // every wave scans the 64 row counts
+        const uint2 irow = wave_scan_incl(make_uint2(ca, ch), ScanSum{});
+        const u32 ia = irow.x, ih = irow.y;
         const u32 tot_a = (u32)__builtin_amdgcn_readlane((int)ia, 63), tot_h = (u32)__builtin_amdgcn_readlane((int)ih, 63);
         const u32 ea = ia - ca, eh = ih - ch;
         const u64 lt_mask = lanemask_lt();

@@ -280,29 +280,8 @@ __global__ __launch_bounds__(BLOCK) void lcp_split_advance_kernel(const Idx* __r
 }
 
 // ---- inclusive max-scan over W in text order ---------------------------------------------------------------------
-template <class Idx>
-__device__ __forceinline__ Idx block_max_scan_excl(Idx v, Idx* s_w, Idx* total) {   // exclusive over the threads of the block
-    const u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    Idx inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const Idx y = __shfl_up(inc, o);
-        if ((int)lane >= o && y > inc) inc = y;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    Idx before = 0, all = 0;
-    for (u32 q = 0; q < BLOCK / WAVE; ++q) {
-        const Idx s = s_w[q];
-        if (q < w && s > before) before = s;
-        if (s > all) all = s;
-    }
-    __syncthreads();
-    Idx ex = __shfl_up(inc, 1);
-    if (lane == 0) ex = 0;
-    if (before > ex) ex = before;
-    *total = all;
-    return ex;
-}
+// (block_scan_excl with ScanMax and identity 0: W holds no smaller value)
+constexpr int SCAN_WAVES = BLOCK / WAVE;
 
 // SCAN_ITEMS consecutive entries of W from `base` (W is the workspace's own buffer: 16-byte aligned, as is every tile)
 template <class Idx>
@@ -318,21 +297,21 @@ __device__ __forceinline__ void load_items(const Idx* W, u64 base, u64 n, Idx (&
 
 template <class Idx>
 __global__ __launch_bounds__(BLOCK) void lcp_tile_max_kernel(const Idx* __restrict__ W, u64 n, Idx* __restrict__ tmax) {
-    __shared__ Idx s_w[BLOCK / WAVE];
+    __shared__ Idx s_w[SCAN_WAVES];
     const u64 base = (u64)blockIdx.x * SCAN_TILE + (u64)threadIdx.x * SCAN_ITEMS;
     Idx it[SCAN_ITEMS];
     load_items<Idx>(W, base, n, it);
     Idx v = 0;
     for (u32 q = 0; q < SCAN_ITEMS; ++q) if (it[q] > v) v = it[q];
     Idx all;
-    (void)block_max_scan_excl<Idx>(v, s_w, &all);
+    (void)block_scan_excl<SCAN_WAVES>(v, (Idx)0, ScanMax{}, s_w, &all);
     if (threadIdx.x == 0) tmax[blockIdx.x] = all;
 }
 
 // one workgroup: exclusive max-scan of the tile maxima, in place
 template <class Idx>
 __global__ __launch_bounds__(BLOCK) void lcp_tile_scan_kernel(Idx* __restrict__ tmax, u64 nt) {
-    __shared__ Idx s_w[BLOCK / WAVE];
+    __shared__ Idx s_w[SCAN_WAVES];
     Idx carry = 0;
     for (u64 base = 0; base < nt; base += SCAN_TILE) {
         const u64 b = base + (u64)threadIdx.x * SCAN_ITEMS;
@@ -340,7 +319,7 @@ __global__ __launch_bounds__(BLOCK) void lcp_tile_scan_kernel(Idx* __restrict__ 
         Idx mx = 0;
         for (u32 q = 0; q < SCAN_ITEMS; ++q) { v[q] = (b + q < nt) ? tmax[b + q] : 0; if (v[q] > mx) mx = v[q]; }
         Idx all;
-        Idx run = block_max_scan_excl<Idx>(mx, s_w, &all);
+        Idx run = block_scan_excl<SCAN_WAVES>(mx, (Idx)0, ScanMax{}, s_w, &all);
         if (carry > run) run = carry;
         for (u32 q = 0; q < SCAN_ITEMS; ++q) {
             if (b + q < nt) tmax[b + q] = run;
@@ -353,14 +332,13 @@ __global__ __launch_bounds__(BLOCK) void lcp_tile_scan_kernel(Idx* __restrict__ 
 // PLCP[j] = max(prefix of the tile, W[..j]) - j, written to out (may be W)
 template <class Idx>
 __global__ __launch_bounds__(BLOCK) void lcp_scan_apply_kernel(const Idx* W, u64 n, const Idx* __restrict__ tpre, Idx* out) {
-    __shared__ Idx s_w[BLOCK / WAVE];
+    __shared__ Idx s_w[SCAN_WAVES];
     const u64 base = (u64)blockIdx.x * SCAN_TILE + (u64)threadIdx.x * SCAN_ITEMS;
     Idx v[SCAN_ITEMS];
     load_items<Idx>(W, base, n, v);
     Idx mx = 0;
     for (u32 q = 0; q < SCAN_ITEMS; ++q) if (v[q] > mx) mx = v[q];
-    Idx all;
-    Idx run = block_max_scan_excl<Idx>(mx, s_w, &all);
+    Idx run = block_scan_excl<SCAN_WAVES>(mx, (Idx)0, ScanMax{}, s_w);
     const Idx pre = tpre[blockIdx.x];
     if (pre > run) run = pre;
     for (u32 q = 0; q < SCAN_ITEMS; ++q) {

@@ -43,27 +43,19 @@ struct SegPlan {              // device resident, written by seg_plan_kernel
 
 // bucket sizes from the per-chunk histogram of the top digit -> SegPlan (one workgroup of 256)
 __global__ __launch_bounds__(256) void seg_plan_kernel(const u32* __restrict__ hist_top, u32 tile, SegPlan* __restrict__ plan) {
-    __shared__ u32 s_w[2][4];
+    __shared__ uint2 s_w[4];
     __shared__ u32 s_tp[RADIX + 1];
-    const int d = threadIdx.x, lane = d & 63, w = d >> 6;
+    const int d = threadIdx.x;
     u32 size = 0;
 #pragma unroll
     for (int c = 0; c < NCHUNK; ++c) size += hist_top[c * RADIX + d];
     const u32 tiles = (u32)(((u64)size + tile - 1) / tile);
-    u32 is = size, it = tiles;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 a = __shfl_up(is, o), b = __shfl_up(it, o);
-        if (lane >= o) { is += a; it += b; }
-    }
-    if (lane == 63) { s_w[0][w] = is; s_w[1][w] = it; }
-    __syncthreads();
-    u32 os = 0, ot = 0;
-    for (int i = 0; i < w; ++i) { os += s_w[0][i]; ot += s_w[1][i]; }
-    plan->bstart[d] = os + is - size;
-    plan->tprefix[d] = ot + it - tiles;
-    s_tp[d] = ot + it - tiles;
-    if (d == RADIX - 1) { plan->bstart[RADIX] = os + is; plan->tprefix[RADIX] = ot + it; s_tp[RADIX] = ot + it; }
+    uint2 tot;   // {records, tiles}
+    const uint2 ex = block_scan_excl<4>(make_uint2(size, tiles), make_uint2(0, 0), ScanSum{}, s_w, &tot);
+    plan->bstart[d] = ex.x;
+    plan->tprefix[d] = ex.y;
+    s_tp[d] = ex.y;
+    if (d == RADIX - 1) { plan->bstart[RADIX] = tot.x; plan->tprefix[RADIX] = tot.y; s_tp[RADIX] = tot.y; }
     __syncthreads();
     if (d <= NCHUNK) {
         // part c starts at the first bucket whose first tile lies at or beyond c/NCHUNK of all tiles
@@ -141,19 +133,8 @@ __global__ __launch_bounds__(BLOCK) void seg_hist_kernel(const KT* __restrict__ 
 __global__ __launch_bounds__(256) void seg_scan_kernel(const u32* __restrict__ hist, const SegPlan* __restrict__ plan,
                                                        u32* __restrict__ base) {
     __shared__ u32 s_w[4];
-    const int b = blockIdx.x, d = threadIdx.x, lane = d & 63, w = d >> 6;
-    const u32 c = hist[b * RADIX + d];
-    u32 incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_w[w] = incl;
-    __syncthreads();
-    u32 run = plan->bstart[b] + incl - c;
-    for (int i = 0; i < w; ++i) run += s_w[i];
-    base[b * RADIX + d] = run;
+    const int b = blockIdx.x, d = threadIdx.x;
+    base[b * RADIX + d] = plan->bstart[b] + block_scan_excl<4>(hist[b * RADIX + d], 0u, ScanSum{}, s_w);
 }
 
 struct SegPassArgs {
@@ -232,12 +213,7 @@ __device__ __forceinline__ void seg_tile(const SegPassArgs& a, const u32 flat, c
         __hip_atomic_store(&a.status[(u64)flat * RADIX + tid],
                            pack_status(a.epoch, flat == first_flat ? FLAG_INCL : FLAG_AGG, count),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        u32 incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
+        const u32 incl = wave_scan_incl(c, ScanSum{});
         if (lane == 63) s_wsum[wave] = incl;
         excl = incl - c;
     }
@@ -607,12 +583,7 @@ __device__ __forceinline__ void text_top_tile(const TextPassArgs& a, const u32 t
         __hip_atomic_store(&a.status[(u64)tile * RADIX + tid],
                            pack_status(a.epoch, tile == first_tile ? FLAG_INCL : FLAG_AGG, count),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        u32 incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
+        const u32 incl = wave_scan_incl(c, ScanSum{});
         if (lane == 63) s_wsum[wave] = incl;
         excl = incl - c;
     }
@@ -824,12 +795,7 @@ __device__ __forceinline__ void text_low_tile(const TextLowArgs& t, const u32 ti
         count = c;
         __hip_atomic_store(&a.status[(u64)tile * RADIX + tid], pack_status(a.epoch, tile == first_tile ? FLAG_INCL : FLAG_AGG, count),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        u32 incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 x = __shfl_up(incl, o);
-            if (lane >= o) incl += x;
-        }
+        const u32 incl = wave_scan_incl(c, ScanSum{});
         if (lane == 63) s_wsum[wave] = incl;
         excl = incl - c;
     }

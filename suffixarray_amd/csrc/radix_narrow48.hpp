@@ -86,12 +86,7 @@ __device__ __forceinline__ void seg48_tile(const Seg48Args& a, const u32 flat, c
         count = c;
         __hip_atomic_store(&a.status[(u64)flat * RADIX + tid], pack_status(a.epoch, flat == first_flat ? FLAG_INCL : FLAG_AGG, count),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        u32 incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
+        const u32 incl = wave_scan_incl(c, ScanSum{});
         if (lane == 63) s_wsum[wave] = incl;
         excl = incl - c;
     }

@@ -40,6 +40,7 @@
 // shared code or structure.
 #pragma once
 #include "common.hpp"
+#include "scan.hpp"
 #include <type_traits>
 
 namespace sa {
@@ -156,21 +157,12 @@ __global__ __launch_bounds__(256) void radix_hist_kernel(const u64* __restrict__
 // digit_base[c][d] = sum_{d'<d} total[d'] + sum_{c'<c} cnt[c'][d]; one workgroup of 256
 __global__ __launch_bounds__(256) void radix_scan_hist_kernel(const u32* __restrict__ hist, u32* __restrict__ base) {
     __shared__ u32 s_w[4];
-    const int d = threadIdx.x, lane = d & 63, w = d >> 6;
+    const int d = threadIdx.x;
     u32 cnt[NCHUNK];
     u32 c = 0;
 #pragma unroll
     for (int k = 0; k < NCHUNK; ++k) { cnt[k] = hist[k * RADIX + d]; c += cnt[k]; }
-    u32 incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_w[w] = incl;
-    __syncthreads();
-    u32 run = incl - c;
-    for (int i = 0; i < w; ++i) run += s_w[i];
+    u32 run = block_scan_excl<4>(c, 0u, ScanSum{}, s_w);
 #pragma unroll
     for (int k = 0; k < NCHUNK; ++k) { base[k * RADIX + d] = run; run += cnt[k]; }
 }
@@ -340,12 +332,7 @@ __device__ __forceinline__ void onesweep_tile(const SortPassArgs& a, const u32 t
         __hip_atomic_store(&a.status[(u64)tile * RADIX + tid],
                            pack_status(a.epoch, tile == first_tile ? FLAG_INCL : FLAG_AGG, count),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        u32 incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
+        const u32 incl = wave_scan_incl(c, ScanSum{});
         if (lane == 63) s_wsum[wave] = incl;
         excl = incl - c;
     }

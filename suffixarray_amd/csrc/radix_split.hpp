@@ -113,16 +113,7 @@ __global__ __launch_bounds__(SPLIT_NB) void split_levels_kernel(const u32* __res
     __shared__ u32 s_w[SPLIT_NB / WAVE];
     const int b = blockIdx.x, d = threadIdx.x, lane = d & 63, w = d >> 6;
     const u32 c = hist[b * SPLIT_NB + d];
-    u32 incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_w[w] = incl;
-    __syncthreads();
-    for (int i = 0; i < w; ++i) incl += s_w[i];
-    s_p[d + 1] = incl;
+    s_p[d + 1] = block_scan_excl<SPLIT_NB / WAVE>(c, 0u, ScanSum{}, s_w) + c;
     if (d == 0) s_p[0] = 0;
     __syncthreads();
     __shared__ u32 s_lv[SPLIT_BITS + 1][SPLIT_NB / WAVE];   // per level, the waves' maxima: ONE global atomic per level and bucket
@@ -148,18 +139,8 @@ __global__ __launch_bounds__(SPLIT_NB) void split_levels_kernel(const u32* __res
 __global__ __launch_bounds__(SPLIT_NB) void split_scan_kernel(const u32* __restrict__ hist, const SegPlan* __restrict__ plan, int hb, int rb,
                                                               u32* __restrict__ base, u32* __restrict__ sub) {
     __shared__ u32 s_w[SPLIT_NB / WAVE];
-    const int b = blockIdx.x, d = threadIdx.x, lane = d & 63, w = d >> 6;
-    const u32 c = hist[b * SPLIT_NB + d];
-    u32 incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_w[w] = incl;
-    __syncthreads();
-    u32 run = plan->bstart[b] + incl - c;
-    for (int i = 0; i < w; ++i) run += s_w[i];
+    const int b = blockIdx.x, d = threadIdx.x;
+    const u32 run = plan->bstart[b] + block_scan_excl<SPLIT_NB / WAVE>(hist[b * SPLIT_NB + d], 0u, ScanSum{}, s_w);
     const int g = hb - rb;
     u32 out = 0;
     if (d < (1 << hb) && (d & ((1 << g) - 1)) == 0) {
@@ -290,12 +271,7 @@ __device__ __forceinline__ void split_tile(const SplitPassArgs& a, const u32 fla
         __hip_atomic_store(&a.status[(u64)flat * SPLIT_NB + 2 * tid + 1], pack_status(a.epoch, fl, c.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     const u32 tot = c.x + c.y;
-    u32 incl = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
+    const u32 incl = wave_scan_incl(tot, ScanSum{});
     if (lane == 63) s_wsum[wave] = incl;
     __syncthreads();   // (every thread has read its two counters)
     u32 excl = incl - tot;
@@ -473,12 +449,7 @@ __device__ __forceinline__ void local_finish_sub(const LocalArgs& a, const u32 s
         u32 tot = 0;
 #pragma unroll
         for (int i = 0; i < WPT; ++i) { cw[i] = s_cw[WPT * tid + i]; tot += (cw[i] & 0xFFFFu) + (cw[i] >> 16); }
-        u32 incl = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
+        const u32 incl = wave_scan_incl(tot, ScanSum{});
         if (lane == 63) s_wsum[wave] = incl;
         __syncthreads();
         u32 run = incl - tot;

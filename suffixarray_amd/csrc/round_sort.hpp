@@ -84,32 +84,32 @@ __global__ __launch_bounds__(256) void loc_plan_kernel(const u32* __restrict__ g
     tiles[t] = lt;
 }
 
-// exclusive scan of the big-group sizes (one workgroup); total[0] = sum
-__global__ __launch_bounds__(1024) void loc_scan_kernel(LocTile* __restrict__ tiles, u32 ntiles, u32* __restrict__ total) {
-    __shared__ u32 s_w[16];
-    __shared__ u32 s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
+// Exclusive scan of one value per tile by ONE workgroup of 1024 threads: put(t, sum of value(t') over t' < t) for every tile,
+// 1024 tiles per trip, the running total carried from trip to trip in LDS.  Returns the total (in every thread).
+// T: u32, or uint2 for two sums at once.
+template <class T, class Value, class Put>
+__device__ __forceinline__ T tiles_scan_excl(u32 ntiles, Value value, Put put) {
+    __shared__ T s_w[16];
+    __shared__ T s_carry;
+    if (threadIdx.x == 0) s_carry = T{};
     __syncthreads();
     for (u32 base = 0; base < ntiles; base += 1024) {
         const u32 t = base + threadIdx.x;
-        const u32 v = (t < ntiles) ? tiles[t].end - tiles[t].local_end : 0u;
-        u32 incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 x = __shfl_up(incl, o);
-            if (lane >= o) incl += x;
-        }
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        u32 off = s_carry;
-        for (int w = 0; w < wave; ++w) off += s_w[w];
-        if (t < ntiles) tiles[t].big_off = off + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = off + incl;
+        const T v = (t < ntiles) ? value(t) : T{};
+        const T carry = s_carry;   // read before the scan's barriers, written again behind them
+        const T ex = carry + block_scan_excl<16>(v, T{}, ScanSum{}, s_w);
+        if (t < ntiles) put(t, ex);
+        if (threadIdx.x == 1023) s_carry = ex + v;
         __syncthreads();
     }
-    if (threadIdx.x == 0) total[0] = s_carry;
+    return s_carry;
+}
+
+// exclusive scan of the big-group sizes (one workgroup); total[0] = sum
+__global__ __launch_bounds__(1024) void loc_scan_kernel(LocTile* __restrict__ tiles, u32 ntiles, u32* __restrict__ total) {
+    const u32 sum = tiles_scan_excl<u32>(ntiles, [&](u32 t) { return tiles[t].end - tiles[t].local_end; },
+                                         [&](u32 t, u32 ex) { tiles[t].big_off = ex; });
+    if (threadIdx.x == 0) total[0] = sum;
 }
 
 // the big groups to / from their compact list (to_list: list <- records; else records <- list).  A big group is cut
@@ -199,12 +199,7 @@ __global__ __launch_bounds__(LOC_BLOCK) void loc_sort_kernel(LocSortArgs a) {
                 s_whist[w * RADIX + tid] = c;
                 c += t;
             }
-            incl = c;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const u32 t = __shfl_up(incl, o);
-                if (lane >= o) incl += t;
-            }
+            incl = wave_scan_incl(c, ScanSum{});
             if (lane == 63) s_wsum[wave] = incl;
         }
         __syncthreads();

@@ -491,47 +491,27 @@ __global__ void mark_done_heads_kernel(const u32* __restrict__ apos, const u8* _
 
 // exclusive scan of the per-tile {active, heads} pairs in three coalesced steps:
 //   reduce 1024 tiles per workgroup -> scan the partials (one workgroup) -> scan inside each group.
-__device__ __forceinline__ uint2 block_excl_scan_1024(uint2 v, u32* s_a, u32* s_h, uint2* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u32 ia = v.x, ih = v.y;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 ta = __shfl_up(ia, o), th = __shfl_up(ih, o);
-        if (lane >= o) { ia += ta; ih += th; }
-    }
-    if (lane == 63) { s_a[wave] = ia; s_h[wave] = ih; }
-    __syncthreads();
-    u32 oa = 0, oh = 0, ta = 0, th = 0;
-    for (int w = 0; w < 16; ++w) {
-        if (w < wave) { oa += s_a[w]; oh += s_h[w]; }
-        ta += s_a[w]; th += s_h[w];
-    }
-    __syncthreads();
-    if (total) *total = make_uint2(ta, th);
-    return make_uint2(oa + ia - v.x, oh + ih - v.y);
-}
-
 __global__ __launch_bounds__(1024) void counts_reduce_kernel(const uint2* __restrict__ counts, u32 ntiles,
                                                              uint2* __restrict__ partial) {
-    __shared__ u32 s_a[16], s_h[16];
+    __shared__ uint2 s_w[16];
     const u32 i = blockIdx.x * 1024 + threadIdx.x;
-    uint2 v = (i < ntiles) ? counts[i] : make_uint2(0, 0);
+    const uint2 v = (i < ntiles) ? counts[i] : make_uint2(0, 0);
     uint2 tot;
-    (void)block_excl_scan_1024(v, s_a, s_h, &tot);
+    (void)block_scan_excl<16>(v, make_uint2(0, 0), ScanSum{}, s_w, &tot);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
 // nparts <= 1024 * PER; one workgroup; partial[] becomes exclusive, totals[0..1] = sums
 __global__ __launch_bounds__(1024) void counts_scan_partials_kernel(uint2* __restrict__ partial, u32 nparts,
                                                                     u32* __restrict__ totals) {
-    __shared__ u32 s_a[16], s_h[16];
+    __shared__ uint2 s_w[16];
     const u32 per = (nparts + 1023) / 1024;
     const u32 lo = threadIdx.x * per;
     const u32 hi = (lo + per < nparts) ? lo + per : nparts;
     uint2 v = make_uint2(0, 0);
     for (u32 i = lo; i < hi; ++i) { v.x += partial[i].x; v.y += partial[i].y; }
     uint2 tot;
-    uint2 e = block_excl_scan_1024(v, s_a, s_h, &tot);
+    uint2 e = block_scan_excl<16>(v, make_uint2(0, 0), ScanSum{}, s_w, &tot);
     for (u32 i = lo; i < hi; ++i) {
         const uint2 c = partial[i];
         partial[i] = e;
@@ -542,12 +522,11 @@ __global__ __launch_bounds__(1024) void counts_scan_partials_kernel(uint2* __res
 
 __global__ __launch_bounds__(1024) void counts_apply_kernel(uint2* __restrict__ counts, u32 ntiles,
                                                             const uint2* __restrict__ partial) {
-    __shared__ u32 s_a[16], s_h[16];
+    __shared__ uint2 s_w[16];
     const u32 i = blockIdx.x * 1024 + threadIdx.x;
-    uint2 v = (i < ntiles) ? counts[i] : make_uint2(0, 0);
-    const uint2 e = block_excl_scan_1024(v, s_a, s_h, nullptr);
-    const uint2 base = partial[blockIdx.x];
-    if (i < ntiles) counts[i] = make_uint2(base.x + e.x, base.y + e.y);
+    const uint2 v = (i < ntiles) ? counts[i] : make_uint2(0, 0);
+    const uint2 e = block_scan_excl<16>(v, make_uint2(0, 0), ScanSum{}, s_w);
+    if (i < ntiles) counts[i] = partial[blockIdx.x] + e;
 }
 
 // ---- compaction of the active elements ---------------------------------------------------------------
@@ -575,12 +554,8 @@ __global__ __launch_bounds__(BLD_BLOCK) void compact_kernel(const u8* __restrict
         if (in && (f & 2u)) { amask |= 1u << k; if (f & 1u) hmask |= 1u << k; }
     }
     const u32 ca = (u32)__popc(amask), ch = (u32)__popc(hmask);
-    u32 ia = ca, ih = ch;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 ta = __shfl_up(ia, o), th = __shfl_up(ih, o);
-        if (lane >= o) { ia += ta; ih += th; }
-    }
+    const uint2 irow = wave_scan_incl(make_uint2(ca, ch), ScanSum{});
+    const u32 ia = irow.x, ih = irow.y;
     if (lane == 63) { s_a[wave] = ia; s_h[wave] = ih; }
     __syncthreads();
     const uint2 off = offsets[blockIdx.x];
@@ -815,7 +790,6 @@ __global__ __launch_bounds__(BLD_BLOCK) void tiny_flags_kernel(const u32* __rest
 __global__ __launch_bounds__(BLD_BLOCK) void tile_last_head_kernel(const u8* __restrict__ lf, u32 n,
                                                                    const u32* __restrict__ posmap,
                                                                    u32* __restrict__ tile_last) {
-    __shared__ u32 s_w[BLD_BLOCK / WAVE];
     const u64 base = (u64)blockIdx.x * BLD_TILE;
     int64_t best = -1;  // largest j with a head
     for (int it = 0; it < BLD_ITEMS; ++it) {
@@ -836,7 +810,6 @@ __global__ __launch_bounds__(BLD_BLOCK) void tile_last_head_kernel(const u8* __r
         for (int w = 0; w < BLD_BLOCK / WAVE; ++w) bb = s_b[w] > bb ? s_b[w] : bb;
         tile_last[blockIdx.x] = (bb < 0) ? NONE32 : (posmap ? posmap[bb] : (u32)bb);
     }
-    (void)s_w;
 }
 
 // exclusive "last defined value" scan over tiles, single workgroup:
@@ -1397,6 +1370,20 @@ struct Builder {
                                src_idx, dst_pos, dst_idx, dst_gid);
     }
 
+    // What a finisher leaves: lf and the scanned counts describe which of the M list records are still tied, tot = {records,
+    // groups} of them.  The lists are compacted into the next ones (ridx0 keeps the old suffix list meanwhile); M, G updated.
+    int compact_lists(u32& M, u32& G, const u32* tot) {
+        if (tot[0] >= M) return 0;   // nothing was resolved: the lists stand
+        if (tot[0]) {
+            SA_HIP_CHECK(hipMemcpyAsync(ridx0.p, aidx.p, (size_t)M * 4, hipMemcpyDeviceToDevice, stream));
+            launch_compact(lf.as<u8>(), M, tot[0], lst_cur, ridx0.as<u32>(), lst_nxt, aidx.as<u32>(), gid.as<u32>());
+            swap_lists();
+        }
+        M = tot[0];
+        G = tot[1];
+        return 0;
+    }
+
     // head/active flags over `cnt` sorted keys (+ optional round write-back), scanned counts.
     int flags_and_counts(const u64* keys, u32 cnt, u8* lf_out, const u32* apos, const u32* sidx, u32* totals_host,
                          bool with_directory = false, const NarrowKeys* nk = nullptr) {
@@ -1823,15 +1810,7 @@ struct Builder {
             for (int c = 1; c < 13; ++c) fprintf(stderr, " %d:%llu", c, ft_host[16 + c]);
             fprintf(stderr, "\n");
         }
-        if (tot[0] < M) {
-            if (tot[0]) {
-                SA_HIP_CHECK(hipMemcpyAsync(ridx0.p, aidx.p, (size_t)M * 4, hipMemcpyDeviceToDevice, stream));
-                launch_compact(lf.as<u8>(), M, tot[0], apos_cur, ridx0.as<u32>(), apos_nxt, aidx.as<u32>(), gid.as<u32>());
-                swap_lists();
-            }
-            M = tot[0];
-            G = tot[1];
-        }
+        if ((rc = compact_lists(M, G, tot))) return rc;
         return 0;
     }
 
@@ -1887,15 +1866,7 @@ struct Builder {
         stats.period_resolved += (u64)M - tot[0];
         if (debug_rounds) fprintf(stderr, "[sa_hip] period finisher: resolved %u of %u -> M'=%u G'=%u\n", M - tot[0], M, tot[0], tot[1]);
         if ((u64)(M - tot[0]) * 8 < M) per_skip = 2 << per_fails++;   // (chains cut by the end of a run split up in later rounds)
-        if (tot[0] < M) {
-            if (tot[0]) {
-                SA_HIP_CHECK(hipMemcpyAsync(ridx0.p, aidx.p, (size_t)M * 4, hipMemcpyDeviceToDevice, stream));
-                launch_compact(lf.as<u8>(), M, tot[0], lst_cur, ridx0.as<u32>(), lst_nxt, aidx.as<u32>(), gid.as<u32>());
-                swap_lists();
-            }
-            M = tot[0];
-            G = tot[1];
-        }
+        if ((rc = compact_lists(M, G, tot))) return rc;
         return 0;
     }
 
@@ -2093,15 +2064,7 @@ struct Builder {
                 hipLaunchKernelGGL(mark_done_heads_kernel, dim3(stream_grid(M, 1024)), dim3(256), 0, stream, (const u32*)apos_cur, (const u8*)done.as<u8>(), M,
                                    flags.as<u8>());
             }
-            if (tot[0] < M) {
-                if (tot[0]) {
-                    SA_HIP_CHECK(hipMemcpyAsync(ridx0.p, aidx.p, (size_t)M * 4, hipMemcpyDeviceToDevice, stream));
-                    launch_compact(lf.as<u8>(), M, tot[0], apos_cur, ridx0.as<u32>(), apos_nxt, aidx.as<u32>(), gid.as<u32>());
-                    swap_lists();
-                }
-                M = tot[0];
-                G = tot[1];
-            }
+            if ((rc = compact_lists(M, G, tot))) return rc;
         }
 
         if (M && (L == 0 || h < L) && (rc = materialise_flags())) return rc;   // (no-op unless the lite pass ran and no tiny pass followed)

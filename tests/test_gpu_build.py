@@ -120,6 +120,23 @@ def test_rebuild_same_handle_is_idempotent(gpu):
         assert np.array_equal(a, b)
 
 
+@pytest.mark.parametrize("n", [4_194_304, 4_194_305])
+def test_counts_scan_one_and_two_partials(gpu, oracle, monkeypatch, n):
+    """The {active, heads} counts of the flags pass are scanned per 1024 tiles of 4096 slots, then over the partial sums
+    (sa_build.hpp: scan_counts): 2^22 slots are exactly one partial, one slot more starts the second.  The 12-byte-record
+    plan takes its flags over all n slots of the suffix array, and keys of 4 characters (27^4 < n) leave every slot tied, so
+    the compaction places all n records by the scanned counts.  Bit-exact against the oracle on both sides."""
+    from suffixarray_amd import synth
+    monkeypatch.setenv("SA_HIP_NARROW", "0")
+    monkeypatch.setenv("SA_HIP_INITIAL_CHARS", "4")
+    t = synth.d1_uniform27(n)
+    with gpu.DeviceIndex(n, 0) as idx:
+        idx.build(t)
+        st = idx.build_stats()
+        assert st["initial_chars"] == 4 and st["pass_launches"][2] + st["pass_launches"][3] == 0, st   # (the narrow plans count per sub-bucket)
+        assert np.array_equal(idx.sa_u32(), oracle.sais(t).astype(np.uint32)), st
+
+
 def test_narrow_record_sort_matches_plain_sort(gpu, oracle, monkeypatch):
     """Initial keys of <= 40 bits are sorted in 8-byte records (top digit first, then LSD passes inside
     the 256 buckets, radix_narrow.hpp); the result must be the plain 12-byte-record sort's, bit for bit:

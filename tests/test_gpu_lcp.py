@@ -60,6 +60,8 @@ def lcp_texts():
     c["fib_small"] = synth.fibonacci(10946)
     for p in range(1, 18):
         c["period%d" % p] = synth.periodic(20000 + p, p) if p > 1 else synth.all_same(20001)
+    words = synth.d2_words(4097)   # the max-scan over W works in tiles of 4096 positions: exactly one tile, and one position more
+    c["tile_4096"], c["tile_4097"] = words[:4096], words
     blk = rng.integers(0, 256, 65536, dtype=np.uint8)
     c["repeat_64k_x12"] = np.tile(blk, 12)
     for sig in cases.ALPHABET_SIGMAS:
