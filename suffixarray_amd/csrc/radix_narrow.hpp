@@ -444,9 +444,10 @@ struct TextPassArgs {
     u32 epoch;
     DeviceStatus* dstat;
     u32 incl_mask;
-    u32* cursor;            // CLAIM form: records of a digit placed so far (zeroed by the host): cursor[digit * cursor_stride]
-    u32 cursor_stride;      // 64 words by default: every digit's counter in a 256-byte line of its own (SA_HIP_CURSOR_PAD=0: 1)
+    u32* cursor;            // CLAIM form: records of a digit placed so far (zeroed by the host): cursor[digit * TOP_CURSOR_STRIDE]
 };
+constexpr u32 TOP_CURSOR_STRIDE = 64;   // words: every digit's counter in a 256-byte line of its own (packed into 1 KB: 4.1-4.2 against
+                                        // 3.5-3.8 ms, profiles/r04_claim_counters_layout.log)
 constexpr int TEXT_HALO = 64;   // >= k0 - 1 (k0 * b <= 40)
 // positions per thread of the text-sourced top-digit pass.  24 (tiles of 12288 as in the narrow passes: 118 VGPRs, 71 KB of
 // LDS, two workgroups per CU) measured 3.67 against 3.61 ms for 16 (three workgroups) on the same box: unlike the narrow
@@ -467,9 +468,7 @@ __device__ __forceinline__ void shl_or_inplace(u32& acc, u32 x, int s) {
 // CLAIM (round 4): the pass need not be stable when the three-pass plan follows (radix_split.hpp: its local pass orders by
 // (key, suffix) whatever order it finds): a tile then claims its place inside a digit with one returning global atomic per
 // non-empty digit instead of publishing its counts and looking back over its predecessors, as seg_split_kernel does.
-// RANKA (with CLAIM): the place inside the tile's digit from one returning LDS atomic per record on ONE tile-wide counter array
-// instead of the ballot-match masks (about 40 vector instructions per record less; not stable).
-template <bool FULL, int BLOCK, bool EXT, bool CLAIM = false, bool RANKA = false>
+template <bool FULL, int BLOCK, bool EXT, bool CLAIM = false>
 __device__ __forceinline__ void text_top_tile(const TextPassArgs& a, const u32 tile, const u32 chunk,
                                               const u32 tile_n, u32* s_keys, u32* s_whist, u32* s_gdelta, u32* s_wsum,
                                               u8* s_code, const u8* s_map, u16* s_ext) {
@@ -550,35 +549,22 @@ __device__ __forceinline__ void text_top_tile(const TextPassArgs& a, const u32 t
 
     // 2. rank by the top digit (bits 24..31 of hi)
     u32 rd[ITEMS];
-    u32* wh = s_whist + (RANKA ? 0 : wave * RADIX);
-    if constexpr (RANKA) {
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const u32 d = hi[j] >> 24;
-            const u32 r = atomicAdd(&s_whist[(FULL || (woff + j * WAVE) < tile_n) ? d : (u32)RADIX], 1u);   // (a slot beyond the text: the spare word of wave 1's counters)
-            rd[j] = r | (d << 16);
-        }
-        sync_lds();
-    } else {
-        wave_rank<FULL>(hi, 24, 255u, woff, tile_n, wh, rd);
-        __syncthreads();   // also: every read of s_code is done (it becomes the digit array below)
-    }
+    u32* wh = s_whist + wave * RADIX;
+    wave_rank<FULL>(hi, 24, 255u, woff, tile_n, wh, rd);
+    __syncthreads();   // also: every read of s_code is done (it becomes the digit array below)
 
     // 3. tile digit counts -> aggregate -> exclusive scan over digits
     u32 count = 0, excl = 0, claim = 0;
     if (tid < RADIX) {
         u32 c = 0;
-        if constexpr (RANKA) { c = s_whist[tid]; }
-        else {
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) {
             const u32 t = s_whist[w * RADIX + tid];
             s_whist[w * RADIX + tid] = c;
             c += t;
         }
-        }
         count = c;
-        if (CLAIM) { if (c) claim = atomicAdd(&a.cursor[(size_t)tid * a.cursor_stride], c); }   // requested now, needed for the stores
+        if (CLAIM) { if (c) claim = atomicAdd(&a.cursor[(size_t)tid * TOP_CURSOR_STRIDE], c); }   // requested now, needed for the stores
         else
         __hip_atomic_store(&a.status[(u64)tile * RADIX + tid],
                            pack_status(a.epoch, tile == first_tile ? FLAG_INCL : FLAG_AGG, count),
@@ -590,11 +576,8 @@ __device__ __forceinline__ void text_top_tile(const TextPassArgs& a, const u32 t
     __syncthreads();
     if (tid < RADIX) {
         for (int i = 0; i < wave; ++i) excl += s_wsum[i];
-        if constexpr (RANKA) s_whist[tid] = excl;
-        else {
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) s_whist[w * RADIX + tid] += excl;
-        }
     }
     __syncthreads();
 
@@ -650,7 +633,7 @@ __device__ __forceinline__ void text_top_tile(const TextPassArgs& a, const u32 t
 }
 
 // 79 VGPRs and 50 KB of LDS: three workgroups (24 waves) per CU
-template <int BLOCK, bool EXT = false, bool CLAIM = false, bool RANKA = false>
+template <int BLOCK, bool EXT = false, bool CLAIM = false>
 __global__ __launch_bounds__(BLOCK, (TEXT_ITEMS > 16 || EXT) ? 4 : 6) void text_top_pass_kernel(TextPassArgs a) {
     constexpr int WAVES = BLOCK / WAVE;
     constexpr u32 TILE = BLOCK * TEXT_ITEMS;
@@ -687,9 +670,9 @@ __global__ __launch_bounds__(BLOCK, (TEXT_ITEMS > 16 || EXT) ? 4 : 6) void text_
     const u32 chunk = s_chunk;
     const u64 rest = a.n - (u64)tile * TILE;
     if (rest >= (u64)TILE)
-        text_top_tile<true, BLOCK, EXT, CLAIM, RANKA>(a, tile, chunk, TILE, s_keys, s_whist, s_gdelta, s_wsum, s_code, s_map, s_ext);
+        text_top_tile<true, BLOCK, EXT, CLAIM>(a, tile, chunk, TILE, s_keys, s_whist, s_gdelta, s_wsum, s_code, s_map, s_ext);
     else
-        text_top_tile<false, BLOCK, EXT, CLAIM, RANKA>(a, tile, chunk, (u32)rest, s_keys, s_whist, s_gdelta, s_wsum, s_code, s_map, s_ext);
+        text_top_tile<false, BLOCK, EXT, CLAIM>(a, tile, chunk, (u32)rest, s_keys, s_whist, s_gdelta, s_wsum, s_code, s_map, s_ext);
 }
 
 // ---- pass 0 of the plain LSD sort straight from the text ---------------------------------------------------
@@ -929,18 +912,10 @@ struct NarrowWorkspace {
     u32 split_max_seen = 0;        // largest sub-bucket of the last sort that looked (0: the plan was not considered)
     u32* split_hist = nullptr;     // [RADIX][SPLIT_NB]
     u32* split_base = nullptr;     // [RADIX][SPLIT_NB]
-    u32* split_cursor = nullptr;   // [RADIX][SPLIT_NB]: the ATOMIC form's claims
-    u32* top_cursor = nullptr;     // [RADIX]: the claims of the top-digit pass's CLAIM form
-    bool cursor_pad = true;        // SA_HIP_CURSOR_PAD=0: the 256 claim counters of the top-digit pass packed into 1 KB (measured on a slow host: 4.1-4.2 against 3.5-3.8 ms)
-    bool split_cursor_t = false;   // SA_HIP_SPLIT_CURSOR_T=1: the split pass's counters as [bin][bucket] (a tile's claims 1 KB apart; measured no better)
-    bool top_atomic_ranks = false; // SA_HIP_TOP_ARANKS=1: ... with LDS-atomic ranks as well
+    u32* split_cursor = nullptr;   // [RADIX][SPLIT_NB]: the split pass's claims
+    u32* top_cursor = nullptr;     // [RADIX][TOP_CURSOR_STRIDE]: the claims of the top-digit pass's CLAIM form
     bool top_claims = true;        // SA_HIP_TOP_CLAIMS=0: the top-digit pass always in its stable form (published counts + look-back)
-    bool split_atomic = true;      // SA_HIP_SPLIT_ATOMIC=0: the split pass with published counts and a look-back per bucket instead of claims by global atomics
-                                   // (measured: 4.25 against 3.05-3.45 ms at n = 1e9, profiles/r04_split_plan_atomic_ab.log)
     u32* split_sub = nullptr;      // [(RADIX << SPLIT_BITS) + 1] sub-bucket starts | [16] largest group per level
-    u64* split_status = nullptr;   // [split_tiles][SPLIT_NB], allocated with the first sort that takes the plan
-    u32 split_tiles = 0;
-    u32 split_epoch = 0;           // epoch of the last split pass (the granules are re-zeroed when the sort's epoch has wrapped)
     u32* host_word = nullptr;      // pinned, 16 words: the largest group per level comes here
     static size_t split_table_bytes() { return (size_t)RADIX * SPLIT_NB * sizeof(u32); }
     static size_t split_sub_words() { return ((size_t)RADIX << SPLIT_BITS) + 1; }
@@ -980,33 +955,18 @@ struct NarrowWorkspace {
         SA_HIP_CHECK(hipMalloc(&split_hist, split_table_bytes()));
         SA_HIP_CHECK(hipMalloc(&split_base, split_table_bytes()));
         SA_HIP_CHECK(hipMalloc(&split_cursor, split_table_bytes()));
-        SA_HIP_CHECK(hipMalloc(&top_cursor, (size_t)RADIX * 64 * sizeof(u32)));
+        SA_HIP_CHECK(hipMalloc(&top_cursor, (size_t)RADIX * TOP_CURSOR_STRIDE * sizeof(u32)));
         SA_HIP_CHECK(hipMalloc(&split_sub, (split_sub_words() + 16) * sizeof(u32)));
         SA_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host_word), 64, hipHostMallocDefault));
         if (const char* e = diag_env("SA_HIP_SPLIT")) split_enabled = atoi(e) != 0;
-        if (const char* e = diag_env("SA_HIP_CURSOR_PAD")) cursor_pad = atoi(e) != 0;
-        if (const char* e = diag_env("SA_HIP_SPLIT_CURSOR_T")) split_cursor_t = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_TOP_CLAIMS")) top_claims = atoi(e) != 0;
-        if (const char* e = diag_env("SA_HIP_TOP_ARANKS")) top_atomic_ranks = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_LOCAL_BIG")) local_big = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_LOCAL_PERSIST")) local_persist = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_LOCAL_GRID")) { const int v = atoi(e); local_grid_force = v > 0 ? (u32)v : 0u; }
-        if (const char* e = diag_env("SA_HIP_SPLIT_ATOMIC")) split_atomic = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_SPLIT_FLAGS")) split_flags = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_LOCAL_BINS")) local_bin_bits = (atoi(e) == 11) ? 11 : 12;
         if (const char* e = diag_env("SA_HIP_SPLIT_ITEMS")) { const int v = atoi(e); split_items = (v == 24 || v == 28) ? v : 32; }
         if (const char* e = diag_env("SA_HIP_SPLIT_CAP")) { const int v = atoi(e); if (v >= 64 && v <= (int)LOCAL_CAP) split_cap = (u32)v; }
-        return 0;
-    }
-    // (zeroed ON THE SORT'S STREAM: a hipMemset on the null stream is not ordered against a non-blocking stream and was still
-    //  clearing granules while the split pass published them)
-    int ensure_split_status(u32 tiles, hipStream_t stream) {
-        if (tiles <= split_tiles) return 0;
-        if (split_status) { SA_HIP_CHECK(hipStreamSynchronize(stream)); (void)hipFree(split_status); }
-        split_status = nullptr; split_tiles = 0;
-        SA_HIP_CHECK(hipMalloc(&split_status, (size_t)tiles * SPLIT_NB * sizeof(u64)));
-        SA_HIP_CHECK(hipMemsetAsync(split_status, 0, (size_t)tiles * SPLIT_NB * sizeof(u64), stream));
-        split_tiles = tiles;
         return 0;
     }
     void destroy() {
@@ -1020,11 +980,10 @@ struct NarrowWorkspace {
         if (split_cursor) (void)hipFree(split_cursor);
         if (top_cursor) (void)hipFree(top_cursor);
         if (split_sub) (void)hipFree(split_sub);
-        if (split_status) (void)hipFree(split_status);
         if (host_word) (void)hipHostFree(host_word);
         map_dev = nullptr;
         plan = nullptr; hist = nullptr; base = nullptr; tickets = nullptr;
-        split_hist = split_base = split_sub = split_cursor = top_cursor = nullptr; split_status = nullptr; split_tiles = 0; host_word = nullptr;
+        split_hist = split_base = split_sub = split_cursor = top_cursor = nullptr; host_word = nullptr;
     }
 };
 
@@ -1120,12 +1079,11 @@ inline int radix_sort_narrow(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_
         t.text = src->text; t.map = nw.map_dev; t.n = n; t.b = src->b; t.k0 = src->k0; t.begin_bit = begin_bit;
         t.keys_out32 = reinterpret_cast<u32*>(keysB); t.ext_out16 = nullptr; t.vals_out = valsB; t.g = g; t.digit_base = ws.base();
         t.status = ws.status; t.ticket = ws.tickets(); t.epoch = ws.epoch; t.dstat = ws.dstat; t.incl_mask = SA_INCL_MASK;
-        t.cursor = nw.top_cursor; t.cursor_stride = nw.cursor_pad ? 64u : 1u;
+        t.cursor = nw.top_cursor;
         int r;
-        if (claim) SA_HIP_CHECK(hipMemsetAsync(nw.top_cursor, 0, (size_t)RADIX * 64 * sizeof(u32), stream));
+        if (claim) SA_HIP_CHECK(hipMemsetAsync(nw.top_cursor, 0, (size_t)RADIX * TOP_CURSOR_STRIDE * sizeof(u32), stream));
         if ((r = ws.timer.start(stream, 1))) return r;
-        if (claim && nw.top_atomic_ranks) hipLaunchKernelGGL((text_top_pass_kernel<512, false, true, true>), dim3(g.tiles), dim3(512), 0, stream, t);
-        else if (claim) hipLaunchKernelGGL((text_top_pass_kernel<512, false, true>), dim3(g.tiles), dim3(512), 0, stream, t);
+        if (claim) hipLaunchKernelGGL((text_top_pass_kernel<512, false, true>), dim3(g.tiles), dim3(512), 0, stream, t);
         else hipLaunchKernelGGL((text_top_pass_kernel<512>), dim3(g.tiles), dim3(512), 0, stream, t);
         if ((r = ws.timer.stop(stream, (u64)n * 9u))) return r;
         ws.pass_records += n; ws.pass_bytes += (u64)n * 9u; ws.passes += 1;
@@ -1199,31 +1157,20 @@ inline int radix_sort_narrow(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_
             const u32 dmask = (1u << rb) - 1u;
             hipLaunchKernelGGL(split_scan_kernel, dim3(RADIX), dim3(SPLIT_NB), 0, stream, (const u32*)nw.split_hist, nw.plan, hb, rb,
                                nw.split_base, nw.split_sub);
-            if (!nw.split_atomic && (rc = nw.ensure_split_status(split_flat_max, stream))) return rc;
-            if (nw.split_atomic) SA_HIP_CHECK(hipMemsetAsync(nw.split_cursor, 0, NarrowWorkspace::split_table_bytes(), stream));
-            if (++ws.epoch >= (1u << 30)) {
+            SA_HIP_CHECK(hipMemsetAsync(nw.split_cursor, 0, NarrowWorkspace::split_table_bytes(), stream));
+            if (++ws.epoch >= (1u << 30)) {   // (the split pass reads no epoch: taken so that the passes after it number theirs as they always have)
                 SA_HIP_CHECK(hipMemsetAsync(ws.status, 0, (size_t)ws.max_tiles * RADIX * sizeof(u64), stream));
                 ws.epoch = 1;
             }
-            if (!nw.split_atomic && ws.epoch <= nw.split_epoch)   // the sort's epoch has wrapped since the last split pass
-                SA_HIP_CHECK(hipMemsetAsync(nw.split_status, 0, (size_t)nw.split_tiles * SPLIT_NB * sizeof(u64), stream));
-            nw.split_epoch = ws.epoch;
             SplitPassArgs a;
             a.keys_in = reinterpret_cast<const u32*>(keysB); a.vals_in = valsB;
             a.keys_out = reinterpret_cast<u32*>(keysA); a.vals_out = valsA;
-            a.plan = nw.plan; a.shift = dshift; a.mask = dmask; a.digit_base = nw.split_base; a.status = nw.split_status;
-            a.ticket = nw.tickets; a.epoch = ws.epoch; a.dstat = ws.dstat; a.incl_mask = SA_INCL_MASK; a.cursor = nw.split_cursor;
-            a.cur_bs = nw.split_cursor_t ? 1u : (u32)SPLIT_NB; a.cur_ds = nw.split_cursor_t ? (u32)RADIX : 1u;
+            a.plan = nw.plan; a.shift = dshift; a.mask = dmask; a.digit_base = nw.split_base;
+            a.ticket = nw.tickets; a.cursor = nw.split_cursor;
             if ((rc = ws.timer.start(stream, 2))) return rc;
-            if (nw.split_atomic) {
-                if (nw.split_items == 32) hipLaunchKernelGGL((seg_split_kernel<512, 32, true>), dim3(split_flat_max), dim3(512), 0, stream, a);
-                else if (nw.split_items == 28) hipLaunchKernelGGL((seg_split_kernel<512, 28, true>), dim3(split_flat_max), dim3(512), 0, stream, a);
-                else hipLaunchKernelGGL((seg_split_kernel<512, 24, true>), dim3(split_flat_max), dim3(512), 0, stream, a);
-            } else {
-                if (nw.split_items == 32) hipLaunchKernelGGL((seg_split_kernel<512, 32, false>), dim3(split_flat_max), dim3(512), 0, stream, a);
-                else if (nw.split_items == 28) hipLaunchKernelGGL((seg_split_kernel<512, 28, false>), dim3(split_flat_max), dim3(512), 0, stream, a);
-                else hipLaunchKernelGGL((seg_split_kernel<512, 24, false>), dim3(split_flat_max), dim3(512), 0, stream, a);
-            }
+            if (nw.split_items == 32) hipLaunchKernelGGL((seg_split_kernel<512, 32>), dim3(split_flat_max), dim3(512), 0, stream, a);
+            else if (nw.split_items == 28) hipLaunchKernelGGL((seg_split_kernel<512, 28>), dim3(split_flat_max), dim3(512), 0, stream, a);
+            else hipLaunchKernelGGL((seg_split_kernel<512, 24>), dim3(split_flat_max), dim3(512), 0, stream, a);
             if ((rc = ws.timer.stop(stream, (u64)n * 16u))) return rc;
             ws.pass_records += n; ws.pass_bytes += (u64)n * 16u; ws.passes += 1;
             LocalArgs l;

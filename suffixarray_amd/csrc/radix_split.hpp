@@ -20,9 +20,10 @@
 //   * The split pass need not be stable (the local pass orders by (key, suffix) whatever order it finds), so it ranks
 //     with one returning LDS atomic per record on ONE tile-wide counter array -- no per-wave histograms, which at 1024 bins
 //     would not fit beside the tile -- and a tile CLAIMS its place inside a bucket's bin with one returning global atomic
-//     per non-empty bin: no published counts, no look-back, nothing waits for another workgroup (ATOMIC; the look-back form,
-//     two adjacent bins per thread, is kept for A/B: 4.25 against 3.05-3.45 ms at n = 1e9).  Geometry and tickets are
-//     seg_onesweep_kernel's, with a plan of its own (tiles of 14 336 records).
+//     per non-empty bin: no published counts, no look-back, nothing waits for another workgroup.  (A look-back form, two
+//     adjacent bins per thread with a status array of its own, was built first and measured at 4.25 against 3.05-3.45 ms at
+//     n = 1e9, profiles/r04_split_plan_atomic_ab.log; it has been removed.)  Geometry and tickets are seg_onesweep_kernel's,
+//     with a plan of its own (tiles of 14 336 records).
 //   * The local pass: bin = the next 12 key bits, 4096 counters of 16 bits packed two per LDS word; one returning LDS atomic
 //     per record gives its place in the bin, a scan the bin starts; the records go to LDS as u64 (key << 32 | suffix) in bin
 //     order, and a record's final place is its bin's start + the number of records of the bin that compare smaller (1.8
@@ -157,57 +158,6 @@ __global__ __launch_bounds__(SPLIT_NB) void split_scan_kernel(const u32* __restr
     if (d == 0 && b == RADIX - 1) sub[(u32)RADIX << rb] = plan->bstart[RADIX];
 }
 
-// decoupled look-back for the two adjacent bins a thread owns (status rows of SPLIT_NB granules); radix_sort.hpp's
-// lookback_prefix with both chains advanced in the same window loads
-template <int LB_WINDOW = SA_LB_WINDOW>
-__device__ __forceinline__ void lookback_prefix_pair(const u64* __restrict__ status, u32 tile, u32 first_tile, u32 digit0,
-                                                     u32 epoch, DeviceStatus* dstat, u32& p0, u32& p1) {
-    u32 pre[2] = {0u, 0u};
-    bool done[2] = {false, false};
-    int64_t t = (int64_t)tile - 1;
-    const int64_t t0 = (int64_t)first_tile;
-    while (t >= t0 && !(done[0] && done[1])) {
-        u64 w[LB_WINDOW][2];
-#pragma unroll
-        for (int i = 0; i < LB_WINDOW; ++i) {
-            const int64_t ti = t - i;
-#pragma unroll
-            for (int k = 0; k < 2; ++k)
-                w[i][k] = (ti >= t0 && !done[k])
-                              ? __hip_atomic_load(&status[(u64)ti * SPLIT_NB + digit0 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                              : 0ull;
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-#pragma unroll
-            for (int i = 0; i < LB_WINDOW; ++i) {
-                const int64_t ti = t - i;
-                if (!done[k] && ti >= t0) {
-                    u64 x = w[i][k];
-                    u32 spins = 0;
-                    while (!((u32)(x >> 34) == epoch && ((x >> 32) & 3u) != 0)) {
-                        ++spins;
-                        if ((spins & 1023u) == 0) {
-                            if (spins >= SPIN_LIMIT ||
-                                __hip_atomic_load(&dstat->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                                __hip_atomic_store(&dstat->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                p0 = pre[0]; p1 = pre[1];
-                                return;   // poisoned; the host reports SA_HIP_EINTERNAL
-                            }
-                        }
-                        __builtin_amdgcn_s_sleep(1);
-                        x = __hip_atomic_load(&status[(u64)ti * SPLIT_NB + digit0 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    pre[k] += (u32)x;
-                    if (((x >> 32) & 3u) == FLAG_INCL) done[k] = true;
-                }
-            }
-        }
-        t -= LB_WINDOW;
-    }
-    p0 = pre[0]; p1 = pre[1];
-}
-
 struct SplitPassArgs {
     const u32* keys_in;
     const u32* vals_in;
@@ -217,27 +167,21 @@ struct SplitPassArgs {
     int shift;             // digit = (key >> shift) & mask: the top rb bits of the narrow key
     u32 mask;
     const u32* digit_base; // [RADIX buckets][SPLIT_NB]
-    u64* status;           // [flat tiles][SPLIT_NB]
     u32* ticket;           // [NCHUNK] (zeroed by the host)
-    u32 epoch;
-    DeviceStatus* dstat;
-    u32 incl_mask;
-    u32* cursor;           // ATOMIC form: records placed so far per (bucket, bin), zeroed by the host: cursor[bucket * cur_bs + bin * cur_ds]
-    u32 cur_bs, cur_ds;    // ([bucket][bin]: SPLIT_NB, 1; SA_HIP_SPLIT_CURSOR_T=1: [bin][bucket] -- 1, RADIX -- so that the claims of a tile lie 1 KB
-                           //  apart instead of in 3 KB of one bucket's row: measured no better, profiles/r04_claim_counters_layout.log)
+    u32* cursor;           // records placed so far per (bucket, bin), zeroed by the host: cursor[bucket * SPLIT_NB + bin]
 };
 
-// ATOMIC: a tile claims its place in a bin with one returning global atomic per non-empty bin instead of publishing its counts
+// A tile claims its place in a bin with one returning global atomic per non-empty bin instead of publishing its counts
 // and looking back over its predecessors -- the pass need not be stable, so the tiles of a bucket need no order among
 // themselves, and nothing waits for another workgroup.
-template <bool FULL, int BLOCK, int ITEMS, bool ATOMIC>
-__device__ __forceinline__ void split_tile(const SplitPassArgs& a, const u32 flat, const u32 first_flat, const u32 bucket,
-                                           const u32 start, const u32 tile_n, u32* s_keys, u32* s_cnt, u32* s_gdelta, u32* s_wsum) {
+template <bool FULL, int BLOCK, int ITEMS>
+__device__ __forceinline__ void split_tile(const SplitPassArgs& a, const u32 bucket, const u32 start, const u32 tile_n,
+                                           u32* s_keys, u32* s_cnt, u32* s_gdelta, u32* s_wsum) {
     static_assert(SPLIT_NB == 2 * BLOCK, "two bins per thread");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u32 woff = (u32)wave * (WAVE * ITEMS) + lane;
 
-    // the bases of this thread's two bins: requested now, needed after the look-back
+    // the bases of this thread's two bins: requested now, needed with the claims
     const uint2 dbase = *reinterpret_cast<const uint2*>(a.digit_base + (size_t)bucket * SPLIT_NB + 2 * tid);
 
     // 1. load (wave-striped), 2. place inside the tile's bin from one returning LDS atomic per record (any order will do)
@@ -258,17 +202,13 @@ __device__ __forceinline__ void split_tile(const SplitPassArgs& a, const u32 fla
     }
     sync_lds();
 
-    // 3. bin counts -> aggregate published -> exclusive scan over the bins
+    // 3. bin counts -> claims in the bucket's bins -> exclusive scan over the bins
     const uint2 c = *reinterpret_cast<const uint2*>(s_cnt + 2 * tid);
     u32 claim0 = 0, claim1 = 0;
-    if (ATOMIC) {   // requested now, needed for the stores
-        u32* cur = a.cursor + (size_t)bucket * a.cur_bs + (size_t)(2 * tid) * a.cur_ds;
-        if (c.x) claim0 = atomicAdd(cur, c.x);
-        if (c.y) claim1 = atomicAdd(cur + a.cur_ds, c.y);
-    } else {
-        const u64 fl = (flat == first_flat) ? FLAG_INCL : FLAG_AGG;
-        __hip_atomic_store(&a.status[(u64)flat * SPLIT_NB + 2 * tid], pack_status(a.epoch, fl, c.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&a.status[(u64)flat * SPLIT_NB + 2 * tid + 1], pack_status(a.epoch, fl, c.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    {   // requested now, needed for the stores
+        const u32 ci = bucket * SPLIT_NB + 2u * (u32)tid;   // (a 32-bit index: with a 64-bit one the 28-record form spills 3 registers)
+        if (c.x) claim0 = atomicAdd(&a.cursor[ci], c.x);
+        if (c.y) claim1 = atomicAdd(&a.cursor[ci + 1], c.y);
     }
     const u32 tot = c.x + c.y;
     const u32 incl = wave_scan_incl(tot, ScanSum{});
@@ -287,18 +227,8 @@ __device__ __forceinline__ void split_tile(const SplitPassArgs& a, const u32 fla
     }
     __syncthreads();
 
-    // 5. look-back inside the bucket, both bins of the thread at once
-    {
-        u32 p0 = claim0, p1 = claim1;
-        if (!ATOMIC && flat > first_flat) {
-            lookback_prefix_pair(a.status, flat, first_flat, 2u * (u32)tid, a.epoch, a.dstat, p0, p1);
-            if (((flat - first_flat) & a.incl_mask) == a.incl_mask) {
-                __hip_atomic_store(&a.status[(u64)flat * SPLIT_NB + 2 * tid], pack_status(a.epoch, FLAG_INCL, p0 + c.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&a.status[(u64)flat * SPLIT_NB + 2 * tid + 1], pack_status(a.epoch, FLAG_INCL, p1 + c.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        *reinterpret_cast<uint2*>(s_gdelta + 2 * tid) = make_uint2(dbase.x + p0 - excl, dbase.y + p1 - (excl + c.x));
-    }
+    // 5. where each of the thread's two bins goes: its base in the bucket + what the tile claimed - its tile-local start
+    *reinterpret_cast<uint2*>(s_gdelta + 2 * tid) = make_uint2(dbase.x + claim0 - excl, dbase.y + claim1 - (excl + c.x));
     __syncthreads();
 
     // 6. coalesced stores per bin run: keys, then the values through the same LDS
@@ -337,7 +267,7 @@ __device__ __forceinline__ void split_tile(const SplitPassArgs& a, const u32 fla
     }
 }
 
-template <int BLOCK, int ITEMS, bool ATOMIC>
+template <int BLOCK, int ITEMS>
 __global__ __launch_bounds__(BLOCK, 4) void seg_split_kernel(SplitPassArgs a) {
     constexpr u32 TILE = BLOCK * ITEMS;
     __shared__ __attribute__((aligned(16))) u32 s_keys[TILE];   // reused for the values
@@ -378,8 +308,8 @@ __global__ __launch_bounds__(BLOCK, 4) void seg_split_kernel(SplitPassArgs a) {
     const u32 first_flat = s_t[bucket];
     const u32 start = s_b[bucket] + (flat - first_flat) * TILE;
     const u32 rest = s_b[bucket + 1] - start;
-    if (rest >= TILE) split_tile<true, BLOCK, ITEMS, ATOMIC>(a, flat, first_flat, bucket, start, TILE, s_keys, s_cnt, s_gdelta, s_wsum);
-    else split_tile<false, BLOCK, ITEMS, ATOMIC>(a, flat, first_flat, bucket, start, rest, s_keys, s_cnt, s_gdelta, s_wsum);
+    if (rest >= TILE) split_tile<true, BLOCK, ITEMS>(a, bucket, start, TILE, s_keys, s_cnt, s_gdelta, s_wsum);
+    else split_tile<false, BLOCK, ITEMS>(a, bucket, start, rest, s_keys, s_cnt, s_gdelta, s_wsum);
 }
 
 // ---- local finish: one sub-bucket per workgroup, ordered completely in LDS ------------------------------------------------

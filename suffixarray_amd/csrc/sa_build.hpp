@@ -1104,13 +1104,9 @@ struct Builder {
     bool fin_left_failed = false;     // this build: a finisher run has given up on a group (the shortcut below is not tried again)
     bool fin_left_fast = true;        // SA_HIP_FIN_LEFT_FAST=0: what a finisher run leaves is always found from the done flags (flags pass + scan + compaction over the list)
     DevBuf fin_left_gid;              // u32[tiles]: next dense group id of a tile's left-out group
-    bool fin_prefetch = false;        // SA_HIP_FIN_PREFETCH=1: the finisher's first-round text fetches as a kernel of their own (measured slower: the gather costs what it saves)
-    bool fin_v2 = false;              // SA_HIP_FIN_V2=1: round 4's restructured finisher (group_finish2_kernel); measured 0-2 % SLOWER than the round-2 kernel
-                                      // (profiles/r04_finisher_v2_ab.log), so it is not the default
     bool fin_useful = true;           // per build: cleared when a run resolves less than a quarter of what it looked at
     bool use_pilot = true;            // SA_HIP_PILOT: 0 = initial key length from the byte distribution alone
     DevBuf fin_flag;                  // u8[M]: per list position, final / head marks of the finisher
-    DevBuf fin_w0;                    // u64[M]: per list position, the text bytes of the finisher's first round (fin_prefetch_kernel)
     bool period_finish = true;        // SA_HIP_PERIOD_FINISH: arithmetic groups inside one periodic run are ordered in one step (period_finish.hpp)
     int per_skip = 0, per_fails = 0;  // per build: an attempt that orders less than an eighth of the active set is repeated only after 2, 4, 8 ... rounds
     DevBuf per_gd, per_bad, per_table, per_dec, per_tf, per_carry;
@@ -1125,7 +1121,6 @@ struct Builder {
         else { u32* t = lst_cur; lst_cur = lst_nxt; lst_nxt = t; }
         lst_first = false;
     }
-    int big_round_chars = 0;             // SA_HIP_BIG_ROUND_CHARS: characters per global round while the finisher is at work (0 = as many as fit; 3..7 measured: no gain, tools/gpu_bigchars_sweep.py)
     u32 fin_count_max = FIN_COUNT_MAX;   // SA_HIP_FIN_COUNT_MAX
     int fin_radix_chars = FIN_RADIX_CHARS;   // SA_HIP_FIN_RADIX_CHARS
     u64 local_records = 0, big_records = 0;   // of the last build: records sorted in LDS / through the big-group list
@@ -1221,14 +1216,11 @@ struct Builder {
         if (const char* e = diag_env("SA_HIP_LITE_FLAGS")) lite_flags = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_LOCAL_ROUNDS")) local_rounds = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_GROUP_FINISH")) group_finish = atoi(e) != 0;
-        if (const char* e = diag_env("SA_HIP_FIN_V2")) fin_v2 = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_FIN_LEFT_FAST")) fin_left_fast = atoi(e) != 0;
-        if (const char* e = diag_env("SA_HIP_FIN_PREFETCH")) fin_prefetch = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_PILOT")) use_pilot = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_PERIOD_FINISH")) period_finish = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_SECTOR_SEARCH")) sector_search = atoi(e);
         if (const char* e = diag_env("SA_HIP_FIN_COUNT_MAX")) fin_count_max = (u32)atoi(e);
-        if (const char* e = diag_env("SA_HIP_BIG_ROUND_CHARS")) big_round_chars = atoi(e);
         if (const char* e = diag_env("SA_HIP_FIN_RADIX_CHARS")) fin_radix_chars = atoi(e);
         if (const char* e = diag_env("SA_HIP_DEBUG_ROUNDS")) debug_rounds = atoi(e) != 0;
         if (debug_rounds) { radix.debug_hook = &Builder::sort_debug_hook; radix.debug_ctx = this; }
@@ -1260,7 +1252,7 @@ struct Builder {
     void destroy() {
         DevBuf* all[] = {&text, &keys0, &keys1, &vals0, &vals1, &flags, &counts, &small, &isa, &apos0, &apos1, &apos2, &aidx,
                          &gid, &rkeys0, &rkeys1, &ridx0, &ridx1, &lf, &tile_last, &carry, &sa_own, &partial, &qdir, &dbg, &done, &pilot,
-                         &gstart, &loc_tiles, &big_keys, &big_vals, &fin_flag, &fin_w0, &fin_left_gid, &lite_stage, &qkeys2, &qskeys, &per_gd, &per_bad, &per_table, &per_dec, &per_tf, &per_carry};
+                         &gstart, &loc_tiles, &big_keys, &big_vals, &fin_flag, &fin_left_gid, &lite_stage, &qkeys2, &qskeys, &per_gd, &per_bad, &per_table, &per_dec, &per_tf, &per_carry};
         for (DevBuf* b : all) b->release();
         radix.destroy();
         narrow.destroy();
@@ -1735,18 +1727,7 @@ struct Builder {
         a.count_max = fin_count_max; a.radix_chars = fin_radix_chars; a.debug = debug_rounds ? 1 : 0;
         a.sa = sa; a.gflags = flags.as<u8>(); a.done = done.as<u8>();
         a.res_idx = ridx0.as<u32>(); a.res_fin = fin_flag.as<u8>(); a.totals = ft;
-        if (fin_v2) {
-            // (ridx0 = the list's ping-pong partner, free here: 4 bytes per record; the fetched words need 8)
-            a.w0 = nullptr;
-            if (fin_prefetch) {
-                if ((rc = fin_w0.ensure((size_t)M * 8 + 64))) return rc;
-                a.w0 = fin_w0.as<u64>();
-                hipLaunchKernelGGL(fin_prefetch_kernel, dim3(ntiles), dim3(256), 0, stream, (const u8*)text.as<u8>(), (const u32*)aidx.as<u32>(),
-                                   (const LocTile*)loc_tiles.as<LocTile>(), (u32)h, fin_w0.as<u64>());
-            }
-            hipLaunchKernelGGL(group_finish2_kernel, dim3(ntiles), dim3(FIN_BLOCK), 0, stream, a, map);
-        }
-        else hipLaunchKernelGGL(group_finish_kernel, dim3(ntiles), dim3(FIN_BLOCK), 0, stream, a, map);
+        hipLaunchKernelGGL(group_finish_kernel, dim3(ntiles), dim3(FIN_BLOCK), 0, stream, a, map);
         unsigned long long ft_host[32] = {0};
         SA_HIP_CHECK(hipMemcpyAsync(mbox + MB_FT, ft, 256, hipMemcpyDeviceToHost, stream));
         // What the run leaves.  When no tile gave up (every record inside the tiles was resolved: totals[0] == totals[1]) that is
@@ -1802,8 +1783,7 @@ struct Builder {
                     "slots radix %llu counting %llu, active record-rounds %llu\n", (unsigned long long)h, M, G, ntiles, ft_host[6], ft_host[0], ft_host[1],
                     tot[0], tot[1], ft_host[2], ft_host[3], ft_host[4], ft_host[5], ft_host[7]);
         if (debug_rounds && ft_host[6])
-            fprintf(stderr, fin_v2 ? "[sa_hip]   finisher v2 (rounds with a split group %llu; split records seen by wave 0: %llu) cycles per tile (thread 0, clock64): fetch+keys %llu, counting + splits %llu, permutation %llu, regroup + finals %llu, tail %llu\n"
-                                   : "[sa_hip]   finisher (radix rounds %llu, radix slots %llu) cycles per tile (thread 0, clock64): fetch+keys %llu, counting sort %llu, radix sort %llu, regroup %llu, write-out %llu\n",
+            fprintf(stderr, "[sa_hip]   finisher (radix rounds %llu, radix slots %llu) cycles per tile (thread 0, clock64): fetch+keys %llu, counting sort %llu, radix sort %llu, regroup %llu, write-out %llu\n",
                     ft_host[3], ft_host[4], ft_host[8] / ft_host[6], ft_host[9] / ft_host[6], ft_host[10] / ft_host[6], ft_host[11] / ft_host[6], ft_host[12] / ft_host[6]);
         if (debug_rounds && ft_host[6]) {
             fprintf(stderr, "[sa_hip]   records by group size at entry [2^c, 2^(c+1)):");
@@ -2072,11 +2052,9 @@ struct Builder {
         while (M && (L == 0 || h < L)) {
             // groups that fit a tile are finished in LDS, whatever their number of rounds; the global round below is for
             // the rest (an average group of more than half a tile: hardly anything fits)
-            bool finisher_ran = false;
             if (group_finish && fin_useful && !have_isa && (u64)M <= (u64)G * (FIN_CAP / 2)) {
                 if ((rc = run_group_finisher(map, b, L, h, M, G, tot))) return rc;
                 if (!M) break;
-                finisher_ran = fin_useful;
             }
             // long repeats -- the finisher gave up, doubling is under way, or the groups are far larger than a tile: groups that
             // are arithmetic progressions inside one periodic run are ordered in one step (full suffix arrays only)
@@ -2098,9 +2076,6 @@ struct Builder {
             int kc = 0;
             if (use_chunk) {
                 kc = (64 - gb) / b;
-                // what the finisher left are groups too large for a tile: a few characters take them apart far enough for
-                // the next finisher run, and every 8 key bits less is a pass less over their records
-                if (finisher_ran && big_round_chars > 0 && kc > big_round_chars) kc = big_round_chars;
                 if (L && (u64)kc > L - h) kc = (int)(L - h);
                 if (kc <= 0) use_chunk = false;
             }

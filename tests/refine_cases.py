@@ -362,8 +362,8 @@ def simulate(gr, n, k, b, L=0, tiny=True, group_finish=True, period_finish=True,
     vouches for (doubling_rounds, rounds, active_total are then lower bounds; handover = the records of the round the model
     stopped before).  t, sa: the text and its suffix array, needed once the shortcut is tried (period_attempt).
     Left out of the restatement, all unreachable at the default settings before exact turns False: per_fails < 8 and
-    per_skip (set by a try that resolves too little: the model stops there), have_isa (set by the first doubling round),
-    SA_HIP_BIG_ROUND_CHARS (0: as many symbols as fit) and round_sort's exit top <= begin_bit (no key bits to sort)."""
+    per_skip (set by a try that resolves too little: the model stops there), have_isa (set by the first doubling round)
+    and round_sort's exit top <= begin_bit (no key bits to sort)."""
     glue = gr.glue.astype(np.int64)
     tied = glue >= 0
     st = dict(tiny_resolved=0, finisher_runs=0, finisher_records=0, finisher_resolved=0, rounds=0, chunk_rounds=0, active_total=0,

@@ -440,14 +440,9 @@ def _tiles(T):
 
 _family("tiles", {  # buckets: top digit -> records; texts made for the tile of the split pass they run with
     "tiles_28": _c("tiles_28", plan=2, form="small", split_max=7331, lite=2, buckets=_tiles(512 * 28)),
-    "tiles_28_lookback": _c("tiles_28", {"SA_HIP_SPLIT_ATOMIC": "0"}, plan=2, form="small", split_max=7331, lite=2, buckets=_tiles(512 * 28)),
     "tiles_24": _c("tiles_24", {"SA_HIP_SPLIT_ITEMS": "24"}, plan=2, form="small", split_max=6229, lite=2, buckets=_tiles(512 * 24)),
-    "tiles_24_lookback": _c("tiles_24", {"SA_HIP_SPLIT_ITEMS": "24", "SA_HIP_SPLIT_ATOMIC": "0"}, plan=2, form="small", split_max=6229, lite=2,
-                            buckets=_tiles(512 * 24)),
     # (the bucket of 2 T = 32 768 records has four sub-buckets of about 8192 at level 2: level 3 is taken)
     "tiles_32": _c("tiles_32", {"SA_HIP_SPLIT_ITEMS": "32"}, plan=3, form="small", split_max=4325, lite=2, buckets=_tiles(512 * 32)),
-    "tiles_32_lookback": _c("tiles_32", {"SA_HIP_SPLIT_ITEMS": "32", "SA_HIP_SPLIT_ATOMIC": "0"}, plan=3, form="small", split_max=4325, lite=2,
-                            buckets=_tiles(512 * 32)),
 })
 _family("length", {  # n against the top-digit pass's tiles of TEXT_TILE positions; below 2^22 no narrow-record sort at all
     "len_m1": _c("len_m1", plan=0, form=None, split_max=0, lite=0, narrow_k=0),

@@ -242,12 +242,12 @@ def test_split_plan_matches_lsd_passes(gpu, oracle, monkeypatch):
     assert not failures, failures
     assert len(levels - {0}) >= 3, levels
     # the large form of the local pass (sub-buckets of up to 16384 records, one workgroup of 1024 threads per CU: what a text
-    # takes whose sub-buckets outgrow 8192 at the finest level), and the split pass with published counts + look-back
+    # takes whose sub-buckets outgrow 8192 at the finest level)
     monkeypatch.delenv("SA_HIP_SPLIT_CAP", raising=False)
     monkeypatch.setenv("SA_HIP_SPLIT", "1")
     monkeypatch.setenv("SA_HIP_SPLIT_FLAGS", "1")
-    # ... and the top-digit pass in its stable form (the default with this plan: claims by global atomics), and with LDS-atomic ranks
-    for env, val in (("SA_HIP_LOCAL_BIG", "1"), ("SA_HIP_SPLIT_ATOMIC", "0"), ("SA_HIP_TOP_CLAIMS", "0"), ("SA_HIP_TOP_ARANKS", "1")):
+    # ... and the top-digit pass in its stable form (the default with this plan: claims by global atomics)
+    for env, val in (("SA_HIP_LOCAL_BIG", "1"), ("SA_HIP_TOP_CLAIMS", "0")):
         monkeypatch.setenv(env, val)
         for name, t, k0, L, cap, taken in runs[:3]:
             if k0:
@@ -487,22 +487,16 @@ def test_group_finisher_matches_global_rounds(gpu, oracle, monkeypatch):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         got, stats = {}, {}
-        for mode in ("1", "v2", "0"):
-            # "v2": round 4's restructured finisher (group_finish2_kernel: per-group depth, large groups split apart by one
-            # wave each, finals straight to their SA slots, failed groups restored) -- measured no faster, kept for A/B
+        for mode in ("1", "0"):
             monkeypatch.setenv("SA_HIP_GROUP_FINISH", "0" if mode == "0" else "1")
-            monkeypatch.setenv("SA_HIP_FIN_V2", "1" if mode == "v2" else "0")
             with gpu.DeviceIndex(t.size, 0) as idx:
                 idx.build(t, L)
                 stats[mode] = idx.build_stats()
                 assert idx.verify() == 0, (name, mode, stats[mode])
                 got[mode] = idx.sa_u32().copy()
-        monkeypatch.delenv("SA_HIP_FIN_V2", raising=False)
         for k in env:
             monkeypatch.delenv(k, raising=False)
         assert np.array_equal(got["1"], got["0"]), (name, stats)
-        assert np.array_equal(got["v2"], got["0"]), (name, stats)
-        assert stats["v2"]["finisher_runs"] > 0 or stats["1"]["finisher_runs"] == 0, (name, stats)
         assert stats["0"]["finisher_runs"] == 0
         if name.startswith("words") and L not in (1, 9):   # (L <= the initial key length: nothing to refine)
             assert stats["1"]["finisher_resolved"] > 0 and stats["1"]["active_total"] < stats["0"]["active_total"], (name, stats)

@@ -22,7 +22,7 @@ import refine_cases as rc
 
 pytestmark = pytest.mark.gpu
 
-SWITCHES = ("SA_HIP_TINY", "SA_HIP_PERIOD_FINISH", "SA_HIP_GROUP_FINISH", "SA_HIP_FIN_V2", "SA_HIP_FIN_LEFT_FAST", "SA_HIP_LOCAL_ROUNDS",
+SWITCHES = ("SA_HIP_TINY", "SA_HIP_PERIOD_FINISH", "SA_HIP_GROUP_FINISH", "SA_HIP_FIN_LEFT_FAST", "SA_HIP_LOCAL_ROUNDS",
             "SA_HIP_INITIAL_CHARS")
 _memo = {}
 
@@ -121,13 +121,12 @@ def test_tiny_finisher(gpu, oracle, monkeypatch, name):
 
 @pytest.mark.parametrize("name", list(rc.finisher_cases()))
 def test_group_finisher(gpu, oracle, monkeypatch, name):
-    """SA_HIP_TINY=0, SA_HIP_PERIOD_FINISH=0; the default kernel, group_finish2_kernel and the done-flag path give the same
-    numbers"""
+    """SA_HIP_TINY=0, SA_HIP_PERIOD_FINISH=0; the default kernel and the done-flag path give the same numbers"""
     case = rc.finisher_cases()[name]
     base = {"SA_HIP_TINY": "0", "SA_HIP_PERIOD_FINISH": "0"}
     sim = dict(tiny=False, period_finish=False)
     first = None
-    for tag, extra in (("", {}), ("+v2", {"SA_HIP_FIN_V2": "1"}), ("+flags", {"SA_HIP_FIN_LEFT_FAST": "0"})):
+    for tag, extra in (("", {}), ("+flags", {"SA_HIP_FIN_LEFT_FAST": "0"})):
         sa, st, m, g = run(gpu, oracle, monkeypatch, "fin", name, case, dict(base, **extra), sim, cap=CAPS.get(name, 256),
                            wide=(tag == "" and name in ("tile_cap_plus_1", "long_lcp")), tag=tag)
         if first is None:

@@ -21,7 +21,7 @@ import split_cases as sc
 pytestmark = pytest.mark.gpu
 
 SWITCHES = ("SA_HIP_SPLIT", "SA_HIP_INITIAL_CHARS", "SA_HIP_LOCAL_PERSIST", "SA_HIP_LOCAL_GRID", "SA_HIP_SPLIT_FLAGS", "SA_HIP_LOCAL_BIG",
-            "SA_HIP_LOCAL_BINS", "SA_HIP_SPLIT_ITEMS", "SA_HIP_SPLIT_ATOMIC", "SA_HIP_DIR_BITS", "SA_HIP_SPLIT_CAP", "SA_HIP_LITE_FLAGS",
+            "SA_HIP_LOCAL_BINS", "SA_HIP_SPLIT_ITEMS", "SA_HIP_DIR_BITS", "SA_HIP_SPLIT_CAP", "SA_HIP_LITE_FLAGS",
             "SA_HIP_TINY", "SA_HIP_GROUP_FINISH", "SA_HIP_PERIOD_FINISH")
 COUNTS = ("tiny_resolved", "finisher_runs", "finisher_records", "finisher_resolved", "period_resolved")
 _memo = {}
@@ -195,7 +195,7 @@ def test_staging_row(gpu, oracle, monkeypatch, names):
 
 @pytest.mark.parametrize("names", _by_text("tiles"))
 def test_split_pass_tiles(gpu, oracle, monkeypatch, names):
-    """buckets of T - 1, T, T + 1, 2 T and 1 records at T = 512 x 24 / 28 / 32, claims by atomics and published counts"""
+    """buckets of T - 1, T, T + 1, 2 T and 1 records at T = 512 x 24 / 28 / 32"""
     run_family(gpu, oracle, monkeypatch, names)
 
 
