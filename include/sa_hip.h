@@ -574,6 +574,57 @@ void sa_hip_free_suffix_array(sa_hip_SuffixArray_struct* sa);
 int sa_hip_write_suffix_array(const sa_hip_SuffixArray_struct* sa, const char* sa_filename, const char* is_quoted_filename);
 int sa_hip_read_suffix_array(sa_hip_SuffixArray_struct* sa, const char* sa_filename);
 
+/* ---- (6) token index: batched n-gram ranges over an int32 text and its suffix array ------------------------------------
+ * The search side of section (1d) (no counterpart in the reference): the text (int32 symbols in [0, 2^31 - 1]) and its suffix
+ * array (int32, what sa_hip_libsais_int[_device] produces; n <= 2^31 - 1) stay in HBM with two search structures -- a
+ * first-symbol directory (when max - min + 1 <= 2^24) and an array of 8-byte keys over the first two symbols of every suffix in
+ * suffix order (csrc/token_query.hpp).  4 + 4 + 8 bytes per symbol plus the directory.  A handle of its own: sa_hip_index and
+ * the byte query of section (4) are not involved.
+ *
+ * Results are {first, second} = {number of suffixes that sort before the pattern (a suffix that ends sorts before one that
+ * continues), number of suffixes that have the pattern as a prefix}: its occurrences are SA[first .. first + second).  A miss
+ * has second == 0 and first is still the exact lower bound; an empty pattern gives {0, n}.  There is no UINT32_MAX and no
+ * "last = first - 1" form here.  Pattern symbols may be any int32 (a negative one sorts below every text symbol), patterns any
+ * length, also longer than the text; Q == 0 is a no-op.
+ *
+ * Errors: NULL pointers, n < 0 and k < 1 with n >= 2 return -1 before any HIP call (T may be NULL when n == 0; n == 0 and
+ * n == 1 give a handle that answers queries); no usable device -3 (never a fallback); out of device memory -2; a negative text
+ * symbol, or (load) an SA entry outside [0, n): -1.  An in-range array that is not the suffix array gives unspecified results
+ * from bounded loops (a search is at most 32 steps, a comparison at most the pattern's length).  A handle owns a non-blocking
+ * stream and a mutex; the device form of the query is asynchronous until sa_hip_token_index_sync, the host form stages
+ * through buffers of the handle.  Nothing is read beyond offsets[Q] symbols of the patterns. */
+typedef struct sa_hip_token_index sa_hip_token_index;
+
+typedef struct sa_hip_token_info {
+    uint64_t n;
+    int64_t  min_symbol;         /* of the text (0 when n == 0)                                                      */
+    int64_t  max_symbol;
+    uint64_t dir_entries;        /* max - min + 2; 0: no directory (range beyond 2^24, n == 0, or switched off)      */
+    uint32_t key_bytes;          /* 8: the key array exists; 0: it does not (n == 0, or switched off)                */
+    uint32_t last_rank;          /* the rank of suffix n - 1                                                         */
+    double   prepare_ms;         /* device time of the search structures (alphabet, range check, directory, keys)    */
+    uint64_t q;                  /* patterns of the last search launch                                               */
+    double   kernel_ms;          /* HIP-event time of the last search launch (the call waits for it)                 */
+} sa_hip_token_info;
+
+/* Host text: upload, suffix array by the integer build of (1d) (same routes, same errors as sa_hip_libsais_int: symbols in
+ * [0, k); k == INT32_MAX admits 2^31 - 1 as a symbol as well), search structures. */
+int sa_hip_token_index_build(sa_hip_token_index** out, const int32_t* T_host, int32_t n, int32_t k, int device);
+/* Adopt a text and its suffix array that are already on `device` (both copied into the handle). */
+int sa_hip_token_index_load_device(sa_hip_token_index** out, const int32_t* T_dev, const int32_t* SA_dev, int32_t n, int device);
+void sa_hip_token_index_destroy(sa_hip_token_index* t);
+/* Pattern i = patterns[offsets[i] .. offsets[i+1]) (offsets in symbols, Q + 1 of them); out[i] as above.  Host pointers. */
+int sa_hip_token_index_query_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q, sa_hip_pair_u32* out);
+/* Every buffer in device memory; no copies, asynchronous on the handle's stream. */
+int sa_hip_token_index_query_batch_device(sa_hip_token_index* t, const void* patterns_dev, const void* offsets_dev, uint64_t Q, void* out_dev);
+int sa_hip_token_index_sync(sa_hip_token_index* t);
+/* Device pointers owned by the handle: text (int32[n]) and suffix array (int32[n]). */
+const void* sa_hip_token_index_text_dev(const sa_hip_token_index* t);
+const void* sa_hip_token_index_sa_dev(const sa_hip_token_index* t);
+/* Copy SA[first .. first + count) to the host (the positions of a range); first + count > n returns -1. */
+int sa_hip_token_index_get_sa_range(sa_hip_token_index* t, uint64_t first, uint64_t count, int32_t* out_host);
+int sa_hip_token_index_info(const sa_hip_token_index* t, sa_hip_token_info* out);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 
 /* Per-build statistics of the last build on this handle (roofline accounting). */

@@ -13,7 +13,10 @@ def __getattr__(name):
     if name == "SuffixArray":
         from . import index
         return index.SuffixArray
+    if name == "TokenIndex":
+        from . import token_index
+        return token_index.TokenIndex
     raise AttributeError(name)
 
 
-__all__ = ["SuffixArray", "DeviceIndex", "SaHipError", "PAIR_DTYPE", "UINT32_MAX"]
+__all__ = ["SuffixArray", "TokenIndex", "DeviceIndex", "SaHipError", "PAIR_DTYPE", "UINT32_MAX"]

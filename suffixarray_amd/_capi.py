@@ -30,6 +30,9 @@ EXPORTS = [
     "sa_hip_libsais_int", "sa_hip_libsais_int_omp", "sa_hip_libsais64_long", "sa_hip_libsais64_long_omp",
     "sa_hip_libsais_plcp_int", "sa_hip_libsais_plcp_int_omp", "sa_hip_libsais_int_device", "sa_hip_libsais64_long_device",
     "sa_hip_plcp_int_device", "sa_hip_sufcheck_long_device",
+    "sa_hip_token_index_build", "sa_hip_token_index_load_device", "sa_hip_token_index_destroy", "sa_hip_token_index_query_batch",
+    "sa_hip_token_index_query_batch_device", "sa_hip_token_index_sync", "sa_hip_token_index_text_dev", "sa_hip_token_index_sa_dev",
+    "sa_hip_token_index_get_sa_range", "sa_hip_token_index_info",
     "sa_hip_last_call_breakdown", "sa_hip_release_workspace",
     "sa_hip_construct_truncated_suffix_array", "sa_hip_get_substring_positions",
     "sa_hip_device_count", "sa_hip_index_create", "sa_hip_index_destroy", "sa_hip_index_build",
@@ -139,6 +142,16 @@ class IntStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
+class TokenInfo(C.Structure):
+    """sa_hip_token_info: the text, the search structures and the last search launch of a token index."""
+    _fields_ = [("n", C.c_uint64), ("min_symbol", C.c_int64), ("max_symbol", C.c_int64), ("dir_entries", C.c_uint64),
+                ("key_bytes", C.c_uint32), ("last_rank", C.c_uint32), ("prepare_ms", C.c_double), ("q", C.c_uint64),
+                ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class ReplicaLayout(C.Structure):
@@ -380,6 +393,26 @@ def lib():
     L.sa_hip_write_suffix_array.argtypes = [C.POINTER(SuffixArrayStruct), C.c_char_p, C.c_char_p]
     L.sa_hip_read_suffix_array.restype = C.c_int
     L.sa_hip_read_suffix_array.argtypes = [C.POINTER(SuffixArrayStruct), C.c_char_p]
+    L.sa_hip_token_index_build.restype = C.c_int
+    L.sa_hip_token_index_build.argtypes = [C.POINTER(vp), vp, i32, i32, C.c_int]
+    L.sa_hip_token_index_load_device.restype = C.c_int
+    L.sa_hip_token_index_load_device.argtypes = [C.POINTER(vp), vp, vp, i32, C.c_int]
+    L.sa_hip_token_index_destroy.restype = None
+    L.sa_hip_token_index_destroy.argtypes = [vp]
+    L.sa_hip_token_index_query_batch.restype = C.c_int
+    L.sa_hip_token_index_query_batch.argtypes = [vp, vp, vp, u64, vp]
+    L.sa_hip_token_index_query_batch_device.restype = C.c_int
+    L.sa_hip_token_index_query_batch_device.argtypes = [vp, vp, vp, u64, vp]
+    L.sa_hip_token_index_sync.restype = C.c_int
+    L.sa_hip_token_index_sync.argtypes = [vp]
+    L.sa_hip_token_index_text_dev.restype = vp
+    L.sa_hip_token_index_text_dev.argtypes = [vp]
+    L.sa_hip_token_index_sa_dev.restype = vp
+    L.sa_hip_token_index_sa_dev.argtypes = [vp]
+    L.sa_hip_token_index_get_sa_range.restype = C.c_int
+    L.sa_hip_token_index_get_sa_range.argtypes = [vp, u64, u64, vp]
+    L.sa_hip_token_index_info.restype = C.c_int
+    L.sa_hip_token_index_info.argtypes = [vp, C.POINTER(TokenInfo)]
     L.sa_hip_sort_pairs.restype = C.c_int
     L.sa_hip_sort_pairs.argtypes = [vp, vp, u64, C.c_int, C.c_int, C.c_int]
     L.sa_hip_synth_uniform27.restype = None
@@ -994,6 +1027,96 @@ def sufcheck_long_device(T_ptr, SA_ptr, n, device=0):
     v = C.c_uint64(0)
     check(lib().sa_hip_sufcheck_long_device(T_ptr, SA_ptr, n, device, C.byref(v)))
     return int(v.value)
+
+
+def pack_ngrams(ngrams):
+    """list of int sequences -> (packed int32 array, uint64 offsets[Q+1]); a symbol that does not fit int32 raises"""
+    off = np.zeros(len(ngrams) + 1, dtype=np.uint64)
+    if len(ngrams):
+        off[1:] = np.cumsum([len(g) for g in ngrams], dtype=np.uint64)
+    flat = [int(v) for g in ngrams for v in g]
+    if flat and (min(flat) < -2 ** 31 or max(flat) > 2 ** 31 - 1):
+        raise ValueError("pattern symbol does not fit int32")
+    return np.array(flat, dtype=np.int32), off
+
+
+class TokenIndex:
+    """Handle API of the token index (sa_hip_token_index): an int32 text, its suffix array and the n-gram search structures in
+    HBM.  Results are structured (first, second) = (suffixes that sort before the pattern, occurrences)."""
+
+    def __init__(self, handle):
+        self._h = handle
+        self._lib = lib()
+
+    @classmethod
+    def build(cls, tokens, k=None, device=0):
+        """From a host text of symbols in [0, k) (k defaults to max + 1): upload, device build, search structures."""
+        t = _int_text(tokens, np.int32)
+        h = C.c_void_p()
+        k = min(_int_k(t, k), 2 ** 31 - 1)   # (k = INT32_MAX admits the symbol 2^31 - 1 too)
+        check(lib().sa_hip_token_index_build(C.byref(h), t.ctypes.data if t.size else None, t.size, k, int(device)))
+        return cls(h)
+
+    @classmethod
+    def load_device(cls, text_dev_ptr, sa_dev_ptr, n, device=0):
+        """Adopt n int32 symbols and their int32 suffix array from device memory (copied into the handle)."""
+        h = C.c_void_p()
+        check(lib().sa_hip_token_index_load_device(C.byref(h), text_dev_ptr, sa_dev_ptr, int(n), int(device)))
+        return cls(h)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.sa_hip_token_index_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def query_batch(self, patterns):
+        """patterns: list of int sequences or (packed int32, uint64 offsets).  -> structured array (first, second)."""
+        buf, off = patterns if isinstance(patterns, tuple) else pack_ngrams(patterns)
+        buf = np.ascontiguousarray(buf, dtype=np.int32)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        q = off.size - 1
+        out = np.zeros(max(q, 1), dtype=PAIR_DTYPE)
+        if q > 0:
+            check(self._lib.sa_hip_token_index_query_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q,
+                                                           out.ctypes.data))
+        return out[:max(q, 0)]
+
+    def query_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, out_dev_ptr):
+        """Every buffer on the device; asynchronous on the handle's stream until sync()."""
+        check(self._lib.sa_hip_token_index_query_batch_device(self._h, patterns_dev_ptr, offsets_dev_ptr, q, out_dev_ptr))
+
+    def sync(self):
+        check(self._lib.sa_hip_token_index_sync(self._h))
+
+    @property
+    def text_dev(self):
+        return self._lib.sa_hip_token_index_text_dev(self._h)
+
+    @property
+    def sa_dev(self):
+        return self._lib.sa_hip_token_index_sa_dev(self._h)
+
+    def sa_range(self, first, count):
+        out = np.empty(max(count, 1), dtype=np.int32)
+        check(self._lib.sa_hip_token_index_get_sa_range(self._h, int(first), int(count), out.ctypes.data))
+        return out[:count]
+
+    def info(self):
+        st = TokenInfo()
+        check(self._lib.sa_hip_token_index_info(self._h, C.byref(st)))
+        return st.as_dict()
 
 
 def construct_truncated_suffix_array(text, max_suffix_length):
