@@ -574,7 +574,7 @@ void sa_hip_free_suffix_array(sa_hip_SuffixArray_struct* sa);
 int sa_hip_write_suffix_array(const sa_hip_SuffixArray_struct* sa, const char* sa_filename, const char* is_quoted_filename);
 int sa_hip_read_suffix_array(sa_hip_SuffixArray_struct* sa, const char* sa_filename);
 
-/* ---- (6) token index: batched n-gram ranges over an int32 text and its suffix array ------------------------------------
+/* ---- (6) token index: n-gram ranges, longest-suffix spans and next-symbol counts over an int32 text and its suffix array ----
  * The search side of section (1d) (no counterpart in the reference): the text (int32 symbols in [0, 2^31 - 1]) and its suffix
  * array (int32, what sa_hip_libsais_int[_device] produces; n <= 2^31 - 1) stay in HBM with two search structures -- a
  * first-symbol directory (when max - min + 1 <= 2^24) and an array of 8-byte keys over the first two symbols of every suffix in
@@ -624,6 +624,64 @@ const void* sa_hip_token_index_sa_dev(const sa_hip_token_index* t);
 /* Copy SA[first .. first + count) to the host (the positions of a range); first + count > n returns -1. */
 int sa_hip_token_index_get_sa_range(sa_hip_token_index* t, uint64_t first, uint64_t count, int32_t* out_host);
 int sa_hip_token_index_info(const sa_hip_token_index* t, sa_hip_token_info* out);
+
+/* (6b) longest-suffix spans and next-symbol counts (csrc/token_next.hpp): given a context, the longest suffix of it that the text
+ * holds, and which symbols follow it how often.  All results are exact.
+ *
+ * A span is the range of a matched prefix: SA[first .. first + count) all start with the same `length` symbols.  Within a span
+ * the next symbol T[SA[r] + length] is non-decreasing in r, and the one suffix that ends behind the match (ended) stands first.
+ *   mode 0, exact: the span of the whole context, length = its length; a miss keeps the exact lower bound in first, count = 0.
+ *   mode 1, longest suffix: the largest L <= min(context length, max_length) (max_length == 0: no cap) such that the last L
+ *     symbols of the context have an effective count >= 1 -- count - ended with need_next = 1, count with need_next = 0.
+ *     L = 0 gives {0, n, 0, 0}; with n == 0 every span is {0, 0, 0, 0}.
+ * The next symbols of a span are the distinct values of T[SA[r] + length] over its suffixes that have one, ascending, each with
+ * its multiplicity; at most cap (>= 1) entries per span are written, the cap smallest, to symbols[i * cap ..] and
+ * counts[i * cap ..].  Slots beyond heads[i].written are not written.  The answer is complete iff covered == total.
+ *
+ * Errors: a NULL handle or argument, mode or need_next other than 0 / 1, cap == 0, Q * cap >= 2^31 and descending offsets return
+ * -1 before any HIP call; Q == 0 is a no-op.  The device forms are asynchronous on the handle's stream until
+ * sa_hip_token_index_sync and chain without a host trip (the span output of one is the span input of the other);
+ * sa_hip_token_index_next_batch_device trusts nothing: first and count are clamped to the array, and an array that is not the
+ * suffix array gives unspecified entries from bounded loops.  The host forms stage through buffers of the handle. */
+typedef struct sa_hip_token_span {
+    uint32_t first;    /* as in sa_hip_pair_u32.first                                          */
+    uint32_t count;    /* suffixes that have the matched symbols as a prefix                   */
+    uint32_t length;   /* matched symbols: SA[first..first+count) all share this prefix        */
+    uint32_t ended;    /* 1: SA[first] + length == n (that suffix has no next symbol); else 0  */
+} sa_hip_token_span;
+
+typedef struct sa_hip_token_next {
+    uint32_t written;   /* entries written for this span, <= cap                               */
+    uint32_t covered;   /* sum of the written counts                                           */
+    uint32_t total;     /* count - ended: suffixes of the span that have a next symbol         */
+    uint32_t reserved;  /* 0                                                                   */
+} sa_hip_token_next;
+
+typedef struct sa_hip_token_next_info {
+    uint64_t q;            /* contexts or spans of the last launch of either kind               */
+    double   spans_ms;     /* HIP-event time of the last span launch (the call waits for it)    */
+    double   next_ms;      /* ... of the last next-symbol launch                                */
+    uint64_t lane_spans;   /* spans of that launch answered by one lane each (count <= 4)       */
+    uint64_t wave_spans;   /* ... walked by one wave each                                       */
+} sa_hip_token_next_info;
+
+/* Context i = patterns[offsets[i] .. offsets[i+1]); spans[Q] out.  Host pointers. */
+int sa_hip_token_index_spans_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                   int mode, uint32_t max_length, int need_next, sa_hip_token_span* spans);
+/* Every buffer in device memory; no copies, asynchronous on the handle's stream. */
+int sa_hip_token_index_spans_batch_device(sa_hip_token_index* t, const void* patterns_dev, const void* offsets_dev, uint64_t Q,
+                                          int mode, uint32_t max_length, int need_next, void* spans_dev);
+/* spans_dev: sa_hip_token_span[Q]; symbols_dev: int32[Q * cap]; counts_dev: uint32[Q * cap]; heads_dev: sa_hip_token_next[Q]. */
+int sa_hip_token_index_next_batch_device(sa_hip_token_index* t, const void* spans_dev, uint64_t Q, uint32_t cap,
+                                         void* symbols_dev, void* counts_dev, void* heads_dev);
+/* Both steps from host contexts: spans (may be NULL), symbols, counts and heads out. */
+int sa_hip_token_index_next_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                  int mode, uint32_t max_length, int need_next, uint32_t cap,
+                                  sa_hip_token_span* spans, int32_t* symbols, uint32_t* counts, sa_hip_token_next* heads);
+/* Host spans in (from an earlier call); first + count > n returns -1. */
+int sa_hip_token_index_next_of_spans(sa_hip_token_index* t, const sa_hip_token_span* spans, uint64_t Q, uint32_t cap,
+                                     int32_t* symbols, uint32_t* counts, sa_hip_token_next* heads);
+int sa_hip_token_index_next_info(const sa_hip_token_index* t, sa_hip_token_next_info* out);
 
 /* ---- instrumentation ---------------------------------------------------------------------- */
 

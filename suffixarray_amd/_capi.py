@@ -13,6 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SA_HIP_LIB", os.path.join(_HERE, "libsa_hip.so"))   # SA_HIP_LIB: A/B builds in tools/
 
 PAIR_DTYPE = np.dtype([("first", "<u4"), ("second", "<u4")])
+SPAN_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("length", "<u4"), ("ended", "<u4")])            # sa_hip_token_span
+NEXT_DTYPE = np.dtype([("written", "<u4"), ("covered", "<u4"), ("total", "<u4"), ("reserved", "<u4")])      # sa_hip_token_next
 UINT32_MAX = 0xFFFFFFFF
 
 # every symbol include/sa_hip.h declares (tests check the library exports all of them)
@@ -33,6 +35,8 @@ EXPORTS = [
     "sa_hip_token_index_build", "sa_hip_token_index_load_device", "sa_hip_token_index_destroy", "sa_hip_token_index_query_batch",
     "sa_hip_token_index_query_batch_device", "sa_hip_token_index_sync", "sa_hip_token_index_text_dev", "sa_hip_token_index_sa_dev",
     "sa_hip_token_index_get_sa_range", "sa_hip_token_index_info",
+    "sa_hip_token_index_spans_batch", "sa_hip_token_index_spans_batch_device", "sa_hip_token_index_next_batch_device",
+    "sa_hip_token_index_next_batch", "sa_hip_token_index_next_of_spans", "sa_hip_token_index_next_info",
     "sa_hip_last_call_breakdown", "sa_hip_release_workspace",
     "sa_hip_construct_truncated_suffix_array", "sa_hip_get_substring_positions",
     "sa_hip_device_count", "sa_hip_index_create", "sa_hip_index_destroy", "sa_hip_index_build",
@@ -149,6 +153,23 @@ class TokenInfo(C.Structure):
     _fields_ = [("n", C.c_uint64), ("min_symbol", C.c_int64), ("max_symbol", C.c_int64), ("dir_entries", C.c_uint64),
                 ("key_bytes", C.c_uint32), ("last_rank", C.c_uint32), ("prepare_ms", C.c_double), ("q", C.c_uint64),
                 ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenSpan(C.Structure):
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("length", C.c_uint32), ("ended", C.c_uint32)]
+
+
+class TokenNext(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("covered", C.c_uint32), ("total", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TokenNextInfo(C.Structure):
+    """sa_hip_token_next_info: the last span and next-symbol launches of a token index."""
+    _fields_ = [("q", C.c_uint64), ("spans_ms", C.c_double), ("next_ms", C.c_double), ("lane_spans", C.c_uint64),
+                ("wave_spans", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -413,6 +434,18 @@ def lib():
     L.sa_hip_token_index_get_sa_range.argtypes = [vp, u64, u64, vp]
     L.sa_hip_token_index_info.restype = C.c_int
     L.sa_hip_token_index_info.argtypes = [vp, C.POINTER(TokenInfo)]
+    L.sa_hip_token_index_spans_batch.restype = C.c_int
+    L.sa_hip_token_index_spans_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, vp]
+    L.sa_hip_token_index_spans_batch_device.restype = C.c_int
+    L.sa_hip_token_index_spans_batch_device.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, vp]
+    L.sa_hip_token_index_next_batch_device.restype = C.c_int
+    L.sa_hip_token_index_next_batch_device.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_index_next_batch.restype = C.c_int
+    L.sa_hip_token_index_next_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_index_next_of_spans.restype = C.c_int
+    L.sa_hip_token_index_next_of_spans.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_index_next_info.restype = C.c_int
+    L.sa_hip_token_index_next_info.argtypes = [vp, C.POINTER(TokenNextInfo)]
     L.sa_hip_sort_pairs.restype = C.c_int
     L.sa_hip_sort_pairs.argtypes = [vp, vp, u64, C.c_int, C.c_int, C.c_int]
     L.sa_hip_synth_uniform27.restype = None
@@ -1116,6 +1149,66 @@ class TokenIndex:
     def info(self):
         st = TokenInfo()
         check(self._lib.sa_hip_token_index_info(self._h, C.byref(st)))
+        return st.as_dict()
+
+    @staticmethod
+    def _packed(patterns):
+        buf, off = patterns if isinstance(patterns, tuple) else pack_ngrams(patterns)
+        return np.ascontiguousarray(buf, dtype=np.int32), np.ascontiguousarray(off, dtype=np.uint64)
+
+    def spans_batch(self, patterns, mode=0, max_length=0, need_next=True):
+        """patterns as in query_batch.  mode 0: the span of every whole pattern; mode 1: of its longest suffix that occurs (with
+        a next symbol when need_next), at most max_length symbols (0: no cap).  -> structured array (first, count, length, ended)."""
+        buf, off = self._packed(patterns)
+        q = off.size - 1
+        out = np.zeros(max(q, 1), dtype=SPAN_DTYPE)
+        if q > 0:
+            check(self._lib.sa_hip_token_index_spans_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
+                                                           int(max_length), int(bool(need_next)), out.ctypes.data))
+        return out[:max(q, 0)]
+
+    def spans_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, mode, max_length, need_next, spans_dev_ptr):
+        """Every buffer on the device; asynchronous on the handle's stream until sync()."""
+        check(self._lib.sa_hip_token_index_spans_batch_device(self._h, patterns_dev_ptr, offsets_dev_ptr, q, int(mode), int(max_length),
+                                                              int(bool(need_next)), spans_dev_ptr))
+
+    def next_batch_device(self, spans_dev_ptr, q, cap, symbols_dev_ptr, counts_dev_ptr, heads_dev_ptr):
+        """Next symbols of q device spans, at most cap entries each; asynchronous on the handle's stream until sync()."""
+        check(self._lib.sa_hip_token_index_next_batch_device(self._h, spans_dev_ptr, q, int(cap), symbols_dev_ptr, counts_dev_ptr,
+                                                             heads_dev_ptr))
+
+    @staticmethod
+    def _next_out(q, cap, fill):
+        return (np.full((max(q, 1), cap), fill, dtype=np.int32), np.full((max(q, 1), cap), fill & 0xFFFFFFFF, dtype=np.uint32),
+                np.zeros(max(q, 1), dtype=NEXT_DTYPE))
+
+    def next_batch(self, patterns, cap=64, mode=0, max_length=0, need_next=True, fill=0):
+        """Spans as in spans_batch, then their next symbols.  -> dict: spans [Q], symbols int32[Q, cap], counts uint32[Q, cap],
+        heads (written, covered, total, reserved)[Q].  Cells beyond heads['written'] keep `fill`."""
+        buf, off = self._packed(patterns)
+        q = off.size - 1
+        spans = np.zeros(max(q, 1), dtype=SPAN_DTYPE)
+        sym, cnt, heads = self._next_out(q, int(cap), fill)
+        if q > 0:
+            check(self._lib.sa_hip_token_index_next_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
+                                                          int(max_length), int(bool(need_next)), int(cap), spans.ctypes.data,
+                                                          sym.ctypes.data, cnt.ctypes.data, heads.ctypes.data))
+        q = max(q, 0)
+        return {"spans": spans[:q], "symbols": sym[:q], "counts": cnt[:q], "heads": heads[:q]}
+
+    def next_of_spans(self, spans, cap=64, fill=0):
+        """Next symbols of host spans (a SPAN_DTYPE array, e.g. from spans_batch); a span beyond the array raises."""
+        spans = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
+        q = spans.size
+        sym, cnt, heads = self._next_out(q, int(cap), fill)
+        if q > 0:
+            check(self._lib.sa_hip_token_index_next_of_spans(self._h, spans.ctypes.data, q, int(cap), sym.ctypes.data, cnt.ctypes.data,
+                                                             heads.ctypes.data))
+        return {"spans": spans, "symbols": sym[:q], "counts": cnt[:q], "heads": heads[:q]}
+
+    def next_info(self):
+        st = TokenNextInfo()
+        check(self._lib.sa_hip_token_index_next_info(self._h, C.byref(st)))
         return st.as_dict()
 
 

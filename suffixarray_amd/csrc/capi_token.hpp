@@ -1,8 +1,10 @@
 // capi_token.hpp -- the C ABI of the token index (include/sa_hip.h section 6), included by sa_capi.hip (same translation unit).
-// The kernels and the search structures are csrc/token_query.hpp; the suffix array of sa_hip_token_index_build comes from
+// The kernels and the search structures are csrc/token_query.hpp, spans and next symbols csrc/token_next.hpp; the suffix array of sa_hip_token_index_build comes from
 // the build behind sa_hip_libsais_int_device (capi_dropins.hpp: int_device).
 #pragma once
 #include "token_query.hpp"
+#include "token_next.hpp"
+#include <vector>
 
 struct sa_hip_token_index {
     int device = 0;
@@ -14,6 +16,17 @@ struct sa_hip_token_index {
     bool q_pending = false;              // recorded, not yet resolved
     u64 q_last = 0;
     double q_ms = 0.0;
+    // spans and next symbols (token_next.hpp)
+    tq::NextKnobs next_knobs;
+    DevBuf s_spans, s_sym, s_cnt, s_heads;   // staging of the host forms
+    DevBuf s_list;                           // [0, 64): the list's length, [64, ..): ranks of the spans left to the wave form
+    hipEvent_t sp_ev[2] = {}, nx_ev[2] = {};
+    bool sp_pending = false, nx_pending = false;
+    u64 s_last = 0;                          // contexts / spans of the last launch of either kind
+    u64 nx_q = 0;                            // spans of the last next launch
+    bool nx_lanes = false;                   // ... and whether it went through the lane form
+    double sp_ms = 0.0, nx_ms = 0.0;
+    u64 nx_lane_spans = 0, nx_wave_spans = 0;
 };
 
 namespace {
@@ -28,9 +41,13 @@ int token_create(sa_hip_token_index** out, int device, const char* who) {
     if (!t) return fail(SA_HIP_ENOMEM, who, "host allocation");
     t->device = device;
     t->x.knobs = tq::Knobs::read();
+    t->next_knobs = tq::NextKnobs::read();
     hipError_t e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&t->q_ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&t->q_ev[1]);
+    for (int j = 0; j < 2; ++j) {
+        if (e == hipSuccess) e = hipEventCreate(&t->q_ev[j]);
+        if (e == hipSuccess) e = hipEventCreate(&t->sp_ev[j]);
+        if (e == hipSuccess) e = hipEventCreate(&t->nx_ev[j]);
+    }
     if (e != hipSuccess) {
         sa_hip_token_index_destroy(t);
         return fail(e == hipErrorOutOfMemory ? SA_HIP_ENOMEM : SA_HIP_EHIP, who, hipGetErrorString(e));
@@ -49,6 +66,81 @@ int token_launch(sa_hip_token_index* t, const int32_t* pat, const u64* off, u64 
     return 0;
 }
 
+// what every spans / next entry point refuses before it touches the handle or the device
+int token_span_args(const char* who, int mode, int need_next) {
+    if (mode != 0 && mode != 1) return fail(SA_HIP_EINVAL, who, "mode is 0 (exact) or 1 (longest suffix)");
+    if (need_next != 0 && need_next != 1) return fail(SA_HIP_EINVAL, who, "need_next is 0 or 1");
+    return 0;
+}
+int token_next_args(const char* who, u64 Q, u32 cap) {
+    if (cap == 0) return fail(SA_HIP_EINVAL, who, "cap == 0");
+    if (Q > 0x7FFFFFFFull / cap || Q * cap >= 0x80000000ull) return fail(SA_HIP_EINVAL, who, "Q * cap >= 2^31");
+    return 0;
+}
+int token_offsets_args(const char* who, const int32_t* patterns, const uint64_t* offsets, u64 Q) {
+    for (u64 i = 0; i < Q; ++i) if (offsets[i + 1] < offsets[i]) return fail(SA_HIP_EINVAL, who, "offsets descend");
+    if (!patterns && offsets[Q]) return fail(SA_HIP_EINVAL, who, "NULL patterns");
+    return 0;
+}
+
+int token_launch_spans(sa_hip_token_index* t, const int32_t* pat, const u64* off, u64 Q, int mode, u32 max_length, int need_next,
+                       sa_hip_token_span* out) {
+    SA_HIP_CHECK(hipEventRecord(t->sp_ev[0], t->stream));
+    const int rc = tq::launch_spans(t->x, t->stream, pat, off, Q, mode, max_length, need_next, out);
+    if (rc) return rc;
+    SA_HIP_CHECK(hipEventRecord(t->sp_ev[1], t->stream));
+    t->sp_pending = true;
+    t->s_last = Q;
+    return 0;
+}
+
+int token_launch_next(sa_hip_token_index* t, const sa_hip_token_span* spans, u64 Q, u32 cap, int32_t* symbols, u32* counts,
+                      sa_hip_token_next* heads) {
+    int rc;
+    if (t->next_knobs.lanes && (rc = t->s_list.ensure(64 + (size_t)Q * 4))) return rc;
+    const tq::NextArgs g{spans, Q, cap, symbols, counts, heads};
+    u32* n_list = t->next_knobs.lanes ? t->s_list.as<u32>() : nullptr;
+    SA_HIP_CHECK(hipEventRecord(t->nx_ev[0], t->stream));
+    if ((rc = tq::launch_next(t->x, t->stream, t->next_knobs, g, n_list ? n_list + 16 : nullptr, n_list))) return rc;
+    SA_HIP_CHECK(hipEventRecord(t->nx_ev[1], t->stream));
+    t->nx_pending = true;
+    t->nx_q = t->s_last = Q;
+    t->nx_lanes = t->next_knobs.lanes;
+    return 0;
+}
+
+// contexts from the host into the handle's staging buffers, spans into s_spans
+int token_stage_spans(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, u64 Q, int mode, u32 max_length,
+                      int need_next) {
+    int rc;
+    const u64 total = offsets[Q];
+    if ((rc = t->q_pat.ensure((size_t)total * 4 + 64)) || (rc = t->q_off.ensure((size_t)(Q + 1) * 8)) ||
+        (rc = t->s_spans.ensure((size_t)Q * sizeof(sa_hip_token_span)))) return rc;
+    if (total) SA_HIP_CHECK(hipMemcpyAsync(t->q_pat.p, patterns, (size_t)total * 4, hipMemcpyHostToDevice, t->stream));
+    SA_HIP_CHECK(hipMemcpyAsync(t->q_off.p, offsets, (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, t->stream));
+    return token_launch_spans(t, t->q_pat.as<int32_t>(), t->q_off.as<u64>(), Q, mode, max_length, need_next, t->s_spans.as<sa_hip_token_span>());
+}
+
+// next symbols of the spans in s_spans to the host; only the written entries of a row are copied out
+int token_stage_next(sa_hip_token_index* t, u64 Q, u32 cap, int32_t* symbols, u32* counts, sa_hip_token_next* heads) {
+    int rc;
+    const size_t cells = (size_t)Q * cap;
+    if ((rc = t->s_sym.ensure(cells * 4)) || (rc = t->s_cnt.ensure(cells * 4)) || (rc = t->s_heads.ensure((size_t)Q * sizeof(sa_hip_token_next)))) return rc;
+    if ((rc = token_launch_next(t, t->s_spans.as<sa_hip_token_span>(), Q, cap, t->s_sym.as<int32_t>(), t->s_cnt.as<u32>(), t->s_heads.as<sa_hip_token_next>()))) return rc;
+    std::vector<u32> hs, hc;
+    try { hs.resize(cells); hc.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, "sa_hip_token_index_next_batch", "host allocation"); }
+    SA_HIP_CHECK(hipMemcpyAsync(heads, t->s_heads.p, (size_t)Q * sizeof(sa_hip_token_next), hipMemcpyDeviceToHost, t->stream));
+    SA_HIP_CHECK(hipMemcpyAsync(hs.data(), t->s_sym.p, cells * 4, hipMemcpyDeviceToHost, t->stream));
+    SA_HIP_CHECK(hipMemcpyAsync(hc.data(), t->s_cnt.p, cells * 4, hipMemcpyDeviceToHost, t->stream));
+    SA_HIP_CHECK(hipStreamSynchronize(t->stream));
+    for (u64 i = 0; i < Q; ++i) {
+        const size_t w = heads[i].written < cap ? heads[i].written : cap;
+        memcpy(symbols + i * cap, hs.data() + i * cap, w * 4);
+        memcpy(counts + i * cap, hc.data() + i * cap, w * 4);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -59,7 +151,12 @@ void sa_hip_token_index_destroy(sa_hip_token_index* t) {
     if (t->stream) (void)hipStreamSynchronize(t->stream);
     t->x.release();
     t->q_pat.release(); t->q_off.release(); t->q_out.release();
-    for (int j = 0; j < 2; ++j) if (t->q_ev[j]) (void)hipEventDestroy(t->q_ev[j]);
+    t->s_spans.release(); t->s_sym.release(); t->s_cnt.release(); t->s_heads.release(); t->s_list.release();
+    for (int j = 0; j < 2; ++j) {
+        if (t->q_ev[j]) (void)hipEventDestroy(t->q_ev[j]);
+        if (t->sp_ev[j]) (void)hipEventDestroy(t->sp_ev[j]);
+        if (t->nx_ev[j]) (void)hipEventDestroy(t->nx_ev[j]);
+    }
     if (t->stream) (void)hipStreamDestroy(t->stream);
     delete t;
 }
@@ -192,6 +289,119 @@ int sa_hip_token_index_info(const sa_hip_token_index* ct, sa_hip_token_info* out
     out->prepare_ms = t->x.prepare_ms;
     out->q = t->q_last;
     out->kernel_ms = t->q_ms;
+    return 0;
+}
+
+// ---- spans and next symbols.  Argument checks come first and touch neither the handle nor the device. ----------------------
+
+int sa_hip_token_index_spans_batch_device(sa_hip_token_index* t, const void* patterns_dev, const void* offsets_dev, uint64_t Q, int mode,
+                                          uint32_t max_length, int need_next, void* spans_dev) {
+    const char* who = "sa_hip_token_index_spans_batch_device";
+    if (!t) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    int rc = token_span_args(who, mode, need_next);
+    if (rc || Q == 0) return rc;
+    if (!offsets_dev || !spans_dev) return fail(SA_HIP_EINVAL, who, "NULL argument");   // (patterns may be NULL: a batch of empty contexts)
+    std::lock_guard<std::mutex> g(t->mu);
+    if ((rc = set_device(t->device))) return rc;
+    return token_launch_spans(t, static_cast<const int32_t*>(patterns_dev), static_cast<const u64*>(offsets_dev), Q, mode, max_length, need_next,
+                              static_cast<sa_hip_token_span*>(spans_dev));
+}
+
+int sa_hip_token_index_spans_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q, int mode,
+                                   uint32_t max_length, int need_next, sa_hip_token_span* spans) {
+    const char* who = "sa_hip_token_index_spans_batch";
+    if (!t) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    int rc = token_span_args(who, mode, need_next);
+    if (rc || Q == 0) return rc;
+    if (!offsets || !spans) return fail(SA_HIP_EINVAL, who, "NULL argument");
+    if ((rc = token_offsets_args(who, patterns, offsets, Q))) return rc;
+    std::lock_guard<std::mutex> g(t->mu);
+    if ((rc = set_device(t->device))) return rc;
+    if ((rc = token_stage_spans(t, patterns, offsets, Q, mode, max_length, need_next))) return rc;
+    SA_HIP_CHECK(hipMemcpyAsync(spans, t->s_spans.p, (size_t)Q * sizeof(sa_hip_token_span), hipMemcpyDeviceToHost, t->stream));
+    SA_HIP_CHECK(hipStreamSynchronize(t->stream));
+    return 0;
+}
+
+int sa_hip_token_index_next_batch_device(sa_hip_token_index* t, const void* spans_dev, uint64_t Q, uint32_t cap, void* symbols_dev,
+                                         void* counts_dev, void* heads_dev) {
+    const char* who = "sa_hip_token_index_next_batch_device";
+    if (!t) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    int rc = token_next_args(who, Q, cap);
+    if (rc || Q == 0) return rc;
+    if (!spans_dev || !symbols_dev || !counts_dev || !heads_dev) return fail(SA_HIP_EINVAL, who, "NULL argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    if ((rc = set_device(t->device))) return rc;
+    return token_launch_next(t, static_cast<const sa_hip_token_span*>(spans_dev), Q, cap, static_cast<int32_t*>(symbols_dev),
+                             static_cast<u32*>(counts_dev), static_cast<sa_hip_token_next*>(heads_dev));
+}
+
+int sa_hip_token_index_next_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q, int mode,
+                                  uint32_t max_length, int need_next, uint32_t cap, sa_hip_token_span* spans, int32_t* symbols,
+                                  uint32_t* counts, sa_hip_token_next* heads) {
+    const char* who = "sa_hip_token_index_next_batch";
+    if (!t) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    int rc = token_span_args(who, mode, need_next);
+    if (rc || (rc = token_next_args(who, Q, cap)) || Q == 0) return rc;
+    if (!offsets || !symbols || !counts || !heads) return fail(SA_HIP_EINVAL, who, "NULL argument");   // (spans may be NULL)
+    if ((rc = token_offsets_args(who, patterns, offsets, Q))) return rc;
+    std::lock_guard<std::mutex> g(t->mu);
+    if ((rc = set_device(t->device))) return rc;
+    if ((rc = token_stage_spans(t, patterns, offsets, Q, mode, max_length, need_next))) return rc;
+    if (spans) SA_HIP_CHECK(hipMemcpyAsync(spans, t->s_spans.p, (size_t)Q * sizeof(sa_hip_token_span), hipMemcpyDeviceToHost, t->stream));
+    return token_stage_next(t, Q, cap, symbols, counts, heads);
+}
+
+int sa_hip_token_index_next_of_spans(sa_hip_token_index* t, const sa_hip_token_span* spans, uint64_t Q, uint32_t cap, int32_t* symbols,
+                                     uint32_t* counts, sa_hip_token_next* heads) {
+    const char* who = "sa_hip_token_index_next_of_spans";
+    if (!t) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    int rc = token_next_args(who, Q, cap);
+    if (rc || Q == 0) return rc;
+    if (!spans || !symbols || !counts || !heads) return fail(SA_HIP_EINVAL, who, "NULL argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    for (u64 i = 0; i < Q; ++i)
+        if (spans[i].first > t->x.n || spans[i].count > t->x.n - spans[i].first) return fail(SA_HIP_EINVAL, who, "span beyond the suffix array");
+    if ((rc = set_device(t->device))) return rc;
+    if ((rc = t->s_spans.ensure((size_t)Q * sizeof(sa_hip_token_span)))) return rc;
+    SA_HIP_CHECK(hipMemcpyAsync(t->s_spans.p, spans, (size_t)Q * sizeof(sa_hip_token_span), hipMemcpyHostToDevice, t->stream));
+    return token_stage_next(t, Q, cap, symbols, counts, heads);
+}
+
+int sa_hip_token_index_next_info(const sa_hip_token_index* ct, sa_hip_token_next_info* out) {
+    if (!ct || !out) return fail(SA_HIP_EINVAL, "sa_hip_token_index_next_info", "NULL argument");
+    sa_hip_token_index* t = const_cast<sa_hip_token_index*>(ct);
+    std::lock_guard<std::mutex> g(t->mu);
+    if (t->sp_pending || t->nx_pending) {
+        int rc = set_device(t->device);
+        if (rc) return rc;
+        float ms = 0.f;
+        if (t->sp_pending) {
+            SA_HIP_CHECK(hipEventSynchronize(t->sp_ev[1]));
+            SA_HIP_CHECK(hipEventElapsedTime(&ms, t->sp_ev[0], t->sp_ev[1]));
+            t->sp_ms = ms;
+            t->sp_pending = false;
+        }
+        if (t->nx_pending) {
+            SA_HIP_CHECK(hipEventSynchronize(t->nx_ev[1]));
+            SA_HIP_CHECK(hipEventElapsedTime(&ms, t->nx_ev[0], t->nx_ev[1]));
+            t->nx_ms = ms;
+            u32 left = 0;   // the list's length: the spans the lane form left to the wave form
+            if (t->nx_lanes) {
+                SA_HIP_CHECK(hipMemcpyAsync(&left, t->s_list.p, sizeof left, hipMemcpyDeviceToHost, t->stream));
+                SA_HIP_CHECK(hipStreamSynchronize(t->stream));
+            }
+            t->nx_wave_spans = t->nx_lanes ? (u64)left : t->nx_q;
+            t->nx_lane_spans = t->nx_q - t->nx_wave_spans;
+            t->nx_pending = false;
+        }
+    }
+    memset(out, 0, sizeof *out);
+    out->q = t->s_last;
+    out->spans_ms = t->sp_ms;
+    out->next_ms = t->nx_ms;
+    out->lane_spans = t->nx_lane_spans;
+    out->wave_spans = t->nx_wave_spans;
     return 0;
 }
 

@@ -23,8 +23,10 @@
 // index range (at most 32 steps, n < 2^31), a comparison reads at most min(pattern length, n) symbols.  SA entries are
 // range-checked once (tq_sa_check_kernel), so T[SA[m] + j] with the j < n - SA[m] test never leaves the text.
 //
-// Out of scope here: int64 texts and libsais64_long arrays, byte arrays with 64-bit indices, next-symbol distributions of a
-// range, multi-GPU sharding of token queries, and anything in bench.py.
+// Longest-suffix spans and the next symbols of a range (with their counts) are token_next.hpp, on top of tq_range below.
+//
+// Out of scope here: int64 texts and libsais64_long arrays, byte arrays with 64-bit indices, multi-GPU sharding of token
+// queries, and anything in bench.py.
 #pragma once
 #include "int_build.hpp"
 #include "scan.hpp"
@@ -150,19 +152,14 @@ __device__ __forceinline__ void tq_text_bounds(const View& x, const int32_t* __r
     *hi = lo2 < lo1 ? lo1 : lo2;
 }
 
-__global__ __launch_bounds__(BLOCK) void tq_search_kernel(View x, const int32_t* __restrict__ pat, const u64* __restrict__ off, u64 Q,
-                                                          sa_hip_pair_u32* __restrict__ out) {
-    const u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= Q) return;
-    const u64 o0 = off[i], o1 = off[i + 1];
-    const u64 m = o1 > o0 ? o1 - o0 : 0;
-    const int32_t* P = pat + o0;
+// {first, count} of the pattern P[0 .. m): what one lane of tq_search_kernel computes (token_next.hpp probes with it as well)
+__device__ __forceinline__ sa_hip_pair_u32 tq_range(const View& x, const int32_t* __restrict__ P, u64 m) {
     sa_hip_pair_u32 res{0u, 0u};
-    if (m == 0) { res.second = x.n; out[i] = res; return; }
-    if (x.n == 0) { out[i] = res; return; }
+    if (m == 0) { res.second = x.n; return res; }
+    if (x.n == 0) return res;
     const int32_t v = P[0];
-    if (v < x.mn) { out[i] = res; return; }                      // below every suffix (a negative symbol among them)
-    if (v > x.mx) { res.first = x.n; out[i] = res; return; }     // above every suffix
+    if (v < x.mn) return res;                                    // below every suffix (a negative symbol among them)
+    if (v > x.mx) { res.first = x.n; return res; }               // above every suffix
     u32 lo = 0, hi = x.n;
     if (x.dir) {
         lo = x.dir[(u32)(v - x.mn)];
@@ -170,7 +167,7 @@ __global__ __launch_bounds__(BLOCK) void tq_search_kernel(View x, const int32_t*
         if (hi < lo) hi = lo;
         if (hi > x.n) hi = x.n;   // (a directory of this handle spans [0, n]; a bound for the loads all the same)
         if (lo > hi) lo = hi;
-        if (m == 1 || lo == hi) { res.first = lo; res.second = hi - lo; out[i] = res; return; }
+        if (m == 1 || lo == hi) { res.first = lo; res.second = hi - lo; return res; }
     }
     if (x.K) {
         const int32_t w = m >= 2 ? P[1] : 0;
@@ -183,8 +180,7 @@ __global__ __launch_bounds__(BLOCK) void tq_search_kernel(View x, const int32_t*
         if (m >= 2 && w < 0) {
             // [v, negative, ...]: after the suffix that ends behind v (the first of v's suffixes when v = T[n - 1]), before every other
             res.first = lo + ((lo < hi && x.last_rank == lo) ? 1u : 0u);
-            out[i] = res;
-            return;
+            return res;
         }
         if (m > 2 && lo < hi) tq_text_bounds(x, P, m, 2, &lo, &hi);
     } else {
@@ -192,7 +188,15 @@ __global__ __launch_bounds__(BLOCK) void tq_search_kernel(View x, const int32_t*
     }
     res.first = lo;
     res.second = hi - lo;
-    out[i] = res;
+    return res;
+}
+
+__global__ __launch_bounds__(BLOCK) void tq_search_kernel(View x, const int32_t* __restrict__ pat, const u64* __restrict__ off, u64 Q,
+                                                          sa_hip_pair_u32* __restrict__ out) {
+    const u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= Q) return;
+    const u64 o0 = off[i], o1 = off[i + 1];
+    out[i] = tq_range(x, pat + o0, o1 > o0 ? o1 - o0 : 0);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------

@@ -3,6 +3,8 @@
     ti = TokenIndex(tokens)                # upload, suffix array (sa_hip_libsais_int's build), search structures
     ti.count([[464, 2068], [11]])          # occurrences of every n-gram: uint32[Q]
     ti.positions([464, 2068], limit=10)    # where: text positions in suffix order
+    ti.next_token_counts([464, 2068])      # {token: count} of what follows the n-gram
+    ti.next_tokens(contexts, cap=64, longest_suffix=True)   # the same per context, backing off to its longest suffix that occurs
 
 On top of the handle API of include/sa_hip.h section 6 (suffixarray_amd._capi.TokenIndex).  No CPU fallback.
 """
@@ -33,6 +35,28 @@ class TokenIndex:
         first, count = self.ranges([list(ngram)])
         c = int(count[0]) if limit is None else min(int(count[0]), int(limit))
         return self._idx.sa_range(int(first[0]), c)
+
+    def longest_suffix(self, contexts, max_length=None, need_next=True):
+        """-> (length, first, count), uint32[Q] each: the longest suffix of context i (at most max_length symbols) that occurs in
+        the text -- with need_next, that occurs with a symbol behind it -- and its range.  length 0: nothing matched, {0, n}."""
+        s = self._idx.spans_batch(contexts, mode=1, max_length=max_length or 0, need_next=need_next)
+        return s["length"].copy(), s["first"].copy(), s["count"].copy()
+
+    def next_tokens(self, ngrams, cap=64, longest_suffix=False, max_length=None):
+        """Which tokens follow every n-gram, and how often.  -> dict of arrays: symbols int32[Q, cap] (ascending) and counts
+        uint32[Q, cap], of which the first written[i] are valid in row i; total[i] = occurrences that have a next token;
+        length[i] = matched symbols; complete[i] = every distinct next token fits in cap (else the cap smallest are given).
+        longest_suffix: an n-gram backs off to its longest suffix (at most max_length symbols) that has a next token."""
+        r = self._idx.next_batch(ngrams, cap=cap, mode=1 if longest_suffix else 0, max_length=max_length or 0, need_next=True)
+        h = r["heads"]
+        return {"symbols": r["symbols"], "counts": r["counts"], "written": h["written"].copy(), "total": h["total"].copy(),
+                "length": r["spans"]["length"].copy(), "complete": h["covered"] == h["total"]}
+
+    def next_token_counts(self, ngram, cap=64, longest_suffix=False, max_length=None):
+        """{token: count} of what follows one n-gram (the cap smallest tokens when there are more)"""
+        r = self.next_tokens([list(ngram)], cap=cap, longest_suffix=longest_suffix, max_length=max_length)
+        w = int(r["written"][0])
+        return {int(s): int(c) for s, c in zip(r["symbols"][0, :w], r["counts"][0, :w])}
 
     def info(self):
         return self._idx.info()
