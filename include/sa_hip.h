@@ -683,6 +683,88 @@ int sa_hip_token_index_next_of_spans(sa_hip_token_index* t, const sa_hip_token_s
                                      int32_t* symbols, uint32_t* counts, sa_hip_token_next* heads);
 int sa_hip_token_index_next_info(const sa_hip_token_index* t, sa_hip_token_next_info* out);
 
+/* (6c) shard sets (csrc/token_shards.hpp, csrc/capi_token_shards.hpp): S token indexes on ONE device, 1 <= S <= 64, answered as
+ * one corpus that was cut at document boundaries -- an n-gram never spans two shards.  Counts are summed over the shards as
+ * uint64, the longest suffix is the longest one that ANY shard holds, next-symbol lists are merged.  Every per-shard array is
+ * shard-major: entry [s * Q + i] belongs to shard s and pattern / context i.
+ *
+ *   ranges  per_shard[s * Q + i] is what shard s's own sa_hip_token_index_query_batch answers for pattern i (a miss keeps the
+ *           exact lower bound in first); totals[i] = sum over s of second.  per_shard may be NULL.
+ *   spans   mode 0: spans[s * Q + i] is shard s's mode-0 span of the whole context; length[i] = the context's length.
+ *           mode 1: L_i = the largest L <= min(context length, max_length) (max_length == 0: no cap) such that the SUM over the
+ *           shards of the effective counts of the last L symbols is >= 1 (effective: count - ended with need_next = 1, count
+ *           with need_next = 0); spans[s * Q + i] is what shard s's own spans_batch answers in mode 0 for those last L_i symbols:
+ *           count 0 with the exact lower bound where the shard does not hold them, {first, 1, L_i, 1} where they only end the
+ *           shard's text.  length[i] = L_i.  In both modes totals[i] = the sum of the effective counts.
+ *   next    the distinct next symbols over the union of the S spans of a context, ascending, their counts summed as uint64; at
+ *           most cap entries, the cap smallest, to symbols[i * cap ..] and counts[i * cap ..]; slots beyond heads[i].written are
+ *           not written.  Merging the shards' own cap-smallest lists is exact: a symbol among the union's cap smallest has at
+ *           most that rank among the symbols of every shard that holds it.  total = sum over s of (count_s - ended_s), covered =
+ *           the sum of the written counts; the answer is complete iff covered == total.  length = the largest `length` among
+ *           the context's S spans (0 from sa_hip_token_shards_merge_device, which sees no spans).
+ *
+ * sa_hip_token_shards_create adopts the handles: the set owns them from then on and sa_hip_token_shards_destroy destroys them;
+ * on any error none is adopted.  NULL arguments, S == 0, S > 64, a NULL entry, a repeated entry and handles on different devices
+ * return -1 before any HIP call.  The other argument errors are those of (6b): NULL pointers, mode or need_next other than 0 / 1,
+ * cap == 0, Q * cap >= 2^31 and descending offsets return -1 before any HIP call; Q == 0 is a no-op; no usable device -3.  A set
+ * owns a non-blocking stream and a mutex; the device forms are asynchronous on that stream until sa_hip_token_shards_sync and
+ * chain without a host trip.  The per-shard lists of the next-symbol calls live in scratch of the set, S * cap * 8 bytes per
+ * context: the batch is worked through in chunks of contexts sized by a scratch budget (sa_hip_token_shards_stats.chunk: the
+ * contexts per chunk of the last such call). */
+typedef struct sa_hip_token_shards sa_hip_token_shards;
+
+typedef struct sa_hip_token_shards_next {
+    uint32_t written;   /* entries written for this context, <= cap                            */
+    uint32_t length;    /* matched symbols (see above)                                         */
+    uint64_t covered;   /* sum of the written counts                                           */
+    uint64_t total;     /* suffixes of the S spans that have a next symbol                     */
+} sa_hip_token_shards_next;
+
+typedef struct sa_hip_token_shards_stats {
+    uint32_t shards;       /* S                                                                            */
+    uint32_t chunk;        /* contexts per chunk of the last next-symbol call (0: none yet)                */
+    uint64_t tokens;       /* sum of the shards' lengths                                                   */
+    uint64_t q;            /* patterns / contexts of the last launch of any kind                           */
+    double   ranges_ms;    /* HIP-event time of the last ranges launch (the call waits for it)             */
+    double   spans_ms;     /* ... of the last spans launch                                                 */
+    double   next_ms;      /* ... of the per-shard next-symbol launches of the last call, over its chunks  */
+    double   merge_ms;     /* ... of its merge launches, over its chunks                                   */
+} sa_hip_token_shards_stats;
+
+int sa_hip_token_shards_create(sa_hip_token_shards** out, sa_hip_token_index* const* shards, uint32_t S);
+void sa_hip_token_shards_destroy(sa_hip_token_shards* set);
+/* The borrowed handle of shard s (NULL: no such shard); the caller serialises its use against the set's calls. */
+sa_hip_token_index* sa_hip_token_shards_shard(sa_hip_token_shards* set, uint32_t s);
+int sa_hip_token_shards_sync(sa_hip_token_shards* set);
+int sa_hip_token_shards_info(const sa_hip_token_shards* set, sa_hip_token_shards_stats* out);
+/* totals[Q]; per_shard[S * Q] or NULL.  Host pointers. */
+int sa_hip_token_shards_query_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                    uint64_t* totals, sa_hip_pair_u32* per_shard);
+/* Every buffer in device memory (per_shard_dev may be NULL); asynchronous on the set's stream. */
+int sa_hip_token_shards_query_batch_device(sa_hip_token_shards* set, const void* patterns_dev, const void* offsets_dev, uint64_t Q,
+                                           void* totals_dev, void* per_shard_dev);
+/* length[Q], totals[Q], spans[S * Q].  Host pointers. */
+int sa_hip_token_shards_spans_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                    int mode, uint32_t max_length, int need_next, uint32_t* length, uint64_t* totals,
+                                    sa_hip_token_span* spans);
+int sa_hip_token_shards_spans_batch_device(sa_hip_token_shards* set, const void* patterns_dev, const void* offsets_dev, uint64_t Q,
+                                           int mode, uint32_t max_length, int need_next, void* length_dev, void* totals_dev,
+                                           void* spans_dev);
+/* Both steps from host contexts: spans[S * Q] (may be NULL), symbols int32[Q * cap], counts uint64[Q * cap], heads[Q] out. */
+int sa_hip_token_shards_next_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                   int mode, uint32_t max_length, int need_next, uint32_t cap, sa_hip_token_span* spans,
+                                   int32_t* symbols, uint64_t* counts, sa_hip_token_shards_next* heads);
+/* spans_dev: sa_hip_token_span[S * Q] as sa_hip_token_shards_spans_batch_device wrote them; the outputs as above, on the device.
+ * Trusts nothing, like sa_hip_token_index_next_batch_device. */
+int sa_hip_token_shards_next_batch_device(sa_hip_token_shards* set, const void* spans_dev, uint64_t Q, uint32_t cap,
+                                          void* symbols_dev, void* counts_dev, void* heads_dev);
+/* The last step of the two calls above on its own: S lists per context as the shards' next-symbol launches write them --
+ * symbols_dev int32[S * Q * cap] (row (s * Q + i) * cap, ascending), counts_dev uint32[S * Q * cap], heads_dev
+ * sa_hip_token_next[S * Q] (written is clamped to cap) -- merged into out_symbols_dev int32[Q * cap], out_counts_dev
+ * uint64[Q * cap], out_heads_dev sa_hip_token_shards_next[Q].  Asynchronous on the set's stream. */
+int sa_hip_token_shards_merge_device(sa_hip_token_shards* set, const void* symbols_dev, const void* counts_dev, const void* heads_dev,
+                                     uint64_t Q, uint32_t cap, void* out_symbols_dev, void* out_counts_dev, void* out_heads_dev);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 
 /* Per-build statistics of the last build on this handle (roofline accounting). */

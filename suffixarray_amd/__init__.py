@@ -16,7 +16,10 @@ def __getattr__(name):
     if name == "TokenIndex":
         from . import token_index
         return token_index.TokenIndex
+    if name == "ShardedTokenIndex":
+        from . import token_shards
+        return token_shards.ShardedTokenIndex
     raise AttributeError(name)
 
 
-__all__ = ["SuffixArray", "TokenIndex", "DeviceIndex", "SaHipError", "PAIR_DTYPE", "UINT32_MAX"]
+__all__ = ["SuffixArray", "TokenIndex", "ShardedTokenIndex", "DeviceIndex", "SaHipError", "PAIR_DTYPE", "UINT32_MAX"]

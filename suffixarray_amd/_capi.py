@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("SA_HIP_LIB", os.path.join(_HERE, "libsa_hip.so"))   #
 PAIR_DTYPE = np.dtype([("first", "<u4"), ("second", "<u4")])
 SPAN_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("length", "<u4"), ("ended", "<u4")])            # sa_hip_token_span
 NEXT_DTYPE = np.dtype([("written", "<u4"), ("covered", "<u4"), ("total", "<u4"), ("reserved", "<u4")])      # sa_hip_token_next
+SHARDS_NEXT_DTYPE = np.dtype([("written", "<u4"), ("length", "<u4"), ("covered", "<u8"), ("total", "<u8")])  # sa_hip_token_shards_next
+SHARDS_MAX = 64
 UINT32_MAX = 0xFFFFFFFF
 
 # every symbol include/sa_hip.h declares (tests check the library exports all of them)
@@ -37,6 +39,10 @@ EXPORTS = [
     "sa_hip_token_index_get_sa_range", "sa_hip_token_index_info",
     "sa_hip_token_index_spans_batch", "sa_hip_token_index_spans_batch_device", "sa_hip_token_index_next_batch_device",
     "sa_hip_token_index_next_batch", "sa_hip_token_index_next_of_spans", "sa_hip_token_index_next_info",
+    "sa_hip_token_shards_create", "sa_hip_token_shards_destroy", "sa_hip_token_shards_shard", "sa_hip_token_shards_sync",
+    "sa_hip_token_shards_info", "sa_hip_token_shards_query_batch", "sa_hip_token_shards_query_batch_device",
+    "sa_hip_token_shards_spans_batch", "sa_hip_token_shards_spans_batch_device", "sa_hip_token_shards_next_batch",
+    "sa_hip_token_shards_next_batch_device", "sa_hip_token_shards_merge_device",
     "sa_hip_last_call_breakdown", "sa_hip_release_workspace",
     "sa_hip_construct_truncated_suffix_array", "sa_hip_get_substring_positions",
     "sa_hip_device_count", "sa_hip_index_create", "sa_hip_index_destroy", "sa_hip_index_build",
@@ -170,6 +176,19 @@ class TokenNextInfo(C.Structure):
     """sa_hip_token_next_info: the last span and next-symbol launches of a token index."""
     _fields_ = [("q", C.c_uint64), ("spans_ms", C.c_double), ("next_ms", C.c_double), ("lane_spans", C.c_uint64),
                 ("wave_spans", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenShardsNext(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("length", C.c_uint32), ("covered", C.c_uint64), ("total", C.c_uint64)]
+
+
+class TokenShardsStats(C.Structure):
+    """sa_hip_token_shards_stats: a shard set and its last ranges, spans and next-symbol launches."""
+    _fields_ = [("shards", C.c_uint32), ("chunk", C.c_uint32), ("tokens", C.c_uint64), ("q", C.c_uint64), ("ranges_ms", C.c_double),
+                ("spans_ms", C.c_double), ("next_ms", C.c_double), ("merge_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -446,6 +465,30 @@ def lib():
     L.sa_hip_token_index_next_of_spans.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, vp]
     L.sa_hip_token_index_next_info.restype = C.c_int
     L.sa_hip_token_index_next_info.argtypes = [vp, C.POINTER(TokenNextInfo)]
+    L.sa_hip_token_shards_create.restype = C.c_int
+    L.sa_hip_token_shards_create.argtypes = [C.POINTER(vp), vp, C.c_uint32]
+    L.sa_hip_token_shards_destroy.restype = None
+    L.sa_hip_token_shards_destroy.argtypes = [vp]
+    L.sa_hip_token_shards_shard.restype = vp
+    L.sa_hip_token_shards_shard.argtypes = [vp, C.c_uint32]
+    L.sa_hip_token_shards_sync.restype = C.c_int
+    L.sa_hip_token_shards_sync.argtypes = [vp]
+    L.sa_hip_token_shards_info.restype = C.c_int
+    L.sa_hip_token_shards_info.argtypes = [vp, C.POINTER(TokenShardsStats)]
+    L.sa_hip_token_shards_query_batch.restype = C.c_int
+    L.sa_hip_token_shards_query_batch.argtypes = [vp, vp, vp, u64, vp, vp]
+    L.sa_hip_token_shards_query_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_query_batch_device.argtypes = [vp, vp, vp, u64, vp, vp]
+    L.sa_hip_token_shards_spans_batch.restype = C.c_int
+    L.sa_hip_token_shards_spans_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, vp, vp, vp]
+    L.sa_hip_token_shards_spans_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_spans_batch_device.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, vp, vp, vp]
+    L.sa_hip_token_shards_next_batch.restype = C.c_int
+    L.sa_hip_token_shards_next_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_shards_next_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_next_batch_device.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_shards_merge_device.restype = C.c_int
+    L.sa_hip_token_shards_merge_device.argtypes = [vp, vp, vp, vp, u64, C.c_uint32, vp, vp, vp]
     L.sa_hip_sort_pairs.restype = C.c_int
     L.sa_hip_sort_pairs.argtypes = [vp, vp, u64, C.c_int, C.c_int, C.c_int]
     L.sa_hip_synth_uniform27.restype = None
@@ -1210,6 +1253,139 @@ class TokenIndex:
         st = TokenNextInfo()
         check(self._lib.sa_hip_token_index_next_info(self._h, C.byref(st)))
         return st.as_dict()
+
+
+class _BorrowedTokenIndex(TokenIndex):
+    """A shard of a TokenShards set: the set owns the handle, close() only lets go of it."""
+
+    def close(self):
+        self._h = C.c_void_p()
+
+
+class TokenShards:
+    """Handle API of a shard set (sa_hip_token_shards): S <= 64 token indexes on one device answered as one corpus.  Per-shard
+    results are shard-major arrays of shape [S, Q]."""
+
+    def __init__(self, handle, shards):
+        self._h = handle
+        self._lib = lib()
+        self.shards = int(shards)
+
+    @classmethod
+    def create(cls, indexes):
+        """Adopts the TokenIndex handles: on success they belong to the set and the wrappers passed in are emptied."""
+        indexes = list(indexes)
+        arr = (C.c_void_p * max(len(indexes), 1))(*[t._h.value if isinstance(t._h, C.c_void_p) else t._h for t in indexes])
+        h = C.c_void_p()
+        check(lib().sa_hip_token_shards_create(C.byref(h), arr, len(indexes)))
+        for t in indexes:
+            t._h = C.c_void_p()
+        return cls(h, len(indexes))
+
+    @classmethod
+    def build(cls, texts, k=None, device=0):
+        """One TokenIndex.build per text, then create(); a failure closes what was built."""
+        built = []
+        try:
+            for t in texts:
+                built.append(TokenIndex.build(t, k, device))
+            return cls.create(built)
+        except Exception:
+            for t in built:
+                t.close()
+            raise
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.sa_hip_token_shards_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def shard(self, s):
+        """The borrowed TokenIndex of shard s (valid while the set lives; do not use it while the set is being asked)."""
+        h = self._lib.sa_hip_token_shards_shard(self._h, int(s))
+        if not h:
+            raise IndexError("no shard %d" % s)
+        return _BorrowedTokenIndex(C.c_void_p(h))
+
+    def sync(self):
+        check(self._lib.sa_hip_token_shards_sync(self._h))
+
+    def info(self):
+        st = TokenShardsStats()
+        check(self._lib.sa_hip_token_shards_info(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def query_batch(self, patterns, per_shard=True):
+        """-> (totals uint64[Q], per_shard structured (first, second)[S, Q] or None)"""
+        buf, off = TokenIndex._packed(patterns)
+        q = off.size - 1
+        totals = np.zeros(max(q, 1), dtype=np.uint64)
+        per = np.zeros((self.shards, max(q, 1)), dtype=PAIR_DTYPE) if per_shard else None
+        if q > 0:
+            check(self._lib.sa_hip_token_shards_query_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q,
+                                                            totals.ctypes.data, per.ctypes.data if per_shard else None))
+        q = max(q, 0)
+        return totals[:q], (per[:, :q] if per_shard else None)
+
+    def query_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, totals_dev_ptr, per_shard_dev_ptr=None):
+        """Every buffer on the device; asynchronous on the set's stream until sync()."""
+        check(self._lib.sa_hip_token_shards_query_batch_device(self._h, patterns_dev_ptr, offsets_dev_ptr, q, totals_dev_ptr, per_shard_dev_ptr))
+
+    def spans_batch(self, patterns, mode=0, max_length=0, need_next=True):
+        """-> dict: length uint32[Q], totals uint64[Q], spans structured (first, count, length, ended)[S, Q]"""
+        buf, off = TokenIndex._packed(patterns)
+        q = off.size - 1
+        length = np.zeros(max(q, 1), dtype=np.uint32)
+        totals = np.zeros(max(q, 1), dtype=np.uint64)
+        spans = np.zeros((self.shards, max(q, 1)), dtype=SPAN_DTYPE)
+        if q > 0:
+            check(self._lib.sa_hip_token_shards_spans_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
+                                                            int(max_length), int(bool(need_next)), length.ctypes.data, totals.ctypes.data,
+                                                            spans.ctypes.data))
+        q = max(q, 0)
+        return {"length": length[:q], "totals": totals[:q], "spans": spans[:, :q]}
+
+    def spans_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, mode, max_length, need_next, length_dev_ptr, totals_dev_ptr, spans_dev_ptr):
+        check(self._lib.sa_hip_token_shards_spans_batch_device(self._h, patterns_dev_ptr, offsets_dev_ptr, q, int(mode), int(max_length),
+                                                               int(bool(need_next)), length_dev_ptr, totals_dev_ptr, spans_dev_ptr))
+
+    def next_batch(self, patterns, cap=64, mode=0, max_length=0, need_next=True, fill=0):
+        """Spans as in spans_batch, then the merged next symbols.  -> dict: spans [S, Q], symbols int32[Q, cap], counts
+        uint64[Q, cap], heads (written, length, covered, total)[Q].  Cells beyond heads['written'] keep `fill`."""
+        buf, off = TokenIndex._packed(patterns)
+        q = off.size - 1
+        cap = int(cap)
+        spans = np.zeros((self.shards, max(q, 1)), dtype=SPAN_DTYPE)
+        sym = np.full((max(q, 1), cap), fill, dtype=np.int32)
+        cnt = np.full((max(q, 1), cap), fill & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        heads = np.zeros(max(q, 1), dtype=SHARDS_NEXT_DTYPE)
+        if q > 0:
+            check(self._lib.sa_hip_token_shards_next_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
+                                                           int(max_length), int(bool(need_next)), cap, spans.ctypes.data, sym.ctypes.data,
+                                                           cnt.ctypes.data, heads.ctypes.data))
+        q = max(q, 0)
+        return {"spans": spans[:, :q], "symbols": sym[:q], "counts": cnt[:q], "heads": heads[:q]}
+
+    def next_batch_device(self, spans_dev_ptr, q, cap, symbols_dev_ptr, counts_dev_ptr, heads_dev_ptr):
+        """Merged next symbols of q contexts from their S * q device spans; asynchronous on the set's stream until sync()."""
+        check(self._lib.sa_hip_token_shards_next_batch_device(self._h, spans_dev_ptr, q, int(cap), symbols_dev_ptr, counts_dev_ptr, heads_dev_ptr))
+
+    def merge_device(self, symbols_dev_ptr, counts_dev_ptr, heads_dev_ptr, q, cap, out_symbols_dev_ptr, out_counts_dev_ptr, out_heads_dev_ptr):
+        """The merge step alone, on S * q device lists; asynchronous on the set's stream until sync()."""
+        check(self._lib.sa_hip_token_shards_merge_device(self._h, symbols_dev_ptr, counts_dev_ptr, heads_dev_ptr, q, int(cap),
+                                                         out_symbols_dev_ptr, out_counts_dev_ptr, out_heads_dev_ptr))
 
 
 def construct_truncated_suffix_array(text, max_suffix_length):

@@ -1,0 +1,388 @@
+// capi_token_shards.hpp -- the C ABI of the shard set (include/sa_hip.h section 6c), included by sa_capi.hip behind capi_token.hpp
+// (same translation unit).  The kernels are csrc/token_shards.hpp; the per-shard next symbols are tq::launch_next of every shard.
+#pragma once
+#include "capi_token.hpp"
+#include "token_shards.hpp"
+
+struct sa_hip_token_shards {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+    u32 S = 0;
+    sa_hip_token_index* shard[tq::SHARDS_MAX] = {};
+    u64 tokens = 0;
+    u32 max_n = 0;
+    u64 chunk_knob = 0;                      // SA_HIP_TOKEN_SHARD_CHUNK: contexts per chunk, 0: from the scratch budget
+    DevBuf tab;                              // tq::View[S]
+    DevBuf q_pat, q_off;                     // staging of the host forms
+    DevBuf r_per, r_tot;                     // ranges: per shard (also when the caller wants none), totals
+    DevBuf s_spans, s_len, s_tot;            // spans of the host forms
+    DevBuf l_sym, l_cnt, l_heads, l_list;    // the per-shard lists of one chunk; l_list as sa_hip_token_index::s_list
+    DevBuf o_sym, o_cnt, o_heads;            // merged output of one chunk (host form)
+    hipEvent_t r_ev[2] = {}, sp_ev[2] = {};
+    std::vector<hipEvent_t> nx_ev;           // 3 per chunk: before the shards' launches, behind them, behind the merge
+    size_t nx_used = 0;                      // events of the last next-symbol call
+    bool r_pending = false, sp_pending = false, nx_pending = false;
+    u64 q_last = 0;
+    u32 chunk_last = 0;
+    double r_ms = 0.0, sp_ms = 0.0, nx_ms = 0.0, mg_ms = 0.0;
+
+    const tq::View* table() const { return tab.as<tq::View>(); }
+};
+
+namespace {
+
+int shards_launch_ranges(sa_hip_token_shards* g, const int32_t* pat, const u64* off, u64 Q, u64* totals, sa_hip_pair_u32* per) {
+    int rc;
+    if (!per) {
+        if ((rc = g->r_per.ensure((size_t)Q * g->S * sizeof(sa_hip_pair_u32)))) return rc;
+        per = g->r_per.as<sa_hip_pair_u32>();
+    }
+    SA_HIP_CHECK(hipEventRecord(g->r_ev[0], g->stream));
+    if ((rc = tq::launch_shard_ranges(g->table(), g->S, g->stream, pat, off, Q, totals, per))) return rc;
+    SA_HIP_CHECK(hipEventRecord(g->r_ev[1], g->stream));
+    g->r_pending = true;
+    g->q_last = Q;
+    return 0;
+}
+
+int shards_launch_spans(sa_hip_token_shards* g, const int32_t* pat, const u64* off, u64 Q, int mode, u32 max_length, int need_next,
+                        u32* length, u64* totals, sa_hip_token_span* spans) {
+    SA_HIP_CHECK(hipEventRecord(g->sp_ev[0], g->stream));
+    const int rc = tq::launch_shard_spans(g->table(), g->S, g->max_n, g->stream, pat, off, Q, mode, max_length, need_next, length, totals, spans);
+    if (rc) return rc;
+    SA_HIP_CHECK(hipEventRecord(g->sp_ev[1], g->stream));
+    g->sp_pending = true;
+    g->q_last = Q;
+    return 0;
+}
+
+int shards_event(sa_hip_token_shards* g, size_t k) {
+    while (g->nx_ev.size() <= k) {
+        hipEvent_t e = nullptr;
+        SA_HIP_CHECK(hipEventCreate(&e));
+        g->nx_ev.push_back(e);
+    }
+    SA_HIP_CHECK(hipEventRecord(g->nx_ev[k], g->stream));
+    return 0;
+}
+
+// contexts from the host into the staging buffers
+int shards_stage_contexts(sa_hip_token_shards* g, const int32_t* patterns, const uint64_t* offsets, u64 Q) {
+    int rc;
+    const u64 total = offsets[Q];
+    if ((rc = g->q_pat.ensure((size_t)total * 4 + 64)) || (rc = g->q_off.ensure((size_t)(Q + 1) * 8))) return rc;
+    if (total) SA_HIP_CHECK(hipMemcpyAsync(g->q_pat.p, patterns, (size_t)total * 4, hipMemcpyHostToDevice, g->stream));
+    SA_HIP_CHECK(hipMemcpyAsync(g->q_off.p, offsets, (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, g->stream));
+    return 0;
+}
+
+// Next symbols of the device spans [S * Q], chunk by chunk: every shard's launch_next on its slice, then the merge.  Device
+// outputs (to_host false): written in place.  Host outputs: every chunk is merged into o_* and its written entries copied out.
+int shards_next(sa_hip_token_shards* g, const sa_hip_token_span* spans, u64 Q, u32 cap, int32_t* symbols, u64* counts,
+                sa_hip_token_shards_next* heads, bool to_host) {
+    const char* who = "sa_hip_token_shards_next_batch";
+    int rc;
+    const u32 S = g->S;
+    const u64 chunk = tq::shard_chunk(g->chunk_knob, S, cap, Q);
+    const size_t cells = (size_t)chunk * cap;
+    bool lanes = false;
+    for (u32 s = 0; s < S; ++s) lanes = lanes || g->shard[s]->next_knobs.lanes;
+    if ((rc = g->l_sym.ensure(cells * S * 4)) || (rc = g->l_cnt.ensure(cells * S * 4)) ||
+        (rc = g->l_heads.ensure((size_t)chunk * S * sizeof(sa_hip_token_next))) || (lanes && (rc = g->l_list.ensure(64 + (size_t)chunk * 4)))) return rc;
+    std::vector<u32> hs;
+    std::vector<u64> hc;
+    if (to_host) {
+        if ((rc = g->o_sym.ensure(cells * 4)) || (rc = g->o_cnt.ensure(cells * 8)) || (rc = g->o_heads.ensure((size_t)chunk * sizeof(sa_hip_token_shards_next)))) return rc;
+        try { hs.resize(cells); hc.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
+    }
+    u32* n_list = lanes ? g->l_list.as<u32>() : nullptr;
+    size_t ev = 0;
+    for (u64 c0 = 0; c0 < Q; c0 += chunk) {
+        const u64 qc = Q - c0 < chunk ? Q - c0 : chunk;
+        if ((rc = shards_event(g, ev++))) return rc;
+        for (u32 s = 0; s < S; ++s) {
+            const sa_hip_token_index* t = g->shard[s];
+            const tq::NextArgs a{spans + (u64)s * Q + c0, qc, cap, g->l_sym.as<int32_t>() + (u64)s * qc * cap, g->l_cnt.as<u32>() + (u64)s * qc * cap,
+                                 g->l_heads.as<sa_hip_token_next>() + (u64)s * qc};
+            if ((rc = tq::launch_next(t->x, g->stream, t->next_knobs, a, n_list ? n_list + 16 : nullptr, n_list))) return rc;
+        }
+        if ((rc = shards_event(g, ev++))) return rc;
+        tq::MergeArgs m{};
+        m.sym = g->l_sym.as<int32_t>(); m.cnt = g->l_cnt.as<u32>(); m.heads = g->l_heads.as<sa_hip_token_next>();
+        m.spans = spans + c0; m.span_stride = Q;
+        m.Q = qc; m.S = S; m.cap = cap;
+        m.out_sym = to_host ? g->o_sym.as<int32_t>() : symbols + c0 * cap;
+        m.out_cnt = to_host ? g->o_cnt.as<u64>() : counts + c0 * cap;
+        m.out_heads = to_host ? g->o_heads.as<sa_hip_token_shards_next>() : heads + c0;
+        if ((rc = tq::launch_merge(g->stream, m))) return rc;
+        if ((rc = shards_event(g, ev++))) return rc;
+        g->nx_used = ev;
+        g->nx_pending = true;
+        if (to_host) {
+            SA_HIP_CHECK(hipMemcpyAsync(heads + c0, g->o_heads.p, (size_t)qc * sizeof(sa_hip_token_shards_next), hipMemcpyDeviceToHost, g->stream));
+            SA_HIP_CHECK(hipMemcpyAsync(hs.data(), g->o_sym.p, (size_t)qc * cap * 4, hipMemcpyDeviceToHost, g->stream));
+            SA_HIP_CHECK(hipMemcpyAsync(hc.data(), g->o_cnt.p, (size_t)qc * cap * 8, hipMemcpyDeviceToHost, g->stream));
+            SA_HIP_CHECK(hipStreamSynchronize(g->stream));
+            for (u64 i = 0; i < qc; ++i) {
+                const size_t w = heads[c0 + i].written < cap ? heads[c0 + i].written : cap;
+                memcpy(symbols + (c0 + i) * cap, hs.data() + i * cap, w * 4);
+                memcpy(counts + (c0 + i) * cap, hc.data() + i * cap, w * 8);
+            }
+        }
+    }
+    g->q_last = Q;
+    g->chunk_last = (u32)chunk;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sa_hip_token_shards_destroy(sa_hip_token_shards* g) {
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    for (u32 s = 0; s < g->S; ++s) sa_hip_token_index_destroy(g->shard[s]);
+    g->tab.release(); g->q_pat.release(); g->q_off.release(); g->r_per.release(); g->r_tot.release();
+    g->s_spans.release(); g->s_len.release(); g->s_tot.release();
+    g->l_sym.release(); g->l_cnt.release(); g->l_heads.release(); g->l_list.release();
+    g->o_sym.release(); g->o_cnt.release(); g->o_heads.release();
+    for (int j = 0; j < 2; ++j) {
+        if (g->r_ev[j]) (void)hipEventDestroy(g->r_ev[j]);
+        if (g->sp_ev[j]) (void)hipEventDestroy(g->sp_ev[j]);
+    }
+    for (hipEvent_t e : g->nx_ev) (void)hipEventDestroy(e);
+    if (g->stream) (void)hipStreamDestroy(g->stream);
+    delete g;
+}
+
+int sa_hip_token_shards_create(sa_hip_token_shards** out, sa_hip_token_index* const* shards, uint32_t S) {
+    const char* who = "sa_hip_token_shards_create";
+    if (!out) return fail(SA_HIP_EINVAL, who, "out == NULL");
+    *out = nullptr;
+    if (!shards) return fail(SA_HIP_EINVAL, who, "NULL shard list");
+    if (S == 0 || S > tq::SHARDS_MAX) return fail(SA_HIP_EINVAL, who, "a set holds 1 to 64 shards");
+    for (u32 s = 0; s < S; ++s) if (!shards[s]) return fail(SA_HIP_EINVAL, who, "NULL shard");
+    for (u32 s = 1; s < S; ++s)
+        for (u32 r = 0; r < s; ++r) if (shards[s] == shards[r]) return fail(SA_HIP_EINVAL, who, "a shard is listed twice");
+    for (u32 s = 1; s < S; ++s) if (shards[s]->device != shards[0]->device) return fail(SA_HIP_EINVAL, who, "shards on different devices");
+    const int device = shards[0]->device;
+    int rc = set_device(device);
+    if (rc) return rc;
+    sa_hip_token_shards* g = new (std::nothrow) sa_hip_token_shards();
+    if (!g) return fail(SA_HIP_ENOMEM, who, "host allocation");
+    g->device = device;
+    if (const char* e = diag_env("SA_HIP_TOKEN_SHARD_CHUNK")) g->chunk_knob = strtoull(e, nullptr, 10);
+    auto run = [&]() -> int {
+        SA_HIP_CHECK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+        for (int j = 0; j < 2; ++j) {
+            SA_HIP_CHECK(hipEventCreate(&g->r_ev[j]));
+            SA_HIP_CHECK(hipEventCreate(&g->sp_ev[j]));
+        }
+        tq::View v[tq::SHARDS_MAX];
+        for (u32 s = 0; s < S; ++s) {
+            std::lock_guard<std::mutex> lk(shards[s]->mu);
+            SA_HIP_CHECK(hipStreamSynchronize(shards[s]->stream));   // whatever the shard was asked before it joined
+            v[s] = shards[s]->x.view();
+            g->tokens += v[s].n;
+            if (v[s].n > g->max_n) g->max_n = v[s].n;
+        }
+        int r2 = g->tab.ensure(sizeof(tq::View) * tq::SHARDS_MAX);
+        if (r2) return r2;
+        SA_HIP_CHECK(hipMemcpyAsync(g->tab.p, v, sizeof(tq::View) * S, hipMemcpyHostToDevice, g->stream));
+        SA_HIP_CHECK(hipStreamSynchronize(g->stream));
+        return 0;
+    };
+    rc = run();
+    if (rc) { sa_hip_token_shards_destroy(g); return rc; }   // g->S is still 0: no shard is adopted
+    g->S = S;
+    for (u32 s = 0; s < S; ++s) g->shard[s] = shards[s];
+    *out = g;
+    return 0;
+}
+
+sa_hip_token_index* sa_hip_token_shards_shard(sa_hip_token_shards* g, uint32_t s) {
+    return g && s < g->S ? g->shard[s] : nullptr;
+}
+
+int sa_hip_token_shards_sync(sa_hip_token_shards* g) {
+    if (!g) return fail(SA_HIP_EINVAL, "sa_hip_token_shards_sync", "NULL handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    int rc = set_device(g->device);
+    if (rc) return rc;
+    SA_HIP_CHECK(hipStreamSynchronize(g->stream));
+    return 0;
+}
+
+int sa_hip_token_shards_info(const sa_hip_token_shards* cg, sa_hip_token_shards_stats* out) {
+    if (!cg || !out) return fail(SA_HIP_EINVAL, "sa_hip_token_shards_info", "NULL argument");
+    sa_hip_token_shards* g = const_cast<sa_hip_token_shards*>(cg);
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (g->r_pending || g->sp_pending || g->nx_pending) {
+        int rc = set_device(g->device);
+        if (rc) return rc;
+        float ms = 0.f;
+        if (g->r_pending) {
+            SA_HIP_CHECK(hipEventSynchronize(g->r_ev[1]));
+            SA_HIP_CHECK(hipEventElapsedTime(&ms, g->r_ev[0], g->r_ev[1]));
+            g->r_ms = ms;
+            g->r_pending = false;
+        }
+        if (g->sp_pending) {
+            SA_HIP_CHECK(hipEventSynchronize(g->sp_ev[1]));
+            SA_HIP_CHECK(hipEventElapsedTime(&ms, g->sp_ev[0], g->sp_ev[1]));
+            g->sp_ms = ms;
+            g->sp_pending = false;
+        }
+        if (g->nx_pending) {
+            SA_HIP_CHECK(hipEventSynchronize(g->nx_ev[g->nx_used - 1]));
+            g->nx_ms = g->mg_ms = 0.0;
+            for (size_t k = 0; k + 3 <= g->nx_used; k += 3) {
+                SA_HIP_CHECK(hipEventElapsedTime(&ms, g->nx_ev[k], g->nx_ev[k + 1]));
+                g->nx_ms += ms;
+                SA_HIP_CHECK(hipEventElapsedTime(&ms, g->nx_ev[k + 1], g->nx_ev[k + 2]));
+                g->mg_ms += ms;
+            }
+            g->nx_pending = false;
+        }
+    }
+    memset(out, 0, sizeof *out);
+    out->shards = g->S;
+    out->chunk = g->chunk_last;
+    out->tokens = g->tokens;
+    out->q = g->q_last;
+    out->ranges_ms = g->r_ms;
+    out->spans_ms = g->sp_ms;
+    out->next_ms = g->nx_ms;
+    out->merge_ms = g->mg_ms;
+    return 0;
+}
+
+// ---- ranges.  Argument checks come first and touch neither the handle nor the device. --------------------------------------
+
+int sa_hip_token_shards_query_batch_device(sa_hip_token_shards* g, const void* patterns_dev, const void* offsets_dev, uint64_t Q,
+                                           void* totals_dev, void* per_shard_dev) {
+    const char* who = "sa_hip_token_shards_query_batch_device";
+    if (!g) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    if (Q == 0) return 0;
+    if (!offsets_dev || !totals_dev) return fail(SA_HIP_EINVAL, who, "NULL argument");   // (patterns may be NULL: a batch of empty patterns)
+    std::lock_guard<std::mutex> lk(g->mu);
+    int rc = set_device(g->device);
+    if (rc) return rc;
+    return shards_launch_ranges(g, static_cast<const int32_t*>(patterns_dev), static_cast<const u64*>(offsets_dev), Q, static_cast<u64*>(totals_dev),
+                                static_cast<sa_hip_pair_u32*>(per_shard_dev));
+}
+
+int sa_hip_token_shards_query_batch(sa_hip_token_shards* g, const int32_t* patterns, const uint64_t* offsets, uint64_t Q, uint64_t* totals,
+                                    sa_hip_pair_u32* per_shard) {
+    const char* who = "sa_hip_token_shards_query_batch";
+    if (!g) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    if (Q == 0) return 0;
+    if (!offsets || !totals) return fail(SA_HIP_EINVAL, who, "NULL argument");
+    int rc = token_offsets_args(who, patterns, offsets, Q);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g->mu);
+    if ((rc = set_device(g->device))) return rc;
+    const size_t per_bytes = (size_t)Q * g->S * sizeof(sa_hip_pair_u32);
+    if ((rc = shards_stage_contexts(g, patterns, offsets, Q)) || (rc = g->r_per.ensure(per_bytes)) || (rc = g->r_tot.ensure((size_t)Q * 8))) return rc;
+    if ((rc = shards_launch_ranges(g, g->q_pat.as<int32_t>(), g->q_off.as<u64>(), Q, g->r_tot.as<u64>(), g->r_per.as<sa_hip_pair_u32>()))) return rc;
+    SA_HIP_CHECK(hipMemcpyAsync(totals, g->r_tot.p, (size_t)Q * 8, hipMemcpyDeviceToHost, g->stream));
+    if (per_shard) SA_HIP_CHECK(hipMemcpyAsync(per_shard, g->r_per.p, per_bytes, hipMemcpyDeviceToHost, g->stream));
+    SA_HIP_CHECK(hipStreamSynchronize(g->stream));
+    return 0;
+}
+
+// ---- spans ----------------------------------------------------------------------------------------------------------------
+
+int sa_hip_token_shards_spans_batch_device(sa_hip_token_shards* g, const void* patterns_dev, const void* offsets_dev, uint64_t Q, int mode,
+                                           uint32_t max_length, int need_next, void* length_dev, void* totals_dev, void* spans_dev) {
+    const char* who = "sa_hip_token_shards_spans_batch_device";
+    if (!g) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    int rc = token_span_args(who, mode, need_next);
+    if (rc || Q == 0) return rc;
+    if (!offsets_dev || !length_dev || !totals_dev || !spans_dev) return fail(SA_HIP_EINVAL, who, "NULL argument");   // (patterns may be NULL)
+    std::lock_guard<std::mutex> lk(g->mu);
+    if ((rc = set_device(g->device))) return rc;
+    return shards_launch_spans(g, static_cast<const int32_t*>(patterns_dev), static_cast<const u64*>(offsets_dev), Q, mode, max_length, need_next,
+                               static_cast<u32*>(length_dev), static_cast<u64*>(totals_dev), static_cast<sa_hip_token_span*>(spans_dev));
+}
+
+int sa_hip_token_shards_spans_batch(sa_hip_token_shards* g, const int32_t* patterns, const uint64_t* offsets, uint64_t Q, int mode,
+                                    uint32_t max_length, int need_next, uint32_t* length, uint64_t* totals, sa_hip_token_span* spans) {
+    const char* who = "sa_hip_token_shards_spans_batch";
+    if (!g) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    int rc = token_span_args(who, mode, need_next);
+    if (rc || Q == 0) return rc;
+    if (!offsets || !length || !totals || !spans) return fail(SA_HIP_EINVAL, who, "NULL argument");
+    if ((rc = token_offsets_args(who, patterns, offsets, Q))) return rc;
+    std::lock_guard<std::mutex> lk(g->mu);
+    if ((rc = set_device(g->device))) return rc;
+    const size_t span_bytes = (size_t)Q * g->S * sizeof(sa_hip_token_span);
+    if ((rc = shards_stage_contexts(g, patterns, offsets, Q)) || (rc = g->s_spans.ensure(span_bytes)) || (rc = g->s_len.ensure((size_t)Q * 4)) ||
+        (rc = g->s_tot.ensure((size_t)Q * 8))) return rc;
+    if ((rc = shards_launch_spans(g, g->q_pat.as<int32_t>(), g->q_off.as<u64>(), Q, mode, max_length, need_next, g->s_len.as<u32>(), g->s_tot.as<u64>(),
+                                  g->s_spans.as<sa_hip_token_span>()))) return rc;
+    SA_HIP_CHECK(hipMemcpyAsync(length, g->s_len.p, (size_t)Q * 4, hipMemcpyDeviceToHost, g->stream));
+    SA_HIP_CHECK(hipMemcpyAsync(totals, g->s_tot.p, (size_t)Q * 8, hipMemcpyDeviceToHost, g->stream));
+    SA_HIP_CHECK(hipMemcpyAsync(spans, g->s_spans.p, span_bytes, hipMemcpyDeviceToHost, g->stream));
+    SA_HIP_CHECK(hipStreamSynchronize(g->stream));
+    return 0;
+}
+
+// ---- next symbols ---------------------------------------------------------------------------------------------------------
+
+int sa_hip_token_shards_next_batch_device(sa_hip_token_shards* g, const void* spans_dev, uint64_t Q, uint32_t cap, void* symbols_dev,
+                                          void* counts_dev, void* heads_dev) {
+    const char* who = "sa_hip_token_shards_next_batch_device";
+    if (!g) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    int rc = token_next_args(who, Q, cap);
+    if (rc || Q == 0) return rc;
+    if (!spans_dev || !symbols_dev || !counts_dev || !heads_dev) return fail(SA_HIP_EINVAL, who, "NULL argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    if ((rc = set_device(g->device))) return rc;
+    return shards_next(g, static_cast<const sa_hip_token_span*>(spans_dev), Q, cap, static_cast<int32_t*>(symbols_dev), static_cast<u64*>(counts_dev),
+                       static_cast<sa_hip_token_shards_next*>(heads_dev), false);
+}
+
+int sa_hip_token_shards_next_batch(sa_hip_token_shards* g, const int32_t* patterns, const uint64_t* offsets, uint64_t Q, int mode,
+                                   uint32_t max_length, int need_next, uint32_t cap, sa_hip_token_span* spans, int32_t* symbols,
+                                   uint64_t* counts, sa_hip_token_shards_next* heads) {
+    const char* who = "sa_hip_token_shards_next_batch";
+    if (!g) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    int rc = token_span_args(who, mode, need_next);
+    if (rc || (rc = token_next_args(who, Q, cap)) || Q == 0) return rc;
+    if (!offsets || !symbols || !counts || !heads) return fail(SA_HIP_EINVAL, who, "NULL argument");   // (spans may be NULL)
+    if ((rc = token_offsets_args(who, patterns, offsets, Q))) return rc;
+    std::lock_guard<std::mutex> lk(g->mu);
+    if ((rc = set_device(g->device))) return rc;
+    const size_t span_bytes = (size_t)Q * g->S * sizeof(sa_hip_token_span);
+    if ((rc = shards_stage_contexts(g, patterns, offsets, Q)) || (rc = g->s_spans.ensure(span_bytes)) || (rc = g->s_len.ensure((size_t)Q * 4)) ||
+        (rc = g->s_tot.ensure((size_t)Q * 8))) return rc;
+    if ((rc = shards_launch_spans(g, g->q_pat.as<int32_t>(), g->q_off.as<u64>(), Q, mode, max_length, need_next, g->s_len.as<u32>(), g->s_tot.as<u64>(),
+                                  g->s_spans.as<sa_hip_token_span>()))) return rc;
+    if (spans) SA_HIP_CHECK(hipMemcpyAsync(spans, g->s_spans.p, span_bytes, hipMemcpyDeviceToHost, g->stream));
+    return shards_next(g, g->s_spans.as<sa_hip_token_span>(), Q, cap, symbols, counts, heads, true);
+}
+
+int sa_hip_token_shards_merge_device(sa_hip_token_shards* g, const void* symbols_dev, const void* counts_dev, const void* heads_dev, uint64_t Q,
+                                     uint32_t cap, void* out_symbols_dev, void* out_counts_dev, void* out_heads_dev) {
+    const char* who = "sa_hip_token_shards_merge_device";
+    if (!g) return fail(SA_HIP_EINVAL, who, "NULL handle");
+    int rc = token_next_args(who, Q, cap);
+    if (rc || Q == 0) return rc;
+    if (!symbols_dev || !counts_dev || !heads_dev || !out_symbols_dev || !out_counts_dev || !out_heads_dev) return fail(SA_HIP_EINVAL, who, "NULL argument");
+    std::lock_guard<std::mutex> lk(g->mu);
+    if ((rc = set_device(g->device))) return rc;
+    tq::MergeArgs m{};
+    m.sym = static_cast<const int32_t*>(symbols_dev); m.cnt = static_cast<const u32*>(counts_dev);
+    m.heads = static_cast<const sa_hip_token_next*>(heads_dev);
+    m.spans = nullptr; m.span_stride = 0;
+    m.Q = Q; m.S = g->S; m.cap = cap;
+    m.out_sym = static_cast<int32_t*>(out_symbols_dev); m.out_cnt = static_cast<u64*>(out_counts_dev);
+    m.out_heads = static_cast<sa_hip_token_shards_next*>(out_heads_dev);
+    return tq::launch_merge(g->stream, m);
+}
+
+}  // extern "C"
