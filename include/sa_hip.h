@@ -765,6 +765,79 @@ int sa_hip_token_shards_next_batch_device(sa_hip_token_shards* set, const void* 
 int sa_hip_token_shards_merge_device(sa_hip_token_shards* set, const void* symbols_dev, const void* counts_dev, const void* heads_dev,
                                      uint64_t Q, uint32_t cap, void* out_symbols_dev, void* out_counts_dev, void* out_heads_dev);
 
+/* (6d) documents (csrc/token_docs.hpp, csrc/capi_token_docs.hpp): which documents hold an n-gram, where in them, and in how many
+ * documents it occurs (its document frequency).  All results are exact.
+ *
+ * A handle gets its documents from a table doc_starts[0 .. D) of text positions: document d is T[starts[d] .. starts[d + 1]) with
+ * starts[D] = n implied.  Required: D >= 1, starts[0] == 0, non-decreasing, every entry <= n (with n == 0 every entry is 0).  Equal
+ * neighbours are empty documents, and those are allowed; doc(p) is the LARGEST d with starts[d] <= p, so an empty document never
+ * owns a token.  An occurrence belongs to the document of its FIRST token.  Occurrences that run over a boundary are not filtered:
+ * callers separate documents with a token of their own, as the shard sets of (6c) already assume.  A second call replaces the
+ * first; D == 0 with a NULL pointer removes the documents.  The handle grows by 8 bytes per token plus 4 (D + 1): a document array
+ * DA[r] = doc(SA[r]) and a previous-rank array PV[r] = the largest r' < r with DA[r'] == DA[r] (-1: none), both int32[n].  Within a
+ * rank range [a, b), rank r is the first occurrence of its document iff PV[r] < a, which is what the counts below stream.
+ *
+ *   locate  the occurrences SA[first .. first + min(count, cap)) of a span as (document, offset inside it), in suffix order, to
+ *           docs[i * cap ..] and offsets[i * cap ..]; the head is {written = min(count, cap), count}.
+ *   docs    examined = budget ? min(count, budget) : count ranks of the span are walked from `first`; distinct = the number of
+ *           distinct documents among them; the first min(distinct, cap) of them are written in order of first appearance by rank,
+ *           docs[i * cap + j] the document and offsets[i * cap + j] the offset inside it of its smallest-rank occurrence.  The
+ *           head is {written, examined, distinct, count}: distinct is the n-gram's exact document frequency iff examined == count.
+ *           cap == 0 means counts only; docs and offsets may then be NULL and are never touched.
+ * Slots beyond `written` are not written.
+ *
+ * Errors returned as -1 before any HIP call: a NULL handle or a NULL required pointer, a bad table (set_documents), a handle
+ * without documents, mode or need_next other than 0 / 1, cap == 0 in locate, Q * cap >= 2^31 and descending offsets; Q == 0 is a
+ * no-op returning 0.  The device forms take sa_hip_token_span[Q] exactly as sa_hip_token_index_spans_batch_device writes them, chain
+ * with it without a host trip and are asynchronous until sa_hip_token_index_sync; they trust nothing: first and count are clamped
+ * to the array, and an array that is not the suffix array gives unspecified entries from bounded loops.  The host forms run the
+ * span step first (locate always in mode 0) and stage through buffers of the handle. */
+typedef struct sa_hip_token_locate {
+    uint32_t written;    /* entries written for this span: min(count, cap)                      */
+    uint32_t count;      /* suffixes of the span                                                */
+} sa_hip_token_locate;
+
+typedef struct sa_hip_token_docs {
+    uint32_t written;    /* entries written for this span: min(distinct, cap)                   */
+    uint32_t examined;   /* ranks walked: budget ? min(count, budget) : count                   */
+    uint32_t distinct;   /* distinct documents among the examined ranks                         */
+    uint32_t count;      /* suffixes of the span                                                */
+} sa_hip_token_docs;
+
+typedef struct sa_hip_token_docs_info {
+    uint64_t documents;     /* D; 0: the handle has no documents                                            */
+    uint64_t bytes;         /* of starts, DA and PV: 8 n + 4 (D + 1)                                        */
+    double   prepare_ms;    /* device time of the last set_documents: the three steps below                 */
+    double   da_ms;         /* ... its document-array pass                                                  */
+    double   sort_ms;       /* ... its sort of the ranks by document                                        */
+    double   pv_ms;         /* ... its previous-rank pass                                                   */
+    uint32_t sort_passes;   /* radix passes of that sort (0: one document)                                  */
+    uint32_t reserved;      /* 0                                                                            */
+    uint64_t locate_q;      /* spans of the last locate launch                                              */
+    double   locate_ms;     /* HIP-event time of it (the call waits for it)                                 */
+    uint64_t docs_q;        /* spans of the last documents launch                                           */
+    double   docs_ms;       /* HIP-event time of it                                                         */
+    uint64_t examined;      /* sum of its heads' examined: the ranks that launch streamed                   */
+} sa_hip_token_docs_info;
+
+int sa_hip_token_index_set_documents(sa_hip_token_index* t, const int32_t* doc_starts_host, uint32_t D);
+/* Copy DA and PV of the ranks [first, first + count) to the host; either output may be NULL.  first + count > n and a handle
+ * without documents return -1. */
+int sa_hip_token_index_get_doc_range(sa_hip_token_index* t, uint64_t first, uint64_t count, int32_t* docs_out, int32_t* prev_out);
+int sa_hip_token_index_docs_info(const sa_hip_token_index* t, sa_hip_token_docs_info* out);
+/* spans_dev: sa_hip_token_span[Q]; docs_dev, offsets_dev: int32[Q * cap]; heads_dev: sa_hip_token_locate[Q]. */
+int sa_hip_token_index_locate_batch_device(sa_hip_token_index* t, const void* spans_dev, uint64_t Q, uint32_t cap, void* docs_dev,
+                                           void* offsets_dev, void* heads_dev);
+/* Both steps from host patterns: spans (may be NULL), docs, offs and heads out. */
+int sa_hip_token_index_locate_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q, uint32_t cap,
+                                    sa_hip_token_span* spans, int32_t* docs, int32_t* offs, sa_hip_token_locate* heads);
+/* heads_dev: sa_hip_token_docs[Q]; docs_dev and offsets_dev may be NULL when cap == 0. */
+int sa_hip_token_index_docs_batch_device(sa_hip_token_index* t, const void* spans_dev, uint64_t Q, uint32_t cap, uint32_t budget,
+                                         void* docs_dev, void* offsets_dev, void* heads_dev);
+int sa_hip_token_index_docs_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q, int mode,
+                                  uint32_t max_length, int need_next, uint32_t cap, uint32_t budget, sa_hip_token_span* spans,
+                                  int32_t* docs, int32_t* offs, sa_hip_token_docs* heads);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 
 /* Per-build statistics of the last build on this handle (roofline accounting). */

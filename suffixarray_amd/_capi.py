@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("SA_HIP_LIB", os.path.join(_HERE, "libsa_hip.so"))   #
 PAIR_DTYPE = np.dtype([("first", "<u4"), ("second", "<u4")])
 SPAN_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("length", "<u4"), ("ended", "<u4")])            # sa_hip_token_span
 NEXT_DTYPE = np.dtype([("written", "<u4"), ("covered", "<u4"), ("total", "<u4"), ("reserved", "<u4")])      # sa_hip_token_next
+LOCATE_DTYPE = np.dtype([("written", "<u4"), ("count", "<u4")])                                            # sa_hip_token_locate
+DOCS_DTYPE = np.dtype([("written", "<u4"), ("examined", "<u4"), ("distinct", "<u4"), ("count", "<u4")])     # sa_hip_token_docs
 SHARDS_NEXT_DTYPE = np.dtype([("written", "<u4"), ("length", "<u4"), ("covered", "<u8"), ("total", "<u8")])  # sa_hip_token_shards_next
 SHARDS_MAX = 64
 UINT32_MAX = 0xFFFFFFFF
@@ -39,6 +41,9 @@ EXPORTS = [
     "sa_hip_token_index_get_sa_range", "sa_hip_token_index_info",
     "sa_hip_token_index_spans_batch", "sa_hip_token_index_spans_batch_device", "sa_hip_token_index_next_batch_device",
     "sa_hip_token_index_next_batch", "sa_hip_token_index_next_of_spans", "sa_hip_token_index_next_info",
+    "sa_hip_token_index_set_documents", "sa_hip_token_index_get_doc_range", "sa_hip_token_index_docs_info",
+    "sa_hip_token_index_locate_batch_device", "sa_hip_token_index_locate_batch", "sa_hip_token_index_docs_batch_device",
+    "sa_hip_token_index_docs_batch",
     "sa_hip_token_shards_create", "sa_hip_token_shards_destroy", "sa_hip_token_shards_shard", "sa_hip_token_shards_sync",
     "sa_hip_token_shards_info", "sa_hip_token_shards_query_batch", "sa_hip_token_shards_query_batch_device",
     "sa_hip_token_shards_spans_batch", "sa_hip_token_shards_spans_batch_device", "sa_hip_token_shards_next_batch",
@@ -176,6 +181,25 @@ class TokenNextInfo(C.Structure):
     """sa_hip_token_next_info: the last span and next-symbol launches of a token index."""
     _fields_ = [("q", C.c_uint64), ("spans_ms", C.c_double), ("next_ms", C.c_double), ("lane_spans", C.c_uint64),
                 ("wave_spans", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenLocate(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("count", C.c_uint32)]
+
+
+class TokenDocs(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("examined", C.c_uint32), ("distinct", C.c_uint32), ("count", C.c_uint32)]
+
+
+class TokenDocsInfo(C.Structure):
+    """sa_hip_token_docs_info: the documents of a token index and its last locate and documents launches."""
+    _fields_ = [("documents", C.c_uint64), ("bytes", C.c_uint64), ("prepare_ms", C.c_double), ("da_ms", C.c_double),
+                ("sort_ms", C.c_double), ("pv_ms", C.c_double), ("sort_passes", C.c_uint32), ("reserved", C.c_uint32),
+                ("locate_q", C.c_uint64), ("locate_ms", C.c_double), ("docs_q", C.c_uint64), ("docs_ms", C.c_double),
+                ("examined", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -465,6 +489,20 @@ def lib():
     L.sa_hip_token_index_next_of_spans.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, vp]
     L.sa_hip_token_index_next_info.restype = C.c_int
     L.sa_hip_token_index_next_info.argtypes = [vp, C.POINTER(TokenNextInfo)]
+    L.sa_hip_token_index_set_documents.restype = C.c_int
+    L.sa_hip_token_index_set_documents.argtypes = [vp, vp, C.c_uint32]
+    L.sa_hip_token_index_get_doc_range.restype = C.c_int
+    L.sa_hip_token_index_get_doc_range.argtypes = [vp, u64, u64, vp, vp]
+    L.sa_hip_token_index_docs_info.restype = C.c_int
+    L.sa_hip_token_index_docs_info.argtypes = [vp, C.POINTER(TokenDocsInfo)]
+    L.sa_hip_token_index_locate_batch_device.restype = C.c_int
+    L.sa_hip_token_index_locate_batch_device.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_index_locate_batch.restype = C.c_int
+    L.sa_hip_token_index_locate_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_index_docs_batch_device.restype = C.c_int
+    L.sa_hip_token_index_docs_batch_device.argtypes = [vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_index_docs_batch.restype = C.c_int
+    L.sa_hip_token_index_docs_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.sa_hip_token_shards_create.restype = C.c_int
     L.sa_hip_token_shards_create.argtypes = [C.POINTER(vp), vp, C.c_uint32]
     L.sa_hip_token_shards_destroy.restype = None
@@ -1253,6 +1291,69 @@ class TokenIndex:
         st = TokenNextInfo()
         check(self._lib.sa_hip_token_index_next_info(self._h, C.byref(st)))
         return st.as_dict()
+
+    def set_documents(self, starts):
+        """starts: the first text position of every document (starts[0] == 0, non-decreasing, <= n); None removes the documents."""
+        if starts is None:
+            check(self._lib.sa_hip_token_index_set_documents(self._h, None, 0))
+            return
+        s = np.ascontiguousarray(starts)
+        if s.ndim != 1 or s.size == 0 or s.size > 0xFFFFFFFF or (s.dtype.kind not in "iu") or int(s.min()) < 0 or int(s.max()) > 2 ** 31 - 1:
+            raise ValueError("doc_starts: a non-empty 1-d sequence of text positions")
+        s = s.astype(np.int32)
+        check(self._lib.sa_hip_token_index_set_documents(self._h, s.ctypes.data, s.size))
+
+    def doc_range(self, first, count):
+        """-> (DA, PV) of the ranks [first, first + count): the document of every rank, and the previous rank of the same document"""
+        da, pv = np.empty(max(count, 1), dtype=np.int32), np.empty(max(count, 1), dtype=np.int32)
+        check(self._lib.sa_hip_token_index_get_doc_range(self._h, int(first), int(count), da.ctypes.data, pv.ctypes.data))
+        return da[:count], pv[:count]
+
+    def docs_info(self):
+        st = TokenDocsInfo()
+        check(self._lib.sa_hip_token_index_docs_info(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def locate_batch_device(self, spans_dev_ptr, q, cap, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr):
+        """(document, offset) of the first cap occurrences of q device spans; asynchronous on the handle's stream until sync()."""
+        check(self._lib.sa_hip_token_index_locate_batch_device(self._h, spans_dev_ptr, q, int(cap), docs_dev_ptr, offsets_dev_ptr,
+                                                               heads_dev_ptr))
+
+    def locate_batch(self, patterns, cap=16, fill=0):
+        """The exact span of every pattern, then its first cap occurrences.  -> dict: spans [Q], docs int32[Q, cap], offsets
+        int32[Q, cap], heads (written, count)[Q].  Cells beyond heads['written'] keep `fill`."""
+        buf, off = self._packed(patterns)
+        q = off.size - 1
+        spans = np.zeros(max(q, 1), dtype=SPAN_DTYPE)
+        docs, offs = np.full((max(q, 1), int(cap)), fill, dtype=np.int32), np.full((max(q, 1), int(cap)), fill, dtype=np.int32)
+        heads = np.zeros(max(q, 1), dtype=LOCATE_DTYPE)
+        if q > 0:
+            check(self._lib.sa_hip_token_index_locate_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(cap),
+                                                            spans.ctypes.data, docs.ctypes.data, offs.ctypes.data, heads.ctypes.data))
+        q = max(q, 0)
+        return {"spans": spans[:q], "docs": docs[:q], "offsets": offs[:q], "heads": heads[:q]}
+
+    def docs_batch_device(self, spans_dev_ptr, q, cap, budget, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr):
+        """Distinct documents of q device spans (cap 0: counts only, docs and offsets may be None); asynchronous until sync()."""
+        check(self._lib.sa_hip_token_index_docs_batch_device(self._h, spans_dev_ptr, q, int(cap), int(budget), docs_dev_ptr, offsets_dev_ptr,
+                                                             heads_dev_ptr))
+
+    def docs_batch(self, patterns, cap=16, budget=0, mode=0, max_length=0, need_next=False, fill=0):
+        """Spans as in spans_batch, then their distinct documents among the first `budget` ranks (0: all).  -> dict: spans [Q], docs
+        int32[Q, cap], offsets int32[Q, cap], heads (written, examined, distinct, count)[Q].  Cells beyond heads['written'] keep `fill`."""
+        buf, off = self._packed(patterns)
+        q = off.size - 1
+        cap = int(cap)
+        spans = np.zeros(max(q, 1), dtype=SPAN_DTYPE)
+        docs, offs = np.full((max(q, 1), cap), fill, dtype=np.int32), np.full((max(q, 1), cap), fill, dtype=np.int32)
+        heads = np.zeros(max(q, 1), dtype=DOCS_DTYPE)
+        if q > 0:
+            check(self._lib.sa_hip_token_index_docs_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
+                                                          int(max_length), int(bool(need_next)), cap, int(budget), spans.ctypes.data,
+                                                          docs.ctypes.data if cap else None, offs.ctypes.data if cap else None,
+                                                          heads.ctypes.data))
+        q = max(q, 0)
+        return {"spans": spans[:q], "docs": docs[:q], "offsets": offs[:q], "heads": heads[:q]}
 
 
 class _BorrowedTokenIndex(TokenIndex):

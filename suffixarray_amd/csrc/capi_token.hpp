@@ -1,9 +1,11 @@
 // capi_token.hpp -- the C ABI of the token index (include/sa_hip.h section 6), included by sa_capi.hip (same translation unit).
-// The kernels and the search structures are csrc/token_query.hpp, spans and next symbols csrc/token_next.hpp; the suffix array of sa_hip_token_index_build comes from
+// The kernels and the search structures are csrc/token_query.hpp, spans and next symbols csrc/token_next.hpp, documents csrc/token_docs.hpp (their entry points:
+// capi_token_docs.hpp); the suffix array of sa_hip_token_index_build comes from
 // the build behind sa_hip_libsais_int_device (capi_dropins.hpp: int_device).
 #pragma once
 #include "token_query.hpp"
 #include "token_next.hpp"
+#include "token_docs.hpp"
 #include <vector>
 
 struct sa_hip_token_index {
@@ -27,6 +29,14 @@ struct sa_hip_token_index {
     bool nx_lanes = false;                   // ... and whether it went through the lane form
     double sp_ms = 0.0, nx_ms = 0.0;
     u64 nx_lane_spans = 0, nx_wave_spans = 0;
+    // documents (token_docs.hpp, capi_token_docs.hpp)
+    tq::Docs docs;
+    DevBuf d_docs, d_offs, d_heads;          // staging of the host forms
+    hipEvent_t lc_ev[2] = {}, dc_ev[2] = {};
+    bool lc_pending = false, dc_pending = false;
+    u64 lc_q = 0, dc_q = 0;                  // spans of the last locate / documents launch
+    double lc_ms = 0.0, dc_ms = 0.0;
+    u64 dc_examined = 0;
 };
 
 namespace {
@@ -47,6 +57,8 @@ int token_create(sa_hip_token_index** out, int device, const char* who) {
         if (e == hipSuccess) e = hipEventCreate(&t->q_ev[j]);
         if (e == hipSuccess) e = hipEventCreate(&t->sp_ev[j]);
         if (e == hipSuccess) e = hipEventCreate(&t->nx_ev[j]);
+        if (e == hipSuccess) e = hipEventCreate(&t->lc_ev[j]);
+        if (e == hipSuccess) e = hipEventCreate(&t->dc_ev[j]);
     }
     if (e != hipSuccess) {
         sa_hip_token_index_destroy(t);
@@ -152,10 +164,14 @@ void sa_hip_token_index_destroy(sa_hip_token_index* t) {
     t->x.release();
     t->q_pat.release(); t->q_off.release(); t->q_out.release();
     t->s_spans.release(); t->s_sym.release(); t->s_cnt.release(); t->s_heads.release(); t->s_list.release();
+    t->docs.release();
+    t->d_docs.release(); t->d_offs.release(); t->d_heads.release();
     for (int j = 0; j < 2; ++j) {
         if (t->q_ev[j]) (void)hipEventDestroy(t->q_ev[j]);
         if (t->sp_ev[j]) (void)hipEventDestroy(t->sp_ev[j]);
         if (t->nx_ev[j]) (void)hipEventDestroy(t->nx_ev[j]);
+        if (t->lc_ev[j]) (void)hipEventDestroy(t->lc_ev[j]);
+        if (t->dc_ev[j]) (void)hipEventDestroy(t->dc_ev[j]);
     }
     if (t->stream) (void)hipStreamDestroy(t->stream);
     delete t;

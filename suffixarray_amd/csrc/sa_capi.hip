@@ -4,8 +4,8 @@
 //
 // This file: the index handle with its build, query, record-retrieval, replica, multi-GPU, CSV and on-disk entry points.
 // capi_dropins.hpp (included below, same translation unit): the libsais- / engine-call-compatible entry points, their device
-// forms and the process-level workspace they share.  capi_token.hpp and capi_token_shards.hpp (included at the end): the token index
-// and sets of them.
+// forms and the process-level workspace they share.  capi_token.hpp, capi_token_docs.hpp and capi_token_shards.hpp (included at the end): the token
+// index, its documents, and sets of token indexes.
 #include <exception>
 #include <mutex>
 #include <new>
@@ -1636,4 +1636,5 @@ int sa_hip_read_suffix_array(sa_hip_SuffixArray_struct* s, const char* sa_filena
 
 // The token index (batched n-gram ranges over an int32 text): a handle and kernels of its own
 #include "capi_token.hpp"
+#include "capi_token_docs.hpp"
 #include "capi_token_shards.hpp"

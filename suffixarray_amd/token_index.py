@@ -5,6 +5,10 @@
     ti.positions([464, 2068], limit=10)    # where: text positions in suffix order
     ti.next_token_counts([464, 2068])      # {token: count} of what follows the n-gram
     ti.next_tokens(contexts, cap=64, longest_suffix=True)   # the same per context, backing off to its longest suffix that occurs
+    ti = TokenIndex(tokens, doc_starts=starts)              # ... with documents: document d is tokens[starts[d] : starts[d + 1]]
+    ti.locate([464, 2068], limit=10)       # where, as (document, offset inside it)
+    ti.document_counts([[464, 2068], [11]])   # in how many documents every n-gram occurs
+    ti.documents(ngrams, cap=16)           # which documents, in order of first appearance by rank
 
 On top of the handle API of include/sa_hip.h section 6 (suffixarray_amd._capi.TokenIndex).  No CPU fallback.
 """
@@ -14,10 +18,48 @@ from . import _capi
 
 
 class TokenIndex:
-    def __init__(self, tokens, k=None, device=0):
-        """tokens: int sequence or array with symbols in [0, k) (k defaults to max + 1), at most 2^31 - 1 of them."""
+    def __init__(self, tokens, k=None, device=0, doc_starts=None):
+        """tokens: int sequence or array with symbols in [0, k) (k defaults to max + 1), at most 2^31 - 1 of them.
+        doc_starts: see set_documents."""
         self._idx = _capi.TokenIndex.build(tokens, k, device)
         self.n = int(self._idx.info()["n"])
+        if doc_starts is not None:
+            try:
+                self.set_documents(doc_starts)
+            except Exception:
+                self.close()
+                raise
+
+    def set_documents(self, starts):
+        """Document d is tokens[starts[d] : starts[d + 1]] (the last one runs to the end): starts[0] == 0, non-decreasing, <= n.
+        Equal neighbours are empty documents.  An occurrence belongs to the document of its first token; separate documents with
+        a token of their own to keep n-grams from running over a boundary.  A second call replaces the table, None removes it."""
+        self._idx.set_documents(starts)
+
+    def locate(self, ngram, limit):
+        """-> (doc, offset), int32 arrays: the first `limit` occurrences of one n-gram in suffix order, each as its document and
+        the offset inside it: tokens[starts[doc] + offset :] starts with the n-gram."""
+        r = self._idx.locate_batch([list(ngram)], cap=max(int(limit), 1))
+        w = min(int(r["heads"]["written"][0]), int(limit))
+        return r["docs"][0, :w].copy(), r["offsets"][0, :w].copy()
+
+    def documents(self, ngrams, cap=16, budget=None, longest_suffix=False, max_length=None):
+        """Which documents hold every n-gram.  -> dict of arrays: docs int32[Q, cap] and offsets int32[Q, cap], of which the first
+        written[i] are valid in row i: the distinct documents in order of first appearance by rank, each with the offset of its
+        smallest-rank occurrence; distinct[i] = distinct documents among the examined[i] = min(count[i], budget) first ranks;
+        exact[i] = every occurrence was examined, so distinct[i] is the document frequency.  longest_suffix: as in next_tokens,
+        without the demand for a next token."""
+        r = self._idx.docs_batch(ngrams, cap=cap, budget=budget or 0, mode=1 if longest_suffix else 0, max_length=max_length or 0,
+                                 need_next=False)
+        h = r["heads"]
+        return {"docs": r["docs"], "offsets": r["offsets"], "written": h["written"].copy(), "distinct": h["distinct"].copy(),
+                "examined": h["examined"].copy(), "count": h["count"].copy(), "exact": h["examined"] == h["count"]}
+
+    def document_counts(self, ngrams, budget=None):
+        """-> (distinct uint32[Q], exact bool[Q]): in how many documents every n-gram occurs (counted over its first `budget`
+        occurrences in suffix order when given; exact says that these were all)"""
+        h = self._idx.docs_batch(ngrams, cap=0, budget=budget or 0)["heads"]
+        return h["distinct"].copy(), h["examined"] == h["count"]
 
     def ranges(self, ngrams):
         """-> (first, count), uint32[Q] each: n-gram i occurs at the text positions SA[first[i] .. first[i] + count[i]);
