@@ -838,6 +838,88 @@ int sa_hip_token_index_docs_batch(sa_hip_token_index* t, const int32_t* patterns
                                   uint32_t max_length, int need_next, uint32_t cap, uint32_t budget, sa_hip_token_span* spans,
                                   int32_t* docs, int32_t* offs, sa_hip_token_docs* heads);
 
+/* (6e) per-document counts and documents holding all n-grams of a group (csrc/token_all.hpp, csrc/capi_token_all.hpp): how often
+ * an n-gram occurs in a given document (its term frequency), and which documents hold every n-gram of a group (an AND query).  All
+ * results are exact.
+ *
+ * Both rest on one more array beside DA and PV of (6d), opt-in, 4 bytes per token: the rank-by-document array RK, int32[n], in which
+ * RK[starts[d] .. starts[d + 1]) holds the ranks { r : DA[r] == d } in ascending order (document d owns starts[d + 1] - starts[d]
+ * text positions and every position is one suffix, so the closed starts table bounds the segments; an empty document has an empty
+ * segment).  sa_hip_token_index_prepare_doc_ranks(t, 1) builds it from the DA the handle holds (a no-op when it is there),
+ * (t, 0) frees it; replacing or removing the documents drops it and the caller prepares again.  A handle that never prepares it has
+ * the bytes and the answers of (6d).
+ *
+ *   doc_counts  counts[i * cap + j] = the number of ranks of span i that belong to document docs[i * cap + j], for j below the
+ *               row's length: written[i] (a uint32 per span, written_stride bytes apart: the `written` field of a
+ *               sa_hip_token_docs[Q] or sa_hip_token_all[G] can be passed as it stands with the struct's size as the stride), or
+ *               cap when written is NULL.  Slots at or beyond a row's length are neither read nor written.  A document id outside
+ *               [0, D), a negative one included, gives 0.
+ *   all         spans[S] are cut into G groups by group_offsets[G + 1] (a HOST array in both forms, copied by the call): it starts
+ *               at 0, ends at S, and every group has 1 .. SA_HIP_TOKEN_ALL_MAX spans.  The driver of a group is its span with
+ *               the smallest count, the lowest index on a tie.  examined = budget ? min(count, budget) : count ranks of the driver
+ *               are walked from its `first`; a rank r among them is a candidate iff it is the first of its document there
+ *               (PV[r] < first), and a candidate matches iff its document holds a rank of every other span of the group.  The
+ *               first min(matched, cap) matches are written in the driver's rank order: docs[g * cap + j] the document and
+ *               offsets[g * cap + j] the offset inside it of the driver's smallest-rank occurrence there.  cap == 0 counts only;
+ *               docs and offsets may then be NULL and are never touched.  matched is the exact number of documents that hold all
+ *               n-grams of the group iff examined == count.  A group with an empty span has an empty driver: everything is 0.
+ * Slots beyond `written` are not written.
+ *
+ * Errors returned as -1 before any HIP call: a NULL handle or a NULL required pointer, a handle without documents, a handle
+ * without RK (the message names sa_hip_token_index_prepare_doc_ranks), a bad group table (not starting at 0, not ending at S, an
+ * empty group, a group above the maximum), cap == 0 in doc_counts, a written_stride that is below 4 or no multiple of 4, G * cap,
+ * Q * cap or S >= 2^31, mode or need_next other than 0 / 1, and descending offsets; Q == 0 and G == 0 are no-ops returning 0.  The
+ * device forms take the spans exactly as sa_hip_token_index_spans_batch_device writes them and docs / written exactly as
+ * sa_hip_token_index_docs_batch_device writes them, chain without a host trip and are asynchronous until sa_hip_token_index_sync;
+ * they trust nothing: first and count are clamped to the array, every search is bounded.  The host forms run the span step first
+ * and stage through buffers of the handle. */
+#define SA_HIP_TOKEN_ALL_MAX 16
+
+typedef struct sa_hip_token_all {
+    uint32_t written;      /* entries written for this group: min(matched, cap)                    */
+    uint32_t examined;     /* ranks of the driver walked: budget ? min(count, budget) : count      */
+    uint32_t matched;      /* candidates whose document holds every other span of the group        */
+    uint32_t candidates;   /* distinct documents among the examined ranks of the driver            */
+    uint32_t driver;       /* index inside the group of the span that was walked                   */
+    uint32_t count;        /* suffixes of the driver                                               */
+    uint32_t reserved[2];  /* 0                                                                    */
+} sa_hip_token_all;
+
+typedef struct sa_hip_token_doc_ranks_info {
+    uint32_t present;       /* 1: the handle holds RK                                              */
+    uint32_t sort_passes;   /* radix passes of its sort (0: one document)                          */
+    uint64_t bytes;         /* of RK: 4 n (0 when it is not there)                                 */
+    double   prepare_ms;    /* device time of the last prepare that built it                       */
+    uint64_t counts_q;      /* spans of the last doc_counts launch                                 */
+    double   counts_ms;     /* HIP-event time of it (the call waits for it)                        */
+    uint64_t all_q;         /* groups of the last all launch                                       */
+    double   all_ms;        /* HIP-event time of it                                                */
+} sa_hip_token_doc_ranks_info;
+
+int sa_hip_token_index_prepare_doc_ranks(sa_hip_token_index* t, int on);
+/* Copy RK[first .. first + count) to the host; first + count > n, a handle without documents or without RK return -1. */
+int sa_hip_token_index_get_doc_ranks(sa_hip_token_index* t, uint64_t first, uint64_t count, int32_t* out);
+int sa_hip_token_index_doc_ranks_info(const sa_hip_token_index* t, sa_hip_token_doc_ranks_info* out);
+/* spans_dev: sa_hip_token_span[Q]; docs_dev: int32[Q * cap]; written_dev: NULL or a uint32 per span, written_stride bytes apart;
+ * counts_dev: uint32[Q * cap]. */
+int sa_hip_token_index_doc_counts_batch_device(sa_hip_token_index* t, const void* spans_dev, uint64_t Q, uint32_t cap,
+                                               const void* docs_dev, const void* written_dev, uint64_t written_stride,
+                                               void* counts_dev);
+/* Both steps from host patterns: docs int32[Q * cap] and written uint32[Q] (may be NULL) in, counts uint32[Q * cap] and spans (may
+ * be NULL) out. */
+int sa_hip_token_index_doc_counts_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q, int mode,
+                                        uint32_t max_length, int need_next, uint32_t cap, const int32_t* docs,
+                                        const uint32_t* written, uint32_t* counts, sa_hip_token_span* spans);
+/* spans_dev: sa_hip_token_span[S]; group_offsets_host: uint64[G + 1]; docs_dev, offsets_dev: int32[G * cap] (may be NULL when
+ * cap == 0); heads_dev: sa_hip_token_all[G]. */
+int sa_hip_token_index_all_batch_device(sa_hip_token_index* t, const void* spans_dev, uint64_t S, const uint64_t* group_offsets_host,
+                                        uint64_t G, uint32_t cap, uint32_t budget, void* docs_dev, void* offsets_dev, void* heads_dev);
+/* Both steps from S host patterns: spans[S] (may be NULL), docs, offs and heads[G] out. */
+int sa_hip_token_index_all_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t S,
+                                 const uint64_t* group_offsets, uint64_t G, int mode, uint32_t max_length, int need_next,
+                                 uint32_t cap, uint32_t budget, sa_hip_token_span* spans, int32_t* docs, int32_t* offs,
+                                 sa_hip_token_all* heads);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 
 /* Per-build statistics of the last build on this handle (roofline accounting). */

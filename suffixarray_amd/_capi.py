@@ -17,6 +17,9 @@ SPAN_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("length", "<u4"), ("
 NEXT_DTYPE = np.dtype([("written", "<u4"), ("covered", "<u4"), ("total", "<u4"), ("reserved", "<u4")])      # sa_hip_token_next
 LOCATE_DTYPE = np.dtype([("written", "<u4"), ("count", "<u4")])                                            # sa_hip_token_locate
 DOCS_DTYPE = np.dtype([("written", "<u4"), ("examined", "<u4"), ("distinct", "<u4"), ("count", "<u4")])     # sa_hip_token_docs
+ALL_DTYPE = np.dtype([("written", "<u4"), ("examined", "<u4"), ("matched", "<u4"), ("candidates", "<u4"), ("driver", "<u4"),
+                      ("count", "<u4"), ("reserved", "<u4", (2,))])                                           # sa_hip_token_all
+TOKEN_ALL_MAX = 16                                                                                          # SA_HIP_TOKEN_ALL_MAX
 SHARDS_NEXT_DTYPE = np.dtype([("written", "<u4"), ("length", "<u4"), ("covered", "<u8"), ("total", "<u8")])  # sa_hip_token_shards_next
 SHARDS_MAX = 64
 UINT32_MAX = 0xFFFFFFFF
@@ -44,6 +47,9 @@ EXPORTS = [
     "sa_hip_token_index_set_documents", "sa_hip_token_index_get_doc_range", "sa_hip_token_index_docs_info",
     "sa_hip_token_index_locate_batch_device", "sa_hip_token_index_locate_batch", "sa_hip_token_index_docs_batch_device",
     "sa_hip_token_index_docs_batch",
+    "sa_hip_token_index_prepare_doc_ranks", "sa_hip_token_index_get_doc_ranks", "sa_hip_token_index_doc_ranks_info",
+    "sa_hip_token_index_doc_counts_batch_device", "sa_hip_token_index_doc_counts_batch", "sa_hip_token_index_all_batch_device",
+    "sa_hip_token_index_all_batch",
     "sa_hip_token_shards_create", "sa_hip_token_shards_destroy", "sa_hip_token_shards_shard", "sa_hip_token_shards_sync",
     "sa_hip_token_shards_info", "sa_hip_token_shards_query_batch", "sa_hip_token_shards_query_batch_device",
     "sa_hip_token_shards_spans_batch", "sa_hip_token_shards_spans_batch_device", "sa_hip_token_shards_next_batch",
@@ -200,6 +206,20 @@ class TokenDocsInfo(C.Structure):
                 ("sort_ms", C.c_double), ("pv_ms", C.c_double), ("sort_passes", C.c_uint32), ("reserved", C.c_uint32),
                 ("locate_q", C.c_uint64), ("locate_ms", C.c_double), ("docs_q", C.c_uint64), ("docs_ms", C.c_double),
                 ("examined", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenAll(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("examined", C.c_uint32), ("matched", C.c_uint32), ("candidates", C.c_uint32),
+                ("driver", C.c_uint32), ("count", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class TokenDocRanksInfo(C.Structure):
+    """sa_hip_token_doc_ranks_info: the rank-by-document array of a token index and its last doc_counts and all launches."""
+    _fields_ = [("present", C.c_uint32), ("sort_passes", C.c_uint32), ("bytes", C.c_uint64), ("prepare_ms", C.c_double),
+                ("counts_q", C.c_uint64), ("counts_ms", C.c_double), ("all_q", C.c_uint64), ("all_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -503,6 +523,20 @@ def lib():
     L.sa_hip_token_index_docs_batch_device.argtypes = [vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.sa_hip_token_index_docs_batch.restype = C.c_int
     L.sa_hip_token_index_docs_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_index_prepare_doc_ranks.restype = C.c_int
+    L.sa_hip_token_index_prepare_doc_ranks.argtypes = [vp, C.c_int]
+    L.sa_hip_token_index_get_doc_ranks.restype = C.c_int
+    L.sa_hip_token_index_get_doc_ranks.argtypes = [vp, u64, u64, vp]
+    L.sa_hip_token_index_doc_ranks_info.restype = C.c_int
+    L.sa_hip_token_index_doc_ranks_info.argtypes = [vp, C.POINTER(TokenDocRanksInfo)]
+    L.sa_hip_token_index_doc_counts_batch_device.restype = C.c_int
+    L.sa_hip_token_index_doc_counts_batch_device.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, u64, vp]
+    L.sa_hip_token_index_doc_counts_batch.restype = C.c_int
+    L.sa_hip_token_index_doc_counts_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_index_all_batch_device.restype = C.c_int
+    L.sa_hip_token_index_all_batch_device.argtypes = [vp, vp, u64, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_index_all_batch.restype = C.c_int
+    L.sa_hip_token_index_all_batch.argtypes = [vp, vp, vp, u64, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.sa_hip_token_shards_create.restype = C.c_int
     L.sa_hip_token_shards_create.argtypes = [C.POINTER(vp), vp, C.c_uint32]
     L.sa_hip_token_shards_destroy.restype = None
@@ -1354,6 +1388,78 @@ class TokenIndex:
                                                           heads.ctypes.data))
         q = max(q, 0)
         return {"spans": spans[:q], "docs": docs[:q], "offsets": offs[:q], "heads": heads[:q]}
+
+    def prepare_doc_ranks(self, on=True):
+        """Build (or, with on=False, free) the rank-by-document array the two calls below need; a no-op when it is already there.
+        Replacing or removing the documents drops it."""
+        check(self._lib.sa_hip_token_index_prepare_doc_ranks(self._h, int(bool(on))))
+
+    def doc_ranks(self, first, count):
+        """-> RK[first : first + count): for every document the ranks of its suffixes, ascending, segment d at starts[d]"""
+        out = np.empty(max(count, 1), dtype=np.int32)
+        check(self._lib.sa_hip_token_index_get_doc_ranks(self._h, int(first), int(count), out.ctypes.data))
+        return out[:count]
+
+    def doc_ranks_info(self):
+        st = TokenDocRanksInfo()
+        check(self._lib.sa_hip_token_index_doc_ranks_info(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def doc_counts_batch_device(self, spans_dev_ptr, q, cap, docs_dev_ptr, written_dev_ptr, written_stride, counts_dev_ptr):
+        """counts[i, j] = ranks of device span i inside document docs[i, j], j below the row's length (written_dev_ptr None: cap);
+        asynchronous on the handle's stream until sync()."""
+        check(self._lib.sa_hip_token_index_doc_counts_batch_device(self._h, spans_dev_ptr, q, int(cap), docs_dev_ptr, written_dev_ptr,
+                                                                   int(written_stride), counts_dev_ptr))
+
+    def doc_counts_batch(self, patterns, docs, written=None, mode=0, max_length=0, need_next=False, fill=0):
+        """Spans as in spans_batch, then how often every one occurs in the documents of its row.  docs: int32[Q, cap]; written:
+        uint32[Q] row lengths or None.  -> dict: spans [Q], counts uint32[Q, cap].  Cells beyond a row's length keep `fill`."""
+        buf, off = self._packed(patterns)
+        q = off.size - 1
+        docs = np.ascontiguousarray(docs, dtype=np.int32)
+        if docs.ndim != 2 or docs.shape[0] != max(q, 0):
+            raise ValueError("docs: one row of document ids per pattern")
+        cap = docs.shape[1]
+        if written is not None:
+            written = np.ascontiguousarray(written, dtype=np.uint32)
+            if written.shape != (max(q, 0),):
+                raise ValueError("written: one row length per pattern")
+        spans = np.zeros(max(q, 1), dtype=SPAN_DTYPE)
+        counts = np.full((max(q, 1), cap), fill & 0xFFFFFFFF, dtype=np.uint32)
+        if q > 0:
+            check(self._lib.sa_hip_token_index_doc_counts_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
+                                                                int(max_length), int(bool(need_next)), cap, docs.ctypes.data,
+                                                                written.ctypes.data if written is not None else None,
+                                                                counts.ctypes.data, spans.ctypes.data))
+        q = max(q, 0)
+        return {"spans": spans[:q], "counts": counts[:q]}
+
+    def all_batch_device(self, spans_dev_ptr, s, group_offsets, cap, budget, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr):
+        """Documents holding all spans of every group; group_offsets is a HOST uint64[G + 1] (copied by the call), everything else on
+        the device (cap 0: counts only, docs and offsets may be None); asynchronous until sync()."""
+        go = np.ascontiguousarray(group_offsets, dtype=np.uint64)
+        check(self._lib.sa_hip_token_index_all_batch_device(self._h, spans_dev_ptr, int(s), go.ctypes.data, go.size - 1, int(cap), int(budget),
+                                                            docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr))
+
+    def all_batch(self, patterns, group_offsets, cap=16, budget=0, mode=0, max_length=0, need_next=False, fill=0):
+        """Spans as in spans_batch, cut into groups by group_offsets (uint64[G + 1]: 0 .. S, 1 .. TOKEN_ALL_MAX spans each), then the
+        documents that hold every span of a group.  -> dict: spans [S], docs int32[G, cap], offsets int32[G, cap], heads (written,
+        examined, matched, candidates, driver, count, reserved)[G].  Cells beyond heads['written'] keep `fill`."""
+        buf, off = self._packed(patterns)
+        s = off.size - 1
+        go = np.ascontiguousarray(group_offsets, dtype=np.uint64)
+        g = go.size - 1
+        cap = int(cap)
+        spans = np.zeros(max(s, 1), dtype=SPAN_DTYPE)
+        docs, offs = np.full((max(g, 1), cap), fill, dtype=np.int32), np.full((max(g, 1), cap), fill, dtype=np.int32)
+        heads = np.zeros(max(g, 1), dtype=ALL_DTYPE)
+        if g > 0:
+            check(self._lib.sa_hip_token_index_all_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, max(s, 0),
+                                                         go.ctypes.data, g, int(mode), int(max_length), int(bool(need_next)), cap,
+                                                         int(budget), spans.ctypes.data, docs.ctypes.data if cap else None,
+                                                         offs.ctypes.data if cap else None, heads.ctypes.data))
+        s, g = max(s, 0), max(g, 0)
+        return {"spans": spans[:s], "docs": docs[:g], "offsets": offs[:g], "heads": heads[:g]}
 
 
 class _BorrowedTokenIndex(TokenIndex):

@@ -1,11 +1,12 @@
 // capi_token.hpp -- the C ABI of the token index (include/sa_hip.h section 6), included by sa_capi.hip (same translation unit).
 // The kernels and the search structures are csrc/token_query.hpp, spans and next symbols csrc/token_next.hpp, documents csrc/token_docs.hpp (their entry points:
-// capi_token_docs.hpp); the suffix array of sa_hip_token_index_build comes from
+// capi_token_docs.hpp), per-document counts and AND groups csrc/token_all.hpp (capi_token_all.hpp); the suffix array of sa_hip_token_index_build comes from
 // the build behind sa_hip_libsais_int_device (capi_dropins.hpp: int_device).
 #pragma once
 #include "token_query.hpp"
 #include "token_next.hpp"
 #include "token_docs.hpp"
+#include "token_all.hpp"
 #include <vector>
 
 struct sa_hip_token_index {
@@ -37,6 +38,17 @@ struct sa_hip_token_index {
     u64 lc_q = 0, dc_q = 0;                  // spans of the last locate / documents launch
     double lc_ms = 0.0, dc_ms = 0.0;
     u64 dc_examined = 0;
+    // the rank-by-document array, per-document counts and AND groups (token_all.hpp, capi_token_all.hpp)
+    tq::DocRanks ranks;
+    DevBuf a_goff, a_cnt, a_wr;              // group offsets of the last all launch; staging of the host doc_counts form
+    u32* a_goff_pin = nullptr;               // pinned: what the asynchronous copy into a_goff reads
+    size_t a_goff_pin_cap = 0;               // ... in entries
+    hipEvent_t a_copied = nullptr;           // that copy is done: the pinned buffer may be rewritten
+    bool a_copy_pending = false;
+    hipEvent_t tf_ev[2] = {}, al_ev[2] = {};
+    bool tf_pending = false, al_pending = false;
+    u64 tf_q = 0, al_q = 0;                  // spans of the last doc_counts launch / groups of the last all launch
+    double tf_ms = 0.0, al_ms = 0.0;
 };
 
 namespace {
@@ -59,7 +71,10 @@ int token_create(sa_hip_token_index** out, int device, const char* who) {
         if (e == hipSuccess) e = hipEventCreate(&t->nx_ev[j]);
         if (e == hipSuccess) e = hipEventCreate(&t->lc_ev[j]);
         if (e == hipSuccess) e = hipEventCreate(&t->dc_ev[j]);
+        if (e == hipSuccess) e = hipEventCreate(&t->tf_ev[j]);
+        if (e == hipSuccess) e = hipEventCreate(&t->al_ev[j]);
     }
+    if (e == hipSuccess) e = hipEventCreate(&t->a_copied);
     if (e != hipSuccess) {
         sa_hip_token_index_destroy(t);
         return fail(e == hipErrorOutOfMemory ? SA_HIP_ENOMEM : SA_HIP_EHIP, who, hipGetErrorString(e));
@@ -166,12 +181,18 @@ void sa_hip_token_index_destroy(sa_hip_token_index* t) {
     t->s_spans.release(); t->s_sym.release(); t->s_cnt.release(); t->s_heads.release(); t->s_list.release();
     t->docs.release();
     t->d_docs.release(); t->d_offs.release(); t->d_heads.release();
+    t->ranks.release();
+    t->a_goff.release(); t->a_cnt.release(); t->a_wr.release();
+    if (t->a_goff_pin) (void)hipHostFree(t->a_goff_pin);
+    if (t->a_copied) (void)hipEventDestroy(t->a_copied);
     for (int j = 0; j < 2; ++j) {
         if (t->q_ev[j]) (void)hipEventDestroy(t->q_ev[j]);
         if (t->sp_ev[j]) (void)hipEventDestroy(t->sp_ev[j]);
         if (t->nx_ev[j]) (void)hipEventDestroy(t->nx_ev[j]);
         if (t->lc_ev[j]) (void)hipEventDestroy(t->lc_ev[j]);
         if (t->dc_ev[j]) (void)hipEventDestroy(t->dc_ev[j]);
+        if (t->tf_ev[j]) (void)hipEventDestroy(t->tf_ev[j]);
+        if (t->al_ev[j]) (void)hipEventDestroy(t->al_ev[j]);
     }
     if (t->stream) (void)hipStreamDestroy(t->stream);
     delete t;

@@ -1637,4 +1637,5 @@ int sa_hip_read_suffix_array(sa_hip_SuffixArray_struct* s, const char* sa_filena
 // The token index (batched n-gram ranges over an int32 text): a handle and kernels of its own
 #include "capi_token.hpp"
 #include "capi_token_docs.hpp"
+#include "capi_token_all.hpp"
 #include "capi_token_shards.hpp"

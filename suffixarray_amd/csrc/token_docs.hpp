@@ -186,6 +186,26 @@ inline int docs_table_check(const char* who, const int32_t* starts, u32 D) {
     return 0;
 }
 
+// The sort of the ranks by document, shared by Docs::build (PV) and DocRanks::build (token_all.hpp: RK).  Scratch: two u64 and two
+// u32 arrays of n and a RadixWorkspace, the caller's to free.
+inline int rank_sort_reserve(RadixWorkspace& ws, DevBuf& k0, DevBuf& k1, DevBuf& v0, DevBuf& v1, u32 n) {
+    int rc;
+    if ((rc = ws.init(n, 512)) || (rc = k0.ensure((size_t)n * 8)) || (rc = k1.ensure((size_t)n * 8)) ||
+        (rc = v0.ensure((size_t)n * 4)) || (rc = v1.ensure((size_t)n * 4))) return rc;
+    return 0;
+}
+// k0: the keys DA[r] widened, n >= 1 of them, D >= 2.  Stable, values = iota, key bits [0, bits_for(D)).  *kr / *vr: the buffers
+// that hold the sorted keys and the ranks in document order; *passes: the radix passes it took.
+inline int rank_sort(RadixWorkspace& ws, hipStream_t stream, DevBuf& k0, DevBuf& k1, DevBuf& v0, DevBuf& v1, u32 n, u32 D, u64** kr,
+                     u32** vr, u32* passes) {
+    const u64 before = ws.passes;
+    const int rc = radix_sort_pairs(ws, stream, k0.as<u64>(), v0.as<u32>(), k1.as<u64>(), v1.as<u32>(), n, 0, bits_for(D), true, false,
+                                    kr, vr);
+    if (rc) return rc;
+    *passes = (u32)(ws.passes - before);
+    return 0;
+}
+
 struct Docs {
     DevBuf starts, da, pv, sum;     // sum: the counter of DocsArgs::examined
     hipEvent_t ev[4] = {};          // begin | DA written | ranks sorted | PV written
@@ -239,10 +259,7 @@ struct Docs {
         SA_HIP_CHECK(hipMemcpyAsync(starts.p, closed.data(), (size_t)(D_ + 1) * 4, hipMemcpyHostToDevice, stream));
         SA_HIP_CHECK(hipStreamSynchronize(stream));      // (closed is a local)
         const bool sorted = D_ > 1 && n > 0;             // one document: PV[r] = r - 1, and iota with zero passes is refused
-        if (sorted) {
-            if ((rc = ws.init(n, 512)) || (rc = k0.ensure((size_t)n * 8)) || (rc = k1.ensure((size_t)n * 8)) ||
-                (rc = v0.ensure((size_t)n * 4)) || (rc = v1.ensure((size_t)n * 4))) return rc;
-        }
+        if (sorted && (rc = rank_sort_reserve(ws, k0, k1, v0, v1, n))) return rc;
         SA_HIP_CHECK(hipEventRecord(ev[0], stream));
         u64* kr = nullptr; u32* vr = nullptr;
         if (n) {
@@ -251,12 +268,7 @@ struct Docs {
             SA_HIP_CHECK(hipGetLastError());
         }
         SA_HIP_CHECK(hipEventRecord(ev[1], stream));
-        if (sorted) {
-            const u64 before = ws.passes;
-            if ((rc = radix_sort_pairs(ws, stream, k0.as<u64>(), v0.as<u32>(), k1.as<u64>(), v1.as<u32>(), n, 0, bits_for(D_), true, false,
-                                       &kr, &vr))) return rc;
-            passes = (u32)(ws.passes - before);
-        }
+        if (sorted && (rc = rank_sort(ws, stream, k0, k1, v0, v1, n, D_, &kr, &vr, &passes))) return rc;
         SA_HIP_CHECK(hipEventRecord(ev[2], stream));
         if (n) {
             hipLaunchKernelGGL(td_pv_kernel, dim3(stream_grid(n, 1024)), dim3(BLOCK), 0, stream, (const u64*)kr, (const u32*)vr, n,

@@ -9,6 +9,8 @@
     ti.locate([464, 2068], limit=10)       # where, as (document, offset inside it)
     ti.document_counts([[464, 2068], [11]])   # in how many documents every n-gram occurs
     ti.documents(ngrams, cap=16)           # which documents, in order of first appearance by rank
+    ti.term_counts(ngrams, docs)           # how often every n-gram occurs in every one of these documents: uint32[Q, len(docs)]
+    ti.documents_with_all([[[464, 2068], [11]]], cap=16)    # per group of n-grams: the documents that hold all of them
 
 On top of the handle API of include/sa_hip.h section 6 (suffixarray_amd._capi.TokenIndex).  No CPU fallback.
 """
@@ -60,6 +62,64 @@ class TokenIndex:
         occurrences in suffix order when given; exact says that these were all)"""
         h = self._idx.docs_batch(ngrams, cap=0, budget=budget or 0)["heads"]
         return h["distinct"].copy(), h["examined"] == h["count"]
+
+    def prepare_document_ranks(self):
+        """Build the rank-by-document array (4 bytes per token) that term_counts and documents_with_all need; they call this on
+        first use.  set_documents drops it."""
+        self._idx.prepare_doc_ranks(True)
+
+    def term_counts(self, ngrams, docs):
+        """-> uint32[len(ngrams), len(docs)]: how often n-gram i occurs in document docs[j] (its term frequency there); a document
+        id outside the table counts 0."""
+        docs = np.ascontiguousarray(docs, dtype=np.int64).reshape(-1)
+        if docs.size and (docs.min() < -2 ** 31 or docs.max() > 2 ** 31 - 1):
+            raise ValueError("docs: document ids are int32")
+        buf, off = self._idx._packed(ngrams)
+        q = max(off.size - 1, 0)
+        if q == 0 or docs.size == 0:
+            return np.zeros((q, docs.size), np.uint32)
+        self.prepare_document_ranks()
+        rows = np.broadcast_to(docs.astype(np.int32), (q, docs.size))
+        return self._idx.doc_counts_batch((buf, off), rows)["counts"]
+
+    @staticmethod
+    def _grouped(groups):
+        flat, goff = [], [0]
+        for g in groups:
+            g = [list(x) for x in g]
+            if not 1 <= len(g) <= _capi.TOKEN_ALL_MAX:
+                raise ValueError("a group holds 1 .. %d n-grams" % _capi.TOKEN_ALL_MAX)
+            flat += g
+            goff.append(len(flat))
+        return flat, np.array(goff, np.uint64)
+
+    def documents_with_all(self, groups, cap=16, budget=None, longest_suffix=False, max_length=None):
+        """Which documents hold ALL n-grams of a group (an AND query).  groups: a list of lists of n-grams, 1 .. 16 per group.
+        -> one dict per group: documents and offsets (int32 arrays, at most cap entries: the matching documents in the rank order
+        of the group's rarest n-gram, each with the offset of that n-gram's smallest-rank occurrence in it), matched (how many
+        documents matched among the first `budget` occurrences of the rarest n-gram), exact (these were all its occurrences, so
+        matched is the number of documents that hold all n-grams), driver (the index of that n-gram inside the group)."""
+        flat, goff = self._grouped(groups)
+        if not len(groups):
+            return []
+        self.prepare_document_ranks()
+        r = self._idx.all_batch(flat, goff, cap=cap, budget=budget or 0, mode=1 if longest_suffix else 0, max_length=max_length or 0,
+                                need_next=False)
+        out = []
+        for i, h in enumerate(r["heads"]):
+            w = int(h["written"])
+            out.append({"documents": r["docs"][i, :w].copy(), "offsets": r["offsets"][i, :w].copy(), "matched": int(h["matched"]),
+                        "exact": bool(h["examined"] == h["count"]), "driver": int(h["driver"])})
+        return out
+
+    def count_documents_with_all(self, groups, budget=None):
+        """-> (matched uint32[G], exact bool[G]): in how many documents all n-grams of every group occur"""
+        flat, goff = self._grouped(groups)
+        if not len(groups):
+            return np.zeros(0, np.uint32), np.zeros(0, np.bool_)
+        self.prepare_document_ranks()
+        h = self._idx.all_batch(flat, goff, cap=0, budget=budget or 0)["heads"]
+        return h["matched"].copy(), h["examined"] == h["count"]
 
     def ranges(self, ngrams):
         """-> (first, count), uint32[Q] each: n-gram i occurs at the text positions SA[first[i] .. first[i] + count[i]);
