@@ -1188,33 +1188,29 @@ def pack_ngrams(ngrams):
     return np.array(flat, dtype=np.int32), off
 
 
-class TokenIndex:
-    """Handle API of the token index (sa_hip_token_index): an int32 text, its suffix array and the n-gram search structures in
-    HBM.  Results are structured (first, second) = (suffixes that sort before the pattern, occurrences)."""
+def _ptr(a):
+    """the address of an array; None for None and for an array without cells"""
+    return a.ctypes.data if a is not None and a.size else None
 
-    def __init__(self, handle):
-        self._h = handle
-        self._lib = lib()
 
-    @classmethod
-    def build(cls, tokens, k=None, device=0):
-        """From a host text of symbols in [0, k) (k defaults to max + 1): upload, device build, search structures."""
-        t = _int_text(tokens, np.int32)
-        h = C.c_void_p()
-        k = min(_int_k(t, k), 2 ** 31 - 1)   # (k = INT32_MAX admits the symbol 2^31 - 1 too)
-        check(lib().sa_hip_token_index_build(C.byref(h), t.ctypes.data if t.size else None, t.size, k, int(device)))
-        return cls(h)
+def _rows(q, dtype, cap=None, fill=0):
+    """An output of the host forms, filled: [max(q, 1)], or [max(q, 1), cap] with a cap (the library gets a row even when the batch
+    is empty; the caller cuts to q).  An unsigned array takes the fill modulo its width."""
+    dt = np.dtype(dtype)
+    if dt.kind == "u":
+        fill &= (1 << 8 * dt.itemsize) - 1
+    shape = max(q, 1) if cap is None else (max(q, 1), cap)
+    return np.full(shape, fill, dtype=dt) if fill else np.zeros(shape, dtype=dt)
 
-    @classmethod
-    def load_device(cls, text_dev_ptr, sa_dev_ptr, n, device=0):
-        """Adopt n int32 symbols and their int32 suffix array from device memory (copied into the handle)."""
-        h = C.c_void_p()
-        check(lib().sa_hip_token_index_load_device(C.byref(h), text_dev_ptr, sa_dev_ptr, int(n), int(device)))
-        return cls(h)
+
+class _TokenHandle:
+    """What TokenIndex and TokenShards share: the handle and its release through the library's _destroy, the packing of a host
+    batch, the call of a host form and the *_info calls."""
+    _destroy = None
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
-            self._lib.sa_hip_token_index_destroy(self._h)
+            getattr(self._lib, self._destroy)(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -1229,17 +1225,59 @@ class TokenIndex:
     def __exit__(self, *exc):
         self.close()
 
+    @staticmethod
+    def _packed(patterns):
+        buf, off = patterns if isinstance(patterns, tuple) else pack_ngrams(patterns)
+        return np.ascontiguousarray(buf, dtype=np.int32), np.ascontiguousarray(off, dtype=np.uint64)
+
+    @classmethod
+    def _contexts(cls, patterns):
+        """-> (packed int32, uint64 offsets, Q) of a host batch"""
+        buf, off = cls._packed(patterns)
+        return buf, off, max(off.size - 1, 0)
+
+    def _call(self, q, fn, *args):
+        """the host form fn on the handle; an empty batch does not reach the library"""
+        if q > 0:
+            check(fn(self._h, *args))
+
+    def _info(self, fn, struct_cls):
+        st = struct_cls()
+        check(fn(self._h, C.byref(st)))
+        return st.as_dict()
+
+
+class TokenIndex(_TokenHandle):
+    """Handle API of the token index (sa_hip_token_index): an int32 text, its suffix array and the n-gram search structures in
+    HBM.  Results are structured (first, second) = (suffixes that sort before the pattern, occurrences)."""
+    _destroy = "sa_hip_token_index_destroy"
+
+    def __init__(self, handle):
+        self._h = handle
+        self._lib = lib()
+
+    @classmethod
+    def build(cls, tokens, k=None, device=0):
+        """From a host text of symbols in [0, k) (k defaults to max + 1): upload, device build, search structures."""
+        t = _int_text(tokens, np.int32)
+        h = C.c_void_p()
+        k = min(_int_k(t, k), 2 ** 31 - 1)   # (k = INT32_MAX admits the symbol 2^31 - 1 too)
+        check(lib().sa_hip_token_index_build(C.byref(h), _ptr(t), t.size, k, int(device)))
+        return cls(h)
+
+    @classmethod
+    def load_device(cls, text_dev_ptr, sa_dev_ptr, n, device=0):
+        """Adopt n int32 symbols and their int32 suffix array from device memory (copied into the handle)."""
+        h = C.c_void_p()
+        check(lib().sa_hip_token_index_load_device(C.byref(h), text_dev_ptr, sa_dev_ptr, int(n), int(device)))
+        return cls(h)
+
     def query_batch(self, patterns):
         """patterns: list of int sequences or (packed int32, uint64 offsets).  -> structured array (first, second)."""
-        buf, off = patterns if isinstance(patterns, tuple) else pack_ngrams(patterns)
-        buf = np.ascontiguousarray(buf, dtype=np.int32)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        q = off.size - 1
-        out = np.zeros(max(q, 1), dtype=PAIR_DTYPE)
-        if q > 0:
-            check(self._lib.sa_hip_token_index_query_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q,
-                                                           out.ctypes.data))
-        return out[:max(q, 0)]
+        buf, off, q = self._contexts(patterns)
+        out = _rows(q, PAIR_DTYPE)
+        self._call(q, self._lib.sa_hip_token_index_query_batch, _ptr(buf), _ptr(off), q, _ptr(out))
+        return out[:q]
 
     def query_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, out_dev_ptr):
         """Every buffer on the device; asynchronous on the handle's stream until sync()."""
@@ -1262,25 +1300,15 @@ class TokenIndex:
         return out[:count]
 
     def info(self):
-        st = TokenInfo()
-        check(self._lib.sa_hip_token_index_info(self._h, C.byref(st)))
-        return st.as_dict()
-
-    @staticmethod
-    def _packed(patterns):
-        buf, off = patterns if isinstance(patterns, tuple) else pack_ngrams(patterns)
-        return np.ascontiguousarray(buf, dtype=np.int32), np.ascontiguousarray(off, dtype=np.uint64)
+        return self._info(self._lib.sa_hip_token_index_info, TokenInfo)
 
     def spans_batch(self, patterns, mode=0, max_length=0, need_next=True):
         """patterns as in query_batch.  mode 0: the span of every whole pattern; mode 1: of its longest suffix that occurs (with
         a next symbol when need_next), at most max_length symbols (0: no cap).  -> structured array (first, count, length, ended)."""
-        buf, off = self._packed(patterns)
-        q = off.size - 1
-        out = np.zeros(max(q, 1), dtype=SPAN_DTYPE)
-        if q > 0:
-            check(self._lib.sa_hip_token_index_spans_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
-                                                           int(max_length), int(bool(need_next)), out.ctypes.data))
-        return out[:max(q, 0)]
+        buf, off, q = self._contexts(patterns)
+        out = _rows(q, SPAN_DTYPE)
+        self._call(q, self._lib.sa_hip_token_index_spans_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)), _ptr(out))
+        return out[:q]
 
     def spans_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, mode, max_length, need_next, spans_dev_ptr):
         """Every buffer on the device; asynchronous on the handle's stream until sync()."""
@@ -1292,39 +1320,27 @@ class TokenIndex:
         check(self._lib.sa_hip_token_index_next_batch_device(self._h, spans_dev_ptr, q, int(cap), symbols_dev_ptr, counts_dev_ptr,
                                                              heads_dev_ptr))
 
-    @staticmethod
-    def _next_out(q, cap, fill):
-        return (np.full((max(q, 1), cap), fill, dtype=np.int32), np.full((max(q, 1), cap), fill & 0xFFFFFFFF, dtype=np.uint32),
-                np.zeros(max(q, 1), dtype=NEXT_DTYPE))
-
     def next_batch(self, patterns, cap=64, mode=0, max_length=0, need_next=True, fill=0):
         """Spans as in spans_batch, then their next symbols.  -> dict: spans [Q], symbols int32[Q, cap], counts uint32[Q, cap],
         heads (written, covered, total, reserved)[Q].  Cells beyond heads['written'] keep `fill`."""
-        buf, off = self._packed(patterns)
-        q = off.size - 1
-        spans = np.zeros(max(q, 1), dtype=SPAN_DTYPE)
-        sym, cnt, heads = self._next_out(q, int(cap), fill)
-        if q > 0:
-            check(self._lib.sa_hip_token_index_next_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
-                                                          int(max_length), int(bool(need_next)), int(cap), spans.ctypes.data,
-                                                          sym.ctypes.data, cnt.ctypes.data, heads.ctypes.data))
-        q = max(q, 0)
+        buf, off, q = self._contexts(patterns)
+        cap = int(cap)
+        spans, heads = _rows(q, SPAN_DTYPE), _rows(q, NEXT_DTYPE)
+        sym, cnt = _rows(q, np.int32, cap, fill), _rows(q, np.uint32, cap, fill)
+        self._call(q, self._lib.sa_hip_token_index_next_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)), cap,
+                   _ptr(spans), _ptr(sym), _ptr(cnt), _ptr(heads))
         return {"spans": spans[:q], "symbols": sym[:q], "counts": cnt[:q], "heads": heads[:q]}
 
     def next_of_spans(self, spans, cap=64, fill=0):
         """Next symbols of host spans (a SPAN_DTYPE array, e.g. from spans_batch); a span beyond the array raises."""
         spans = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
-        q = spans.size
-        sym, cnt, heads = self._next_out(q, int(cap), fill)
-        if q > 0:
-            check(self._lib.sa_hip_token_index_next_of_spans(self._h, spans.ctypes.data, q, int(cap), sym.ctypes.data, cnt.ctypes.data,
-                                                             heads.ctypes.data))
+        q, cap = spans.size, int(cap)
+        sym, cnt, heads = _rows(q, np.int32, cap, fill), _rows(q, np.uint32, cap, fill), _rows(q, NEXT_DTYPE)
+        self._call(q, self._lib.sa_hip_token_index_next_of_spans, _ptr(spans), q, cap, _ptr(sym), _ptr(cnt), _ptr(heads))
         return {"spans": spans, "symbols": sym[:q], "counts": cnt[:q], "heads": heads[:q]}
 
     def next_info(self):
-        st = TokenNextInfo()
-        check(self._lib.sa_hip_token_index_next_info(self._h, C.byref(st)))
-        return st.as_dict()
+        return self._info(self._lib.sa_hip_token_index_next_info, TokenNextInfo)
 
     def set_documents(self, starts):
         """starts: the first text position of every document (starts[0] == 0, non-decreasing, <= n); None removes the documents."""
@@ -1344,9 +1360,7 @@ class TokenIndex:
         return da[:count], pv[:count]
 
     def docs_info(self):
-        st = TokenDocsInfo()
-        check(self._lib.sa_hip_token_index_docs_info(self._h, C.byref(st)))
-        return st.as_dict()
+        return self._info(self._lib.sa_hip_token_index_docs_info, TokenDocsInfo)
 
     def locate_batch_device(self, spans_dev_ptr, q, cap, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr):
         """(document, offset) of the first cap occurrences of q device spans; asynchronous on the handle's stream until sync()."""
@@ -1356,15 +1370,11 @@ class TokenIndex:
     def locate_batch(self, patterns, cap=16, fill=0):
         """The exact span of every pattern, then its first cap occurrences.  -> dict: spans [Q], docs int32[Q, cap], offsets
         int32[Q, cap], heads (written, count)[Q].  Cells beyond heads['written'] keep `fill`."""
-        buf, off = self._packed(patterns)
-        q = off.size - 1
-        spans = np.zeros(max(q, 1), dtype=SPAN_DTYPE)
-        docs, offs = np.full((max(q, 1), int(cap)), fill, dtype=np.int32), np.full((max(q, 1), int(cap)), fill, dtype=np.int32)
-        heads = np.zeros(max(q, 1), dtype=LOCATE_DTYPE)
-        if q > 0:
-            check(self._lib.sa_hip_token_index_locate_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(cap),
-                                                            spans.ctypes.data, docs.ctypes.data, offs.ctypes.data, heads.ctypes.data))
-        q = max(q, 0)
+        buf, off, q = self._contexts(patterns)
+        cap = int(cap)
+        spans, heads = _rows(q, SPAN_DTYPE), _rows(q, LOCATE_DTYPE)
+        docs, offs = _rows(q, np.int32, cap, fill), _rows(q, np.int32, cap, fill)
+        self._call(q, self._lib.sa_hip_token_index_locate_batch, _ptr(buf), _ptr(off), q, cap, _ptr(spans), _ptr(docs), _ptr(offs), _ptr(heads))
         return {"spans": spans[:q], "docs": docs[:q], "offsets": offs[:q], "heads": heads[:q]}
 
     def docs_batch_device(self, spans_dev_ptr, q, cap, budget, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr):
@@ -1375,18 +1385,12 @@ class TokenIndex:
     def docs_batch(self, patterns, cap=16, budget=0, mode=0, max_length=0, need_next=False, fill=0):
         """Spans as in spans_batch, then their distinct documents among the first `budget` ranks (0: all).  -> dict: spans [Q], docs
         int32[Q, cap], offsets int32[Q, cap], heads (written, examined, distinct, count)[Q].  Cells beyond heads['written'] keep `fill`."""
-        buf, off = self._packed(patterns)
-        q = off.size - 1
+        buf, off, q = self._contexts(patterns)
         cap = int(cap)
-        spans = np.zeros(max(q, 1), dtype=SPAN_DTYPE)
-        docs, offs = np.full((max(q, 1), cap), fill, dtype=np.int32), np.full((max(q, 1), cap), fill, dtype=np.int32)
-        heads = np.zeros(max(q, 1), dtype=DOCS_DTYPE)
-        if q > 0:
-            check(self._lib.sa_hip_token_index_docs_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
-                                                          int(max_length), int(bool(need_next)), cap, int(budget), spans.ctypes.data,
-                                                          docs.ctypes.data if cap else None, offs.ctypes.data if cap else None,
-                                                          heads.ctypes.data))
-        q = max(q, 0)
+        spans, heads = _rows(q, SPAN_DTYPE), _rows(q, DOCS_DTYPE)
+        docs, offs = _rows(q, np.int32, cap, fill), _rows(q, np.int32, cap, fill)
+        self._call(q, self._lib.sa_hip_token_index_docs_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)), cap,
+                   int(budget), _ptr(spans), _ptr(docs), _ptr(offs), _ptr(heads))
         return {"spans": spans[:q], "docs": docs[:q], "offsets": offs[:q], "heads": heads[:q]}
 
     def prepare_doc_ranks(self, on=True):
@@ -1401,9 +1405,7 @@ class TokenIndex:
         return out[:count]
 
     def doc_ranks_info(self):
-        st = TokenDocRanksInfo()
-        check(self._lib.sa_hip_token_index_doc_ranks_info(self._h, C.byref(st)))
-        return st.as_dict()
+        return self._info(self._lib.sa_hip_token_index_doc_ranks_info, TokenDocRanksInfo)
 
     def doc_counts_batch_device(self, spans_dev_ptr, q, cap, docs_dev_ptr, written_dev_ptr, written_stride, counts_dev_ptr):
         """counts[i, j] = ranks of device span i inside document docs[i, j], j below the row's length (written_dev_ptr None: cap);
@@ -1414,24 +1416,18 @@ class TokenIndex:
     def doc_counts_batch(self, patterns, docs, written=None, mode=0, max_length=0, need_next=False, fill=0):
         """Spans as in spans_batch, then how often every one occurs in the documents of its row.  docs: int32[Q, cap]; written:
         uint32[Q] row lengths or None.  -> dict: spans [Q], counts uint32[Q, cap].  Cells beyond a row's length keep `fill`."""
-        buf, off = self._packed(patterns)
-        q = off.size - 1
+        buf, off, q = self._contexts(patterns)
         docs = np.ascontiguousarray(docs, dtype=np.int32)
-        if docs.ndim != 2 or docs.shape[0] != max(q, 0):
+        if docs.ndim != 2 or docs.shape[0] != q:
             raise ValueError("docs: one row of document ids per pattern")
         cap = docs.shape[1]
         if written is not None:
             written = np.ascontiguousarray(written, dtype=np.uint32)
-            if written.shape != (max(q, 0),):
+            if written.shape != (q,):
                 raise ValueError("written: one row length per pattern")
-        spans = np.zeros(max(q, 1), dtype=SPAN_DTYPE)
-        counts = np.full((max(q, 1), cap), fill & 0xFFFFFFFF, dtype=np.uint32)
-        if q > 0:
-            check(self._lib.sa_hip_token_index_doc_counts_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
-                                                                int(max_length), int(bool(need_next)), cap, docs.ctypes.data,
-                                                                written.ctypes.data if written is not None else None,
-                                                                counts.ctypes.data, spans.ctypes.data))
-        q = max(q, 0)
+        spans, counts = _rows(q, SPAN_DTYPE), _rows(q, np.uint32, cap, fill)
+        self._call(q, self._lib.sa_hip_token_index_doc_counts_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)), cap,
+                   docs.ctypes.data, _ptr(written), counts.ctypes.data, _ptr(spans))
         return {"spans": spans[:q], "counts": counts[:q]}
 
     def all_batch_device(self, spans_dev_ptr, s, group_offsets, cap, budget, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr):
@@ -1445,20 +1441,14 @@ class TokenIndex:
         """Spans as in spans_batch, cut into groups by group_offsets (uint64[G + 1]: 0 .. S, 1 .. TOKEN_ALL_MAX spans each), then the
         documents that hold every span of a group.  -> dict: spans [S], docs int32[G, cap], offsets int32[G, cap], heads (written,
         examined, matched, candidates, driver, count, reserved)[G].  Cells beyond heads['written'] keep `fill`."""
-        buf, off = self._packed(patterns)
-        s = off.size - 1
+        buf, off, s = self._contexts(patterns)
         go = np.ascontiguousarray(group_offsets, dtype=np.uint64)
-        g = go.size - 1
+        g = max(go.size - 1, 0)
         cap = int(cap)
-        spans = np.zeros(max(s, 1), dtype=SPAN_DTYPE)
-        docs, offs = np.full((max(g, 1), cap), fill, dtype=np.int32), np.full((max(g, 1), cap), fill, dtype=np.int32)
-        heads = np.zeros(max(g, 1), dtype=ALL_DTYPE)
-        if g > 0:
-            check(self._lib.sa_hip_token_index_all_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, max(s, 0),
-                                                         go.ctypes.data, g, int(mode), int(max_length), int(bool(need_next)), cap,
-                                                         int(budget), spans.ctypes.data, docs.ctypes.data if cap else None,
-                                                         offs.ctypes.data if cap else None, heads.ctypes.data))
-        s, g = max(s, 0), max(g, 0)
+        spans, heads = _rows(s, SPAN_DTYPE), _rows(g, ALL_DTYPE)
+        docs, offs = _rows(g, np.int32, cap, fill), _rows(g, np.int32, cap, fill)
+        self._call(g, self._lib.sa_hip_token_index_all_batch, _ptr(buf), _ptr(off), s, go.ctypes.data, g, int(mode), int(max_length),
+                   int(bool(need_next)), cap, int(budget), _ptr(spans), _ptr(docs), _ptr(offs), _ptr(heads))
         return {"spans": spans[:s], "docs": docs[:g], "offsets": offs[:g], "heads": heads[:g]}
 
 
@@ -1469,9 +1459,10 @@ class _BorrowedTokenIndex(TokenIndex):
         self._h = C.c_void_p()
 
 
-class TokenShards:
+class TokenShards(_TokenHandle):
     """Handle API of a shard set (sa_hip_token_shards): S <= 64 token indexes on one device answered as one corpus.  Per-shard
     results are shard-major arrays of shape [S, Q]."""
+    _destroy = "sa_hip_token_shards_destroy"
 
     def __init__(self, handle, shards):
         self._h = handle
@@ -1502,23 +1493,6 @@ class TokenShards:
                 t.close()
             raise
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.sa_hip_token_shards_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     def shard(self, s):
         """The borrowed TokenIndex of shard s (valid while the set lives; do not use it while the set is being asked)."""
         h = self._lib.sa_hip_token_shards_shard(self._h, int(s))
@@ -1530,20 +1504,18 @@ class TokenShards:
         check(self._lib.sa_hip_token_shards_sync(self._h))
 
     def info(self):
-        st = TokenShardsStats()
-        check(self._lib.sa_hip_token_shards_info(self._h, C.byref(st)))
-        return st.as_dict()
+        return self._info(self._lib.sa_hip_token_shards_info, TokenShardsStats)
+
+    def _shard_rows(self, q, dtype):
+        """a per-shard output of zeros, [S, max(q, 1)]"""
+        return np.zeros((self.shards, max(q, 1)), dtype=dtype)
 
     def query_batch(self, patterns, per_shard=True):
         """-> (totals uint64[Q], per_shard structured (first, second)[S, Q] or None)"""
-        buf, off = TokenIndex._packed(patterns)
-        q = off.size - 1
-        totals = np.zeros(max(q, 1), dtype=np.uint64)
-        per = np.zeros((self.shards, max(q, 1)), dtype=PAIR_DTYPE) if per_shard else None
-        if q > 0:
-            check(self._lib.sa_hip_token_shards_query_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q,
-                                                            totals.ctypes.data, per.ctypes.data if per_shard else None))
-        q = max(q, 0)
+        buf, off, q = self._contexts(patterns)
+        totals = _rows(q, np.uint64)
+        per = self._shard_rows(q, PAIR_DTYPE) if per_shard else None
+        self._call(q, self._lib.sa_hip_token_shards_query_batch, _ptr(buf), _ptr(off), q, _ptr(totals), _ptr(per))
         return totals[:q], (per[:, :q] if per_shard else None)
 
     def query_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, totals_dev_ptr, per_shard_dev_ptr=None):
@@ -1552,16 +1524,10 @@ class TokenShards:
 
     def spans_batch(self, patterns, mode=0, max_length=0, need_next=True):
         """-> dict: length uint32[Q], totals uint64[Q], spans structured (first, count, length, ended)[S, Q]"""
-        buf, off = TokenIndex._packed(patterns)
-        q = off.size - 1
-        length = np.zeros(max(q, 1), dtype=np.uint32)
-        totals = np.zeros(max(q, 1), dtype=np.uint64)
-        spans = np.zeros((self.shards, max(q, 1)), dtype=SPAN_DTYPE)
-        if q > 0:
-            check(self._lib.sa_hip_token_shards_spans_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
-                                                            int(max_length), int(bool(need_next)), length.ctypes.data, totals.ctypes.data,
-                                                            spans.ctypes.data))
-        q = max(q, 0)
+        buf, off, q = self._contexts(patterns)
+        length, totals, spans = _rows(q, np.uint32), _rows(q, np.uint64), self._shard_rows(q, SPAN_DTYPE)
+        self._call(q, self._lib.sa_hip_token_shards_spans_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)),
+                   _ptr(length), _ptr(totals), _ptr(spans))
         return {"length": length[:q], "totals": totals[:q], "spans": spans[:, :q]}
 
     def spans_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, mode, max_length, need_next, length_dev_ptr, totals_dev_ptr, spans_dev_ptr):
@@ -1571,18 +1537,12 @@ class TokenShards:
     def next_batch(self, patterns, cap=64, mode=0, max_length=0, need_next=True, fill=0):
         """Spans as in spans_batch, then the merged next symbols.  -> dict: spans [S, Q], symbols int32[Q, cap], counts
         uint64[Q, cap], heads (written, length, covered, total)[Q].  Cells beyond heads['written'] keep `fill`."""
-        buf, off = TokenIndex._packed(patterns)
-        q = off.size - 1
+        buf, off, q = self._contexts(patterns)
         cap = int(cap)
-        spans = np.zeros((self.shards, max(q, 1)), dtype=SPAN_DTYPE)
-        sym = np.full((max(q, 1), cap), fill, dtype=np.int32)
-        cnt = np.full((max(q, 1), cap), fill & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
-        heads = np.zeros(max(q, 1), dtype=SHARDS_NEXT_DTYPE)
-        if q > 0:
-            check(self._lib.sa_hip_token_shards_next_batch(self._h, buf.ctypes.data if buf.size else None, off.ctypes.data, q, int(mode),
-                                                           int(max_length), int(bool(need_next)), cap, spans.ctypes.data, sym.ctypes.data,
-                                                           cnt.ctypes.data, heads.ctypes.data))
-        q = max(q, 0)
+        spans, heads = self._shard_rows(q, SPAN_DTYPE), _rows(q, SHARDS_NEXT_DTYPE)
+        sym, cnt = _rows(q, np.int32, cap, fill), _rows(q, np.uint64, cap, fill)
+        self._call(q, self._lib.sa_hip_token_shards_next_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)), cap,
+                   _ptr(spans), _ptr(sym), _ptr(cnt), _ptr(heads))
         return {"spans": spans[:, :q], "symbols": sym[:q], "counts": cnt[:q], "heads": heads[:q]}
 
     def next_batch_device(self, spans_dev_ptr, q, cap, symbols_dev_ptr, counts_dev_ptr, heads_dev_ptr):

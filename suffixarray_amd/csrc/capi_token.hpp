@@ -2,11 +2,16 @@
 // The kernels and the search structures are csrc/token_query.hpp, spans and next symbols csrc/token_next.hpp, documents csrc/token_docs.hpp (their entry points:
 // capi_token_docs.hpp), per-document counts and AND groups csrc/token_all.hpp (capi_token_all.hpp); the suffix array of sa_hip_token_index_build comes from
 // the build behind sa_hip_libsais_int_device (capi_dropins.hpp: int_device).
+// What the four capi_token*.hpp files share is here and in two small headers: the stopwatch of a launch (launch_timer.hpp), the upload of
+// a host batch of contexts (token_upload), and the copy of the written entries of staged rows to the caller (host_rows.hpp).
 #pragma once
+#include "launch_timer.hpp"
+#include "host_rows.hpp"
 #include "token_query.hpp"
 #include "token_next.hpp"
 #include "token_docs.hpp"
 #include "token_all.hpp"
+#include <array>
 #include <vector>
 
 struct sa_hip_token_index {
@@ -15,28 +20,19 @@ struct sa_hip_token_index {
     std::mutex mu;
     tq::Index x;
     DevBuf q_pat, q_off, q_out;          // staging of the host-pointer query
-    hipEvent_t q_ev[2] = {};             // the last search launch
-    bool q_pending = false;              // recorded, not yet resolved
-    u64 q_last = 0;
-    double q_ms = 0.0;
+    LaunchTimer tm_q;                    // the last search launch
     // spans and next symbols (token_next.hpp)
     tq::NextKnobs next_knobs;
     DevBuf s_spans, s_sym, s_cnt, s_heads;   // staging of the host forms
     DevBuf s_list;                           // [0, 64): the list's length, [64, ..): ranks of the spans left to the wave form
-    hipEvent_t sp_ev[2] = {}, nx_ev[2] = {};
-    bool sp_pending = false, nx_pending = false;
+    LaunchTimer tm_sp, tm_nx;                // the last spans / next launch
     u64 s_last = 0;                          // contexts / spans of the last launch of either kind
-    u64 nx_q = 0;                            // spans of the last next launch
-    bool nx_lanes = false;                   // ... and whether it went through the lane form
-    double sp_ms = 0.0, nx_ms = 0.0;
+    bool nx_lanes = false;                   // whether the last next launch went through the lane form
     u64 nx_lane_spans = 0, nx_wave_spans = 0;
     // documents (token_docs.hpp, capi_token_docs.hpp)
     tq::Docs docs;
     DevBuf d_docs, d_offs, d_heads;          // staging of the host forms
-    hipEvent_t lc_ev[2] = {}, dc_ev[2] = {};
-    bool lc_pending = false, dc_pending = false;
-    u64 lc_q = 0, dc_q = 0;                  // spans of the last locate / documents launch
-    double lc_ms = 0.0, dc_ms = 0.0;
+    LaunchTimer tm_lc, tm_dc;                // the last locate / documents launch
     u64 dc_examined = 0;
     // the rank-by-document array, per-document counts and AND groups (token_all.hpp, capi_token_all.hpp)
     tq::DocRanks ranks;
@@ -45,10 +41,9 @@ struct sa_hip_token_index {
     size_t a_goff_pin_cap = 0;               // ... in entries
     hipEvent_t a_copied = nullptr;           // that copy is done: the pinned buffer may be rewritten
     bool a_copy_pending = false;
-    hipEvent_t tf_ev[2] = {}, al_ev[2] = {};
-    bool tf_pending = false, al_pending = false;
-    u64 tf_q = 0, al_q = 0;                  // spans of the last doc_counts launch / groups of the last all launch
-    double tf_ms = 0.0, al_ms = 0.0;
+    LaunchTimer tm_tf, tm_al;                // the last doc_counts launch (q: spans) / all launch (q: groups)
+
+    std::array<LaunchTimer*, 7> timers() { return {&tm_q, &tm_sp, &tm_nx, &tm_lc, &tm_dc, &tm_tf, &tm_al}; }
 };
 
 namespace {
@@ -65,15 +60,7 @@ int token_create(sa_hip_token_index** out, int device, const char* who) {
     t->x.knobs = tq::Knobs::read();
     t->next_knobs = tq::NextKnobs::read();
     hipError_t e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
-    for (int j = 0; j < 2; ++j) {
-        if (e == hipSuccess) e = hipEventCreate(&t->q_ev[j]);
-        if (e == hipSuccess) e = hipEventCreate(&t->sp_ev[j]);
-        if (e == hipSuccess) e = hipEventCreate(&t->nx_ev[j]);
-        if (e == hipSuccess) e = hipEventCreate(&t->lc_ev[j]);
-        if (e == hipSuccess) e = hipEventCreate(&t->dc_ev[j]);
-        if (e == hipSuccess) e = hipEventCreate(&t->tf_ev[j]);
-        if (e == hipSuccess) e = hipEventCreate(&t->al_ev[j]);
-    }
+    for (LaunchTimer* w : t->timers()) if (e == hipSuccess) e = w->create();
     if (e == hipSuccess) e = hipEventCreate(&t->a_copied);
     if (e != hipSuccess) {
         sa_hip_token_index_destroy(t);
@@ -84,13 +71,9 @@ int token_create(sa_hip_token_index** out, int device, const char* who) {
 }
 
 int token_launch(sa_hip_token_index* t, const int32_t* pat, const u64* off, u64 Q, sa_hip_pair_u32* out) {
-    SA_HIP_CHECK(hipEventRecord(t->q_ev[0], t->stream));
-    const int rc = t->x.search(t->stream, pat, off, Q, out);
-    if (rc) return rc;
-    SA_HIP_CHECK(hipEventRecord(t->q_ev[1], t->stream));
-    t->q_pending = true;
-    t->q_last = Q;
-    return 0;
+    int rc;
+    if ((rc = t->tm_q.begin(t->stream)) || (rc = t->x.search(t->stream, pat, off, Q, out))) return rc;
+    return t->tm_q.end(t->stream, Q);
 }
 
 // what every spans / next entry point refuses before it touches the handle or the device
@@ -112,11 +95,9 @@ int token_offsets_args(const char* who, const int32_t* patterns, const uint64_t*
 
 int token_launch_spans(sa_hip_token_index* t, const int32_t* pat, const u64* off, u64 Q, int mode, u32 max_length, int need_next,
                        sa_hip_token_span* out) {
-    SA_HIP_CHECK(hipEventRecord(t->sp_ev[0], t->stream));
-    const int rc = tq::launch_spans(t->x, t->stream, pat, off, Q, mode, max_length, need_next, out);
-    if (rc) return rc;
-    SA_HIP_CHECK(hipEventRecord(t->sp_ev[1], t->stream));
-    t->sp_pending = true;
+    int rc;
+    if ((rc = t->tm_sp.begin(t->stream)) || (rc = tq::launch_spans(t->x, t->stream, pat, off, Q, mode, max_length, need_next, out)) ||
+        (rc = t->tm_sp.end(t->stream, Q))) return rc;
     t->s_last = Q;
     return 0;
 }
@@ -127,12 +108,21 @@ int token_launch_next(sa_hip_token_index* t, const sa_hip_token_span* spans, u64
     if (t->next_knobs.lanes && (rc = t->s_list.ensure(64 + (size_t)Q * 4))) return rc;
     const tq::NextArgs g{spans, Q, cap, symbols, counts, heads};
     u32* n_list = t->next_knobs.lanes ? t->s_list.as<u32>() : nullptr;
-    SA_HIP_CHECK(hipEventRecord(t->nx_ev[0], t->stream));
-    if ((rc = tq::launch_next(t->x, t->stream, t->next_knobs, g, n_list ? n_list + 16 : nullptr, n_list))) return rc;
-    SA_HIP_CHECK(hipEventRecord(t->nx_ev[1], t->stream));
-    t->nx_pending = true;
-    t->nx_q = t->s_last = Q;
+    if ((rc = t->tm_nx.begin(t->stream)) || (rc = tq::launch_next(t->x, t->stream, t->next_knobs, g, n_list ? n_list + 16 : nullptr, n_list)) ||
+        (rc = t->tm_nx.end(t->stream, Q))) return rc;
+    t->s_last = Q;
     t->nx_lanes = t->next_knobs.lanes;
+    return 0;
+}
+
+// a host batch of contexts into staging buffers (of a handle or of a shard set): the symbols [0, offsets[Q]) are staged, nothing beyond
+// them is read
+int token_upload(DevBuf& pat, DevBuf& off, hipStream_t stream, const int32_t* patterns, const uint64_t* offsets, u64 Q) {
+    int rc;
+    const u64 total = offsets[Q];
+    if ((rc = pat.ensure((size_t)total * 4 + 64)) || (rc = off.ensure((size_t)(Q + 1) * 8))) return rc;
+    if (total) SA_HIP_CHECK(hipMemcpyAsync(pat.p, patterns, (size_t)total * 4, hipMemcpyHostToDevice, stream));
+    SA_HIP_CHECK(hipMemcpyAsync(off.p, offsets, (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, stream));
     return 0;
 }
 
@@ -140,31 +130,26 @@ int token_launch_next(sa_hip_token_index* t, const sa_hip_token_span* spans, u64
 int token_stage_spans(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, u64 Q, int mode, u32 max_length,
                       int need_next) {
     int rc;
-    const u64 total = offsets[Q];
-    if ((rc = t->q_pat.ensure((size_t)total * 4 + 64)) || (rc = t->q_off.ensure((size_t)(Q + 1) * 8)) ||
-        (rc = t->s_spans.ensure((size_t)Q * sizeof(sa_hip_token_span)))) return rc;
-    if (total) SA_HIP_CHECK(hipMemcpyAsync(t->q_pat.p, patterns, (size_t)total * 4, hipMemcpyHostToDevice, t->stream));
-    SA_HIP_CHECK(hipMemcpyAsync(t->q_off.p, offsets, (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, t->stream));
+    if ((rc = t->s_spans.ensure((size_t)Q * sizeof(sa_hip_token_span))) || (rc = token_upload(t->q_pat, t->q_off, t->stream, patterns, offsets, Q))) return rc;
     return token_launch_spans(t, t->q_pat.as<int32_t>(), t->q_off.as<u64>(), Q, mode, max_length, need_next, t->s_spans.as<sa_hip_token_span>());
 }
 
 // next symbols of the spans in s_spans to the host; only the written entries of a row are copied out
-int token_stage_next(sa_hip_token_index* t, u64 Q, u32 cap, int32_t* symbols, u32* counts, sa_hip_token_next* heads) {
+int token_stage_next(sa_hip_token_index* t, const char* who, u64 Q, u32 cap, int32_t* symbols, u32* counts, sa_hip_token_next* heads) {
     int rc;
     const size_t cells = (size_t)Q * cap;
     if ((rc = t->s_sym.ensure(cells * 4)) || (rc = t->s_cnt.ensure(cells * 4)) || (rc = t->s_heads.ensure((size_t)Q * sizeof(sa_hip_token_next)))) return rc;
     if ((rc = token_launch_next(t, t->s_spans.as<sa_hip_token_span>(), Q, cap, t->s_sym.as<int32_t>(), t->s_cnt.as<u32>(), t->s_heads.as<sa_hip_token_next>()))) return rc;
-    std::vector<u32> hs, hc;
-    try { hs.resize(cells); hc.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, "sa_hip_token_index_next_batch", "host allocation"); }
+    std::vector<int32_t> hs;
+    std::vector<u32> hc;
+    try { hs.resize(cells); hc.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
     SA_HIP_CHECK(hipMemcpyAsync(heads, t->s_heads.p, (size_t)Q * sizeof(sa_hip_token_next), hipMemcpyDeviceToHost, t->stream));
     SA_HIP_CHECK(hipMemcpyAsync(hs.data(), t->s_sym.p, cells * 4, hipMemcpyDeviceToHost, t->stream));
     SA_HIP_CHECK(hipMemcpyAsync(hc.data(), t->s_cnt.p, cells * 4, hipMemcpyDeviceToHost, t->stream));
     SA_HIP_CHECK(hipStreamSynchronize(t->stream));
-    for (u64 i = 0; i < Q; ++i) {
-        const size_t w = heads[i].written < cap ? heads[i].written : cap;
-        memcpy(symbols + i * cap, hs.data() + i * cap, w * 4);
-        memcpy(counts + i * cap, hc.data() + i * cap, w * 4);
-    }
+    const StridedLen written{&heads[0].written, sizeof heads[0]};
+    copy_written_rows(symbols, hs.data(), Q, cap, written);
+    copy_written_rows(counts, hc.data(), Q, cap, written);
     return 0;
 }
 
@@ -185,15 +170,7 @@ void sa_hip_token_index_destroy(sa_hip_token_index* t) {
     t->a_goff.release(); t->a_cnt.release(); t->a_wr.release();
     if (t->a_goff_pin) (void)hipHostFree(t->a_goff_pin);
     if (t->a_copied) (void)hipEventDestroy(t->a_copied);
-    for (int j = 0; j < 2; ++j) {
-        if (t->q_ev[j]) (void)hipEventDestroy(t->q_ev[j]);
-        if (t->sp_ev[j]) (void)hipEventDestroy(t->sp_ev[j]);
-        if (t->nx_ev[j]) (void)hipEventDestroy(t->nx_ev[j]);
-        if (t->lc_ev[j]) (void)hipEventDestroy(t->lc_ev[j]);
-        if (t->dc_ev[j]) (void)hipEventDestroy(t->dc_ev[j]);
-        if (t->tf_ev[j]) (void)hipEventDestroy(t->tf_ev[j]);
-        if (t->al_ev[j]) (void)hipEventDestroy(t->al_ev[j]);
-    }
+    for (LaunchTimer* w : t->timers()) w->destroy();
     if (t->stream) (void)hipStreamDestroy(t->stream);
     delete t;
 }
@@ -263,15 +240,11 @@ int sa_hip_token_index_query_batch(sa_hip_token_index* t, const int32_t* pattern
     if (!t) return fail(SA_HIP_EINVAL, who, "NULL handle");
     if (Q == 0) return 0;
     if (!offsets || !out) return fail(SA_HIP_EINVAL, who, "NULL argument");
-    for (u64 i = 0; i < Q; ++i) if (offsets[i + 1] < offsets[i]) return fail(SA_HIP_EINVAL, who, "offsets descend");
-    const u64 total = offsets[Q];   // symbols [0, offsets[Q]) are staged, nothing beyond them is read
-    if (!patterns && total) return fail(SA_HIP_EINVAL, who, "NULL patterns");
-    std::lock_guard<std::mutex> g(t->mu);
-    int rc = set_device(t->device);
+    int rc = token_offsets_args(who, patterns, offsets, Q);
     if (rc) return rc;
-    if ((rc = t->q_pat.ensure((size_t)total * 4 + 64)) || (rc = t->q_off.ensure((size_t)(Q + 1) * 8)) || (rc = t->q_out.ensure((size_t)Q * 8))) return rc;
-    if (total) SA_HIP_CHECK(hipMemcpyAsync(t->q_pat.p, patterns, (size_t)total * 4, hipMemcpyHostToDevice, t->stream));
-    SA_HIP_CHECK(hipMemcpyAsync(t->q_off.p, offsets, (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, t->stream));
+    std::lock_guard<std::mutex> g(t->mu);
+    if ((rc = set_device(t->device))) return rc;
+    if ((rc = t->q_out.ensure((size_t)Q * 8)) || (rc = token_upload(t->q_pat, t->q_off, t->stream, patterns, offsets, Q))) return rc;
     if ((rc = token_launch(t, t->q_pat.as<int32_t>(), t->q_off.as<u64>(), Q, t->q_out.as<sa_hip_pair_u32>()))) return rc;
     SA_HIP_CHECK(hipMemcpyAsync(out, t->q_out.p, (size_t)Q * 8, hipMemcpyDeviceToHost, t->stream));
     SA_HIP_CHECK(hipStreamSynchronize(t->stream));
@@ -307,14 +280,9 @@ int sa_hip_token_index_info(const sa_hip_token_index* ct, sa_hip_token_info* out
     if (!ct || !out) return fail(SA_HIP_EINVAL, "sa_hip_token_index_info", "NULL argument");
     sa_hip_token_index* t = const_cast<sa_hip_token_index*>(ct);
     std::lock_guard<std::mutex> g(t->mu);
-    if (t->q_pending) {
+    if (t->tm_q.pending) {
         int rc = set_device(t->device);
-        if (rc) return rc;
-        float ms = 0.f;
-        SA_HIP_CHECK(hipEventSynchronize(t->q_ev[1]));
-        SA_HIP_CHECK(hipEventElapsedTime(&ms, t->q_ev[0], t->q_ev[1]));
-        t->q_ms = ms;
-        t->q_pending = false;
+        if (rc || (rc = t->tm_q.resolve())) return rc;
     }
     memset(out, 0, sizeof *out);
     out->n = t->x.n;
@@ -324,8 +292,8 @@ int sa_hip_token_index_info(const sa_hip_token_index* ct, sa_hip_token_info* out
     out->key_bytes = t->x.key_bytes;
     out->last_rank = t->x.last_rank;
     out->prepare_ms = t->x.prepare_ms;
-    out->q = t->q_last;
-    out->kernel_ms = t->q_ms;
+    out->q = t->tm_q.q;
+    out->kernel_ms = t->tm_q.ms;
     return 0;
 }
 
@@ -386,7 +354,7 @@ int sa_hip_token_index_next_batch(sa_hip_token_index* t, const int32_t* patterns
     if ((rc = set_device(t->device))) return rc;
     if ((rc = token_stage_spans(t, patterns, offsets, Q, mode, max_length, need_next))) return rc;
     if (spans) SA_HIP_CHECK(hipMemcpyAsync(spans, t->s_spans.p, (size_t)Q * sizeof(sa_hip_token_span), hipMemcpyDeviceToHost, t->stream));
-    return token_stage_next(t, Q, cap, symbols, counts, heads);
+    return token_stage_next(t, who, Q, cap, symbols, counts, heads);
 }
 
 int sa_hip_token_index_next_of_spans(sa_hip_token_index* t, const sa_hip_token_span* spans, uint64_t Q, uint32_t cap, int32_t* symbols,
@@ -402,41 +370,31 @@ int sa_hip_token_index_next_of_spans(sa_hip_token_index* t, const sa_hip_token_s
     if ((rc = set_device(t->device))) return rc;
     if ((rc = t->s_spans.ensure((size_t)Q * sizeof(sa_hip_token_span)))) return rc;
     SA_HIP_CHECK(hipMemcpyAsync(t->s_spans.p, spans, (size_t)Q * sizeof(sa_hip_token_span), hipMemcpyHostToDevice, t->stream));
-    return token_stage_next(t, Q, cap, symbols, counts, heads);
+    return token_stage_next(t, who, Q, cap, symbols, counts, heads);
 }
 
 int sa_hip_token_index_next_info(const sa_hip_token_index* ct, sa_hip_token_next_info* out) {
     if (!ct || !out) return fail(SA_HIP_EINVAL, "sa_hip_token_index_next_info", "NULL argument");
     sa_hip_token_index* t = const_cast<sa_hip_token_index*>(ct);
     std::lock_guard<std::mutex> g(t->mu);
-    if (t->sp_pending || t->nx_pending) {
+    if (t->tm_sp.pending || t->tm_nx.pending) {
         int rc = set_device(t->device);
-        if (rc) return rc;
-        float ms = 0.f;
-        if (t->sp_pending) {
-            SA_HIP_CHECK(hipEventSynchronize(t->sp_ev[1]));
-            SA_HIP_CHECK(hipEventElapsedTime(&ms, t->sp_ev[0], t->sp_ev[1]));
-            t->sp_ms = ms;
-            t->sp_pending = false;
-        }
-        if (t->nx_pending) {
-            SA_HIP_CHECK(hipEventSynchronize(t->nx_ev[1]));
-            SA_HIP_CHECK(hipEventElapsedTime(&ms, t->nx_ev[0], t->nx_ev[1]));
-            t->nx_ms = ms;
+        if (rc || (rc = t->tm_sp.resolve())) return rc;
+        if (t->tm_nx.pending) {
             u32 left = 0;   // the list's length: the spans the lane form left to the wave form
             if (t->nx_lanes) {
                 SA_HIP_CHECK(hipMemcpyAsync(&left, t->s_list.p, sizeof left, hipMemcpyDeviceToHost, t->stream));
                 SA_HIP_CHECK(hipStreamSynchronize(t->stream));
             }
-            t->nx_wave_spans = t->nx_lanes ? (u64)left : t->nx_q;
-            t->nx_lane_spans = t->nx_q - t->nx_wave_spans;
-            t->nx_pending = false;
+            if ((rc = t->tm_nx.resolve())) return rc;
+            t->nx_wave_spans = t->nx_lanes ? (u64)left : t->tm_nx.q;
+            t->nx_lane_spans = t->tm_nx.q - t->nx_wave_spans;
         }
     }
     memset(out, 0, sizeof *out);
     out->q = t->s_last;
-    out->spans_ms = t->sp_ms;
-    out->next_ms = t->nx_ms;
+    out->spans_ms = t->tm_sp.ms;
+    out->next_ms = t->tm_nx.ms;
     out->lane_spans = t->nx_lane_spans;
     out->wave_spans = t->nx_wave_spans;
     return 0;

@@ -2,7 +2,9 @@
 // (include/sa_hip.h section 6e), included by sa_capi.hip behind capi_token_docs.hpp (same translation unit).  The rank-by-document
 // array and the kernels are csrc/token_all.hpp.
 // Argument checks come first and touch neither the handle nor the device; whether the handle has documents and the array is looked
-// up under its mutex, still before any HIP call.
+// up under its mutex, still before any HIP call.  The two stopwatches are LaunchTimer members of the handle (launch_timer.hpp); the
+// host doc_counts form moves the caller's rows in and the counts out with copy_written_rows (host_rows.hpp), all_batch with
+// capi_token_docs.hpp's token_rows_out.
 #pragma once
 #include "capi_token_docs.hpp"
 #include "token_all.hpp"
@@ -34,13 +36,9 @@ int token_all_args(const char* who, u64 S, const uint64_t* goff, u64 G, u32 cap)
 int token_launch_tf(sa_hip_token_index* t, const sa_hip_token_span* spans, u64 Q, u32 cap, const int32_t* docs, const void* written,
                     u64 stride, u32* counts) {
     const tq::TfArgs g{spans, Q, cap, docs, static_cast<const unsigned char*>(written), stride, counts};
-    SA_HIP_CHECK(hipEventRecord(t->tf_ev[0], t->stream));
-    const int rc = tq::launch_tf(t->x, t->docs, t->ranks, t->stream, g);
-    if (rc) return rc;
-    SA_HIP_CHECK(hipEventRecord(t->tf_ev[1], t->stream));
-    t->tf_pending = true;
-    t->tf_q = Q;
-    return 0;
+    int rc;
+    if ((rc = t->tm_tf.begin(t->stream)) || (rc = tq::launch_tf(t->x, t->docs, t->ranks, t->stream, g))) return rc;
+    return t->tm_tf.end(t->stream, Q);
 }
 
 // the checked table goes through a pinned buffer of the handle, so the caller's array is free when the call returns and the
@@ -64,12 +62,8 @@ int token_launch_all(sa_hip_token_index* t, const sa_hip_token_span* spans, cons
     SA_HIP_CHECK(hipEventRecord(t->a_copied, t->stream));
     t->a_copy_pending = true;
     const tq::AllArgs g{spans, t->a_goff.as<u32>(), G, cap, budget, docs, offs, heads};
-    SA_HIP_CHECK(hipEventRecord(t->al_ev[0], t->stream));
-    if ((rc = tq::launch_all(t->x, t->docs, t->ranks, t->stream, g))) return rc;
-    SA_HIP_CHECK(hipEventRecord(t->al_ev[1], t->stream));
-    t->al_pending = true;
-    t->al_q = G;
-    return 0;
+    if ((rc = t->tm_al.begin(t->stream)) || (rc = tq::launch_all(t->x, t->docs, t->ranks, t->stream, g))) return rc;
+    return t->tm_al.end(t->stream, G);
 }
 
 }  // namespace
@@ -113,32 +107,19 @@ int sa_hip_token_index_doc_ranks_info(const sa_hip_token_index* ct, sa_hip_token
     if (!ct || !out) return fail(SA_HIP_EINVAL, "sa_hip_token_index_doc_ranks_info", "NULL argument");
     sa_hip_token_index* t = const_cast<sa_hip_token_index*>(ct);
     std::lock_guard<std::mutex> g(t->mu);
-    if (t->tf_pending || t->al_pending) {
+    if (t->tm_tf.pending || t->tm_al.pending) {
         int rc = set_device(t->device);
-        if (rc) return rc;
-        float ms = 0.f;
-        if (t->tf_pending) {
-            SA_HIP_CHECK(hipEventSynchronize(t->tf_ev[1]));
-            SA_HIP_CHECK(hipEventElapsedTime(&ms, t->tf_ev[0], t->tf_ev[1]));
-            t->tf_ms = ms;
-            t->tf_pending = false;
-        }
-        if (t->al_pending) {
-            SA_HIP_CHECK(hipEventSynchronize(t->al_ev[1]));
-            SA_HIP_CHECK(hipEventElapsedTime(&ms, t->al_ev[0], t->al_ev[1]));
-            t->al_ms = ms;
-            t->al_pending = false;
-        }
+        if (rc || (rc = t->tm_tf.resolve()) || (rc = t->tm_al.resolve())) return rc;
     }
     memset(out, 0, sizeof *out);
     out->present = t->ranks.have ? 1u : 0u;
     out->sort_passes = t->ranks.passes;
     out->bytes = t->ranks.bytes;
     out->prepare_ms = t->ranks.prepare_ms;
-    out->counts_q = t->tf_q;
-    out->counts_ms = t->tf_ms;
-    out->all_q = t->al_q;
-    out->all_ms = t->al_ms;
+    out->counts_q = t->tm_tf.q;
+    out->counts_ms = t->tm_tf.ms;
+    out->all_q = t->tm_al.q;
+    out->all_ms = t->tm_al.ms;
     return 0;
 }
 
@@ -173,10 +154,8 @@ int sa_hip_token_index_doc_counts_batch(sa_hip_token_index* t, const int32_t* pa
     std::vector<int32_t> hd;
     std::vector<u32> hc;
     try { hd.assign(cells, 0); hc.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
-    for (u64 i = 0; i < Q; ++i) {
-        const size_t w = written ? (written[i] < cap ? written[i] : cap) : cap;
-        memcpy(hd.data() + i * cap, docs + i * cap, w * 4);
-    }
+    auto slots = [&](u64 i) { return written ? written[i] : cap; };
+    copy_written_rows(hd.data(), docs, Q, cap, slots);
     if ((rc = token_stage_spans(t, patterns, offsets, Q, mode, max_length, need_next))) return rc;
     if (spans) SA_HIP_CHECK(hipMemcpyAsync(spans, t->s_spans.p, (size_t)Q * sizeof(sa_hip_token_span), hipMemcpyDeviceToHost, t->stream));
     SA_HIP_CHECK(hipMemcpyAsync(t->d_docs.p, hd.data(), cells * 4, hipMemcpyHostToDevice, t->stream));
@@ -185,10 +164,7 @@ int sa_hip_token_index_doc_counts_batch(sa_hip_token_index* t, const int32_t* pa
                               t->a_cnt.as<u32>()))) return rc;
     SA_HIP_CHECK(hipMemcpyAsync(hc.data(), t->a_cnt.p, cells * 4, hipMemcpyDeviceToHost, t->stream));
     SA_HIP_CHECK(hipStreamSynchronize(t->stream));
-    for (u64 i = 0; i < Q; ++i) {
-        const size_t w = written ? (written[i] < cap ? written[i] : cap) : cap;
-        memcpy(counts + i * cap, hc.data() + i * cap, w * 4);
-    }
+    copy_written_rows(counts, hc.data(), Q, cap, slots);
     return 0;
 }
 

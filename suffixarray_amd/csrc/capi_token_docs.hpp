@@ -1,7 +1,8 @@
 // capi_token_docs.hpp -- the C ABI of a token index's documents (include/sa_hip.h section 6d), included by sa_capi.hip behind
 // capi_token.hpp (same translation unit).  The structures and the kernels are csrc/token_docs.hpp.
 // Argument checks come first and touch neither the handle nor the device; whether the handle has documents is looked up under its
-// mutex, still before any HIP call.
+// mutex, still before any HIP call.  The two stopwatches are LaunchTimer members of the handle (launch_timer.hpp), the contexts of a
+// host form go up through token_stage_spans, and token_rows_out copies the written rows back with copy_written_rows (host_rows.hpp).
 #pragma once
 #include "capi_token.hpp"
 #include "token_docs.hpp"
@@ -20,28 +21,20 @@ int token_has_docs(const sa_hip_token_index* t, const char* who) {
 int token_launch_locate(sa_hip_token_index* t, const sa_hip_token_span* spans, u64 Q, u32 cap, int32_t* docs, int32_t* offs,
                         sa_hip_token_locate* heads) {
     const tq::LocateArgs g{spans, Q, cap, docs, offs, heads};
-    SA_HIP_CHECK(hipEventRecord(t->lc_ev[0], t->stream));
-    const int rc = tq::launch_locate(t->x, t->docs, t->stream, g);
-    if (rc) return rc;
-    SA_HIP_CHECK(hipEventRecord(t->lc_ev[1], t->stream));
-    t->lc_pending = true;
-    t->lc_q = Q;
-    return 0;
+    int rc;
+    if ((rc = t->tm_lc.begin(t->stream)) || (rc = tq::launch_locate(t->x, t->docs, t->stream, g))) return rc;
+    return t->tm_lc.end(t->stream, Q);
 }
 
 int token_launch_docs(sa_hip_token_index* t, const sa_hip_token_span* spans, u64 Q, u32 cap, u32 budget, int32_t* docs, int32_t* offs,
                       sa_hip_token_docs* heads) {
     const tq::DocsArgs g{spans, Q, cap, budget, docs, offs, heads, t->docs.sum.as<unsigned long long>()};
-    SA_HIP_CHECK(hipEventRecord(t->dc_ev[0], t->stream));
-    const int rc = tq::launch_docs(t->x, t->docs, t->stream, g);
-    if (rc) return rc;
-    SA_HIP_CHECK(hipEventRecord(t->dc_ev[1], t->stream));
-    t->dc_pending = true;
-    t->dc_q = Q;
-    return 0;
+    int rc;
+    if ((rc = t->tm_dc.begin(t->stream)) || (rc = tq::launch_docs(t->x, t->docs, t->stream, g))) return rc;
+    return t->tm_dc.end(t->stream, Q);
 }
 
-// rows of the staged cells to the host: only the written entries of a row are copied out
+// heads and rows of the staged cells to the host: only the written entries of a row are copied out (host_rows.hpp)
 template <class Head>
 int token_rows_out(sa_hip_token_index* t, const char* who, u64 Q, u32 cap, int32_t* docs, int32_t* offs, Head* heads) {
     const size_t cells = (size_t)Q * cap;
@@ -53,11 +46,9 @@ int token_rows_out(sa_hip_token_index* t, const char* who, u64 Q, u32 cap, int32
         SA_HIP_CHECK(hipMemcpyAsync(ho.data(), t->d_offs.p, cells * 4, hipMemcpyDeviceToHost, t->stream));
     }
     SA_HIP_CHECK(hipStreamSynchronize(t->stream));
-    for (u64 i = 0; i < Q && cap; ++i) {
-        const size_t w = heads[i].written < cap ? heads[i].written : cap;
-        memcpy(docs + i * cap, hd.data() + i * cap, w * 4);
-        memcpy(offs + i * cap, ho.data() + i * cap, w * 4);
-    }
+    const StridedLen written{&heads[0].written, sizeof(Head)};
+    copy_written_rows(docs, hd.data(), Q, cap, written);
+    copy_written_rows(offs, ho.data(), Q, cap, written);
     return 0;
 }
 
@@ -106,27 +97,17 @@ int sa_hip_token_index_docs_info(const sa_hip_token_index* ct, sa_hip_token_docs
     if (!ct || !out) return fail(SA_HIP_EINVAL, "sa_hip_token_index_docs_info", "NULL argument");
     sa_hip_token_index* t = const_cast<sa_hip_token_index*>(ct);
     std::lock_guard<std::mutex> g(t->mu);
-    if (t->lc_pending || t->dc_pending) {
+    if (t->tm_lc.pending || t->tm_dc.pending) {
         int rc = set_device(t->device);
-        if (rc) return rc;
-        float ms = 0.f;
-        if (t->lc_pending) {
-            SA_HIP_CHECK(hipEventSynchronize(t->lc_ev[1]));
-            SA_HIP_CHECK(hipEventElapsedTime(&ms, t->lc_ev[0], t->lc_ev[1]));
-            t->lc_ms = ms;
-            t->lc_pending = false;
-        }
-        if (t->dc_pending) {
-            SA_HIP_CHECK(hipEventSynchronize(t->dc_ev[1]));
-            SA_HIP_CHECK(hipEventElapsedTime(&ms, t->dc_ev[0], t->dc_ev[1]));
-            t->dc_ms = ms;
+        if (rc || (rc = t->tm_lc.resolve())) return rc;
+        if (t->tm_dc.pending) {
             unsigned long long sum = 0;
             if (t->docs.sum.p) {
                 SA_HIP_CHECK(hipMemcpyAsync(&sum, t->docs.sum.p, sizeof sum, hipMemcpyDeviceToHost, t->stream));
                 SA_HIP_CHECK(hipStreamSynchronize(t->stream));
             }
+            if ((rc = t->tm_dc.resolve())) return rc;
             t->dc_examined = sum;
-            t->dc_pending = false;
         }
     }
     memset(out, 0, sizeof *out);
@@ -137,10 +118,10 @@ int sa_hip_token_index_docs_info(const sa_hip_token_index* ct, sa_hip_token_docs
     out->sort_ms = t->docs.sort_ms;
     out->pv_ms = t->docs.pv_ms;
     out->sort_passes = t->docs.passes;
-    out->locate_q = t->lc_q;
-    out->locate_ms = t->lc_ms;
-    out->docs_q = t->dc_q;
-    out->docs_ms = t->dc_ms;
+    out->locate_q = t->tm_lc.q;
+    out->locate_ms = t->tm_lc.ms;
+    out->docs_q = t->tm_dc.q;
+    out->docs_ms = t->tm_dc.ms;
     out->examined = t->dc_examined;
     return 0;
 }

@@ -1,5 +1,7 @@
 // capi_token_shards.hpp -- the C ABI of the shard set (include/sa_hip.h section 6c), included by sa_capi.hip behind capi_token.hpp
 // (same translation unit).  The kernels are csrc/token_shards.hpp; the per-shard next symbols are tq::launch_next of every shard.
+// The stopwatches, the upload of a host batch and the row copy are capi_token.hpp's; the per-chunk events of the next symbols, summed
+// into two figures, are the set's own.
 #pragma once
 #include "capi_token.hpp"
 #include "token_shards.hpp"
@@ -19,13 +21,13 @@ struct sa_hip_token_shards {
     DevBuf s_spans, s_len, s_tot;            // spans of the host forms
     DevBuf l_sym, l_cnt, l_heads, l_list;    // the per-shard lists of one chunk; l_list as sa_hip_token_index::s_list
     DevBuf o_sym, o_cnt, o_heads;            // merged output of one chunk (host form)
-    hipEvent_t r_ev[2] = {}, sp_ev[2] = {};
+    LaunchTimer tm_r, tm_sp;                 // the last ranges / spans launch
     std::vector<hipEvent_t> nx_ev;           // 3 per chunk: before the shards' launches, behind them, behind the merge
     size_t nx_used = 0;                      // events of the last next-symbol call
-    bool r_pending = false, sp_pending = false, nx_pending = false;
-    u64 q_last = 0;
+    bool nx_pending = false;
+    u64 q_last = 0;                          // contexts of the last launch of any kind
     u32 chunk_last = 0;
-    double r_ms = 0.0, sp_ms = 0.0, nx_ms = 0.0, mg_ms = 0.0;
+    double nx_ms = 0.0, mg_ms = 0.0;
 
     const tq::View* table() const { return tab.as<tq::View>(); }
 };
@@ -38,21 +40,18 @@ int shards_launch_ranges(sa_hip_token_shards* g, const int32_t* pat, const u64* 
         if ((rc = g->r_per.ensure((size_t)Q * g->S * sizeof(sa_hip_pair_u32)))) return rc;
         per = g->r_per.as<sa_hip_pair_u32>();
     }
-    SA_HIP_CHECK(hipEventRecord(g->r_ev[0], g->stream));
-    if ((rc = tq::launch_shard_ranges(g->table(), g->S, g->stream, pat, off, Q, totals, per))) return rc;
-    SA_HIP_CHECK(hipEventRecord(g->r_ev[1], g->stream));
-    g->r_pending = true;
+    if ((rc = g->tm_r.begin(g->stream)) || (rc = tq::launch_shard_ranges(g->table(), g->S, g->stream, pat, off, Q, totals, per)) ||
+        (rc = g->tm_r.end(g->stream, Q))) return rc;
     g->q_last = Q;
     return 0;
 }
 
 int shards_launch_spans(sa_hip_token_shards* g, const int32_t* pat, const u64* off, u64 Q, int mode, u32 max_length, int need_next,
                         u32* length, u64* totals, sa_hip_token_span* spans) {
-    SA_HIP_CHECK(hipEventRecord(g->sp_ev[0], g->stream));
-    const int rc = tq::launch_shard_spans(g->table(), g->S, g->max_n, g->stream, pat, off, Q, mode, max_length, need_next, length, totals, spans);
-    if (rc) return rc;
-    SA_HIP_CHECK(hipEventRecord(g->sp_ev[1], g->stream));
-    g->sp_pending = true;
+    int rc;
+    if ((rc = g->tm_sp.begin(g->stream)) ||
+        (rc = tq::launch_shard_spans(g->table(), g->S, g->max_n, g->stream, pat, off, Q, mode, max_length, need_next, length, totals, spans)) ||
+        (rc = g->tm_sp.end(g->stream, Q))) return rc;
     g->q_last = Q;
     return 0;
 }
@@ -64,16 +63,6 @@ int shards_event(sa_hip_token_shards* g, size_t k) {
         g->nx_ev.push_back(e);
     }
     SA_HIP_CHECK(hipEventRecord(g->nx_ev[k], g->stream));
-    return 0;
-}
-
-// contexts from the host into the staging buffers
-int shards_stage_contexts(sa_hip_token_shards* g, const int32_t* patterns, const uint64_t* offsets, u64 Q) {
-    int rc;
-    const u64 total = offsets[Q];
-    if ((rc = g->q_pat.ensure((size_t)total * 4 + 64)) || (rc = g->q_off.ensure((size_t)(Q + 1) * 8))) return rc;
-    if (total) SA_HIP_CHECK(hipMemcpyAsync(g->q_pat.p, patterns, (size_t)total * 4, hipMemcpyHostToDevice, g->stream));
-    SA_HIP_CHECK(hipMemcpyAsync(g->q_off.p, offsets, (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, g->stream));
     return 0;
 }
 
@@ -90,7 +79,7 @@ int shards_next(sa_hip_token_shards* g, const sa_hip_token_span* spans, u64 Q, u
     for (u32 s = 0; s < S; ++s) lanes = lanes || g->shard[s]->next_knobs.lanes;
     if ((rc = g->l_sym.ensure(cells * S * 4)) || (rc = g->l_cnt.ensure(cells * S * 4)) ||
         (rc = g->l_heads.ensure((size_t)chunk * S * sizeof(sa_hip_token_next))) || (lanes && (rc = g->l_list.ensure(64 + (size_t)chunk * 4)))) return rc;
-    std::vector<u32> hs;
+    std::vector<int32_t> hs;
     std::vector<u64> hc;
     if (to_host) {
         if ((rc = g->o_sym.ensure(cells * 4)) || (rc = g->o_cnt.ensure(cells * 8)) || (rc = g->o_heads.ensure((size_t)chunk * sizeof(sa_hip_token_shards_next)))) return rc;
@@ -124,11 +113,9 @@ int shards_next(sa_hip_token_shards* g, const sa_hip_token_span* spans, u64 Q, u
             SA_HIP_CHECK(hipMemcpyAsync(hs.data(), g->o_sym.p, (size_t)qc * cap * 4, hipMemcpyDeviceToHost, g->stream));
             SA_HIP_CHECK(hipMemcpyAsync(hc.data(), g->o_cnt.p, (size_t)qc * cap * 8, hipMemcpyDeviceToHost, g->stream));
             SA_HIP_CHECK(hipStreamSynchronize(g->stream));
-            for (u64 i = 0; i < qc; ++i) {
-                const size_t w = heads[c0 + i].written < cap ? heads[c0 + i].written : cap;
-                memcpy(symbols + (c0 + i) * cap, hs.data() + i * cap, w * 4);
-                memcpy(counts + (c0 + i) * cap, hc.data() + i * cap, w * 8);
-            }
+            const StridedLen written{&heads[c0].written, sizeof heads[0]};
+            copy_written_rows(symbols + c0 * cap, hs.data(), qc, cap, written);
+            copy_written_rows(counts + c0 * cap, hc.data(), qc, cap, written);
         }
     }
     g->q_last = Q;
@@ -149,10 +136,7 @@ void sa_hip_token_shards_destroy(sa_hip_token_shards* g) {
     g->s_spans.release(); g->s_len.release(); g->s_tot.release();
     g->l_sym.release(); g->l_cnt.release(); g->l_heads.release(); g->l_list.release();
     g->o_sym.release(); g->o_cnt.release(); g->o_heads.release();
-    for (int j = 0; j < 2; ++j) {
-        if (g->r_ev[j]) (void)hipEventDestroy(g->r_ev[j]);
-        if (g->sp_ev[j]) (void)hipEventDestroy(g->sp_ev[j]);
-    }
+    g->tm_r.destroy(); g->tm_sp.destroy();
     for (hipEvent_t e : g->nx_ev) (void)hipEventDestroy(e);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
@@ -177,10 +161,8 @@ int sa_hip_token_shards_create(sa_hip_token_shards** out, sa_hip_token_index* co
     if (const char* e = diag_env("SA_HIP_TOKEN_SHARD_CHUNK")) g->chunk_knob = strtoull(e, nullptr, 10);
     auto run = [&]() -> int {
         SA_HIP_CHECK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-        for (int j = 0; j < 2; ++j) {
-            SA_HIP_CHECK(hipEventCreate(&g->r_ev[j]));
-            SA_HIP_CHECK(hipEventCreate(&g->sp_ev[j]));
-        }
+        SA_HIP_CHECK(g->tm_r.create());
+        SA_HIP_CHECK(g->tm_sp.create());
         tq::View v[tq::SHARDS_MAX];
         for (u32 s = 0; s < S; ++s) {
             std::lock_guard<std::mutex> lk(shards[s]->mu);
@@ -220,23 +202,11 @@ int sa_hip_token_shards_info(const sa_hip_token_shards* cg, sa_hip_token_shards_
     if (!cg || !out) return fail(SA_HIP_EINVAL, "sa_hip_token_shards_info", "NULL argument");
     sa_hip_token_shards* g = const_cast<sa_hip_token_shards*>(cg);
     std::lock_guard<std::mutex> lk(g->mu);
-    if (g->r_pending || g->sp_pending || g->nx_pending) {
+    if (g->tm_r.pending || g->tm_sp.pending || g->nx_pending) {
         int rc = set_device(g->device);
-        if (rc) return rc;
-        float ms = 0.f;
-        if (g->r_pending) {
-            SA_HIP_CHECK(hipEventSynchronize(g->r_ev[1]));
-            SA_HIP_CHECK(hipEventElapsedTime(&ms, g->r_ev[0], g->r_ev[1]));
-            g->r_ms = ms;
-            g->r_pending = false;
-        }
-        if (g->sp_pending) {
-            SA_HIP_CHECK(hipEventSynchronize(g->sp_ev[1]));
-            SA_HIP_CHECK(hipEventElapsedTime(&ms, g->sp_ev[0], g->sp_ev[1]));
-            g->sp_ms = ms;
-            g->sp_pending = false;
-        }
+        if (rc || (rc = g->tm_r.resolve()) || (rc = g->tm_sp.resolve())) return rc;
         if (g->nx_pending) {
+            float ms = 0.f;
             SA_HIP_CHECK(hipEventSynchronize(g->nx_ev[g->nx_used - 1]));
             g->nx_ms = g->mg_ms = 0.0;
             for (size_t k = 0; k + 3 <= g->nx_used; k += 3) {
@@ -253,8 +223,8 @@ int sa_hip_token_shards_info(const sa_hip_token_shards* cg, sa_hip_token_shards_
     out->chunk = g->chunk_last;
     out->tokens = g->tokens;
     out->q = g->q_last;
-    out->ranges_ms = g->r_ms;
-    out->spans_ms = g->sp_ms;
+    out->ranges_ms = g->tm_r.ms;
+    out->spans_ms = g->tm_sp.ms;
     out->next_ms = g->nx_ms;
     out->merge_ms = g->mg_ms;
     return 0;
@@ -286,7 +256,7 @@ int sa_hip_token_shards_query_batch(sa_hip_token_shards* g, const int32_t* patte
     std::lock_guard<std::mutex> lk(g->mu);
     if ((rc = set_device(g->device))) return rc;
     const size_t per_bytes = (size_t)Q * g->S * sizeof(sa_hip_pair_u32);
-    if ((rc = shards_stage_contexts(g, patterns, offsets, Q)) || (rc = g->r_per.ensure(per_bytes)) || (rc = g->r_tot.ensure((size_t)Q * 8))) return rc;
+    if ((rc = token_upload(g->q_pat, g->q_off, g->stream, patterns, offsets, Q)) || (rc = g->r_per.ensure(per_bytes)) || (rc = g->r_tot.ensure((size_t)Q * 8))) return rc;
     if ((rc = shards_launch_ranges(g, g->q_pat.as<int32_t>(), g->q_off.as<u64>(), Q, g->r_tot.as<u64>(), g->r_per.as<sa_hip_pair_u32>()))) return rc;
     SA_HIP_CHECK(hipMemcpyAsync(totals, g->r_tot.p, (size_t)Q * 8, hipMemcpyDeviceToHost, g->stream));
     if (per_shard) SA_HIP_CHECK(hipMemcpyAsync(per_shard, g->r_per.p, per_bytes, hipMemcpyDeviceToHost, g->stream));
@@ -320,7 +290,7 @@ int sa_hip_token_shards_spans_batch(sa_hip_token_shards* g, const int32_t* patte
     std::lock_guard<std::mutex> lk(g->mu);
     if ((rc = set_device(g->device))) return rc;
     const size_t span_bytes = (size_t)Q * g->S * sizeof(sa_hip_token_span);
-    if ((rc = shards_stage_contexts(g, patterns, offsets, Q)) || (rc = g->s_spans.ensure(span_bytes)) || (rc = g->s_len.ensure((size_t)Q * 4)) ||
+    if ((rc = token_upload(g->q_pat, g->q_off, g->stream, patterns, offsets, Q)) || (rc = g->s_spans.ensure(span_bytes)) || (rc = g->s_len.ensure((size_t)Q * 4)) ||
         (rc = g->s_tot.ensure((size_t)Q * 8))) return rc;
     if ((rc = shards_launch_spans(g, g->q_pat.as<int32_t>(), g->q_off.as<u64>(), Q, mode, max_length, need_next, g->s_len.as<u32>(), g->s_tot.as<u64>(),
                                   g->s_spans.as<sa_hip_token_span>()))) return rc;
@@ -358,7 +328,7 @@ int sa_hip_token_shards_next_batch(sa_hip_token_shards* g, const int32_t* patter
     std::lock_guard<std::mutex> lk(g->mu);
     if ((rc = set_device(g->device))) return rc;
     const size_t span_bytes = (size_t)Q * g->S * sizeof(sa_hip_token_span);
-    if ((rc = shards_stage_contexts(g, patterns, offsets, Q)) || (rc = g->s_spans.ensure(span_bytes)) || (rc = g->s_len.ensure((size_t)Q * 4)) ||
+    if ((rc = token_upload(g->q_pat, g->q_off, g->stream, patterns, offsets, Q)) || (rc = g->s_spans.ensure(span_bytes)) || (rc = g->s_len.ensure((size_t)Q * 4)) ||
         (rc = g->s_tot.ensure((size_t)Q * 8))) return rc;
     if ((rc = shards_launch_spans(g, g->q_pat.as<int32_t>(), g->q_off.as<u64>(), Q, mode, max_length, need_next, g->s_len.as<u32>(), g->s_tot.as<u64>(),
                                   g->s_spans.as<sa_hip_token_span>()))) return rc;

@@ -4,8 +4,8 @@
 //
 // This file: the index handle with its build, query, record-retrieval, replica, multi-GPU, CSV and on-disk entry points.
 // capi_dropins.hpp (included below, same translation unit): the libsais- / engine-call-compatible entry points, their device
-// forms and the process-level workspace they share.  capi_token.hpp, capi_token_docs.hpp and capi_token_shards.hpp (included at the end): the token
-// index, its documents, and sets of token indexes.
+// forms and the process-level workspace they share.  capi_token.hpp, capi_token_docs.hpp, capi_token_all.hpp and capi_token_shards.hpp (included
+// at the end): the token index, its documents, per-document counts and AND groups, and sets of token indexes.
 #include <exception>
 #include <mutex>
 #include <new>

@@ -45,7 +45,7 @@ def make_documents(t, seed=3):
     """document starts of Zipf-ish lengths (16 tokens times a Zipf(1.3) draw, at most a million); t gets SEP at every document's end"""
     rng = np.random.default_rng(seed)
     n = t.size
-    lens = np.minimum(rng.zipf(1.3, max(n // 16, 1)) * 16, 1_000_000).astype(np.int64)
+    lens = np.minimum(rng.zipf(1.3, max(n // 16, 1)), 1_000_000 // 16).astype(np.int64) * 16      # (cut first: 16 times a large draw wraps)
     ends = np.cumsum(lens)
     ends = ends[ends < n]
     starts = np.concatenate([[0], ends]).astype(np.int32)

@@ -1,5 +1,5 @@
 // host_sanitize.cpp -- the host-only code of libsa_hip (CSV extractor threads, row copying, record retrieval, the
-// opt-in host index) under AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU (sanitizers are not available
+// opt-in host index, the token index's copy of written rows) under AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU (sanitizers are not available
 // on the GPU pool, and this code never touches the device):
 //     g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -D__HIP_PLATFORM_AMD__ \
 //         -I/opt/rocm/include -Isuffixarray_amd/csrc tools/host_sanitize.cpp -o /tmp/host_sanitize -lpthread
@@ -12,6 +12,7 @@
 #include "csv_ingest.hpp"
 #include "records.hpp"
 #include "host_index.hpp"
+#include "host_rows.hpp"
 
 using namespace sa;
 
@@ -100,10 +101,43 @@ static int check_host_index() {
     return 0;
 }
 
+// copy_written_rows with Q = 3, cap = 4: a destination of sentinels between two guard cells; row lengths none, exactly cap and
+// beyond cap (clamped), once from a callable and once from an array of 16-byte heads; then cap = 0
+template <class Cell>
+static int check_rows() {
+    const u64 Q = 3;
+    const u32 cap = 4;
+    const Cell sentinel = (Cell)0x5A5A5A5A5A5A5A5Aull;
+    struct Head { u32 written, other[3]; };
+    static_assert(sizeof(Head) == 16, "the stride of the heads[i].written use");
+    const Head heads[Q] = {{0, {7, 7, 7}}, {4, {7, 7, 7}}, {9, {7, 7, 7}}};
+    std::vector<Cell> src(Q * cap);
+    for (size_t j = 0; j < src.size(); ++j) src[j] = (Cell)(100 + j);
+    auto holds = [&](const std::vector<Cell>& dst, bool copied) {
+        if (dst.front() != sentinel || dst.back() != sentinel) return false;
+        for (u64 i = 0; i < Q; ++i)
+            for (u32 j = 0; j < cap; ++j) {
+                const bool in = copied && j < (heads[i].written < cap ? heads[i].written : cap);
+                if (dst[1 + i * cap + j] != (in ? src[i * cap + j] : sentinel)) return false;
+            }
+        return true;
+    };
+    std::vector<Cell> a(Q * cap + 2, sentinel), b(a), c(a);
+    copy_written_rows(a.data() + 1, src.data(), Q, cap, [&](u64 i) { return heads[i].written; });
+    REQUIRE(holds(a, true));
+    copy_written_rows(b.data() + 1, src.data(), Q, cap, StridedLen{&heads[0].written, sizeof(Head)});
+    REQUIRE(holds(b, true));
+    copy_written_rows(c.data() + 1, src.data(), Q, 0, StridedLen{&heads[0].written, sizeof(Head)});
+    copy_written_rows(static_cast<Cell*>(nullptr), static_cast<const Cell*>(nullptr), Q, 0, [](u64) { return 9u; });
+    REQUIRE(holds(c, false));
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const char* dir = argc > 1 ? argv[1] : "/tmp";
     if (check_csv(dir)) return 1;
     if (check_host_index()) return 1;
+    if (check_rows<int32_t>() || check_rows<u64>()) return 1;
     printf("host_sanitize: clean\n");
     return 0;
 }
