@@ -920,6 +920,67 @@ int sa_hip_token_index_all_batch(sa_hip_token_index* t, const int32_t* patterns,
                                  uint32_t cap, uint32_t budget, sa_hip_token_span* spans, int32_t* docs, int32_t* offs,
                                  sa_hip_token_all* heads);
 
+/* (6f) matching statistics (csrc/token_match.hpp, csrc/capi_token_match.hpp): which parts of a query text stand verbatim in the
+ * corpus.  For every position of the text the longest prefix of what follows that the corpus holds, with its range and count, and
+ * per query document the maximal matches, the longest one and the tokens they cover.  All results are exact.
+ *
+ * A batch is Q query documents in the usual layout: document d is patterns[offsets[d] .. offsets[d + 1]), the offsets are
+ * non-decreasing.  A position is a flat index j into patterns; total = offsets[Q].  With M = max_length (0: no cap) and avail(j) =
+ * the tokens from j to the end of j's document:
+ *   ms(j)   the largest L <= min(avail(j), M, n) such that patterns[j .. j + L) occurs in the text;
+ *   match   spans[j] = {first, count, length = ms(j), ended} of that prefix: exactly what sa_hip_token_index_spans_batch answers in
+ *           mode 0 for it.  L = 0 gives {0, n, 0, 0}; with n == 0 every match is {0, 0, 0, 0}; a position outside every document
+ *           (j < offsets[0]) gets {0, 0, 0, 0};
+ *   end(j)  j + ms(j); it never passes the end of j's document and is non-decreasing in j.
+ * A match of length >= 1 is maximal when no other position's match of the same document contains it, which holds iff
+ * end(j) > end(j - 1).  Per document the docs step gives the maximal matches of at least min_length (>= 1) symbols in position
+ * order: positions[d * cap + k] = the offset inside the document, out_spans[d * cap + k] = its match, for k < written; and the head
+ * {written = min(maximal, cap), maximal = how many there are, longest = the largest ms of the document whatever min_length is,
+ * covered = the tokens of the document that lie inside a match of at least min_length symbols}.  Cells beyond `written` are not
+ * written; cap == 0 computes the heads alone, positions and out_spans may then be NULL and are never touched; an empty document has
+ * a head of zeros.
+ *
+ * Cost: a position is one range search, two comparisons against its neighbours in suffix order and, where 1 <= ms(j) < the capped
+ * length, a second range search; a search step compares as many symbols as its suffix shares with the text, so a text copied
+ * verbatim from the corpus costs about m * min(m, M) * log2 n symbol reads for its m positions.  max_length is the caller's lever.
+ *
+ * Errors returned as -1 before any HIP call: a NULL handle or a NULL required pointer, min_length == 0, total >= 2^31,
+ * Q * cap >= 2^31, and in the host forms (which compute total) descending offsets; Q == 0 is a no-op returning 0; no usable device
+ * -3.  The device forms are asynchronous on the handle's stream until sa_hip_token_index_sync and chain without a host trip (the
+ * span output of the first is the span input of the second); they trust nothing: every loop is bounded, a document's end is
+ * clamped to total, a span's length to what is left of its document, and an array that is not the suffix array gives unspecified
+ * answers.  The host forms stage through buffers of the handle and copy out only the written cells of a row. */
+typedef struct sa_hip_token_match_head {
+    uint32_t written;    /* maximal matches written for this document: min(maximal, cap)        */
+    uint32_t maximal;    /* maximal matches of at least min_length symbols                       */
+    uint32_t longest;    /* the largest ms(j) of the document                                    */
+    uint32_t covered;    /* tokens inside a match of at least min_length symbols                 */
+} sa_hip_token_match_head;
+
+typedef struct sa_hip_token_match_info {
+    uint64_t q;            /* documents of the last launch of either kind                        */
+    uint64_t positions;    /* positions of the last match launch                                 */
+    double   match_ms;     /* HIP-event time of the last match launch (the call waits for it)    */
+    double   docs_ms;      /* ... of the last docs launch                                        */
+} sa_hip_token_match_info;
+
+/* spans_dev: sa_hip_token_span[total], total = offsets[Q], index = position in patterns. */
+int sa_hip_token_index_match_batch_device(sa_hip_token_index* t, const void* patterns_dev, const void* offsets_dev, uint64_t Q,
+                                          uint64_t total, uint32_t max_length, void* spans_dev);
+/* spans_dev as the call above writes them; positions_dev: uint32[Q * cap] and out_spans_dev: sa_hip_token_span[Q * cap] (may be
+ * NULL when cap == 0); heads_dev: sa_hip_token_match_head[Q]. */
+int sa_hip_token_index_match_docs_batch_device(sa_hip_token_index* t, const void* spans_dev, const void* offsets_dev, uint64_t Q,
+                                               uint32_t min_length, uint32_t cap, void* positions_dev, void* out_spans_dev,
+                                               void* heads_dev);
+/* Host pointers; spans[offsets[Q]] out. */
+int sa_hip_token_index_match_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                   uint32_t max_length, sa_hip_token_span* spans);
+/* Both steps from host documents: spans[offsets[Q]] (may be NULL), positions, out_spans and heads[Q] out. */
+int sa_hip_token_index_match_docs_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                        uint32_t max_length, uint32_t min_length, uint32_t cap, sa_hip_token_span* spans,
+                                        uint32_t* positions, sa_hip_token_span* out_spans, sa_hip_token_match_head* heads);
+int sa_hip_token_index_match_info(const sa_hip_token_index* t, sa_hip_token_match_info* out);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 
 /* Per-build statistics of the last build on this handle (roofline accounting). */

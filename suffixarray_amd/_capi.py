@@ -19,6 +19,7 @@ LOCATE_DTYPE = np.dtype([("written", "<u4"), ("count", "<u4")])                 
 DOCS_DTYPE = np.dtype([("written", "<u4"), ("examined", "<u4"), ("distinct", "<u4"), ("count", "<u4")])     # sa_hip_token_docs
 ALL_DTYPE = np.dtype([("written", "<u4"), ("examined", "<u4"), ("matched", "<u4"), ("candidates", "<u4"), ("driver", "<u4"),
                       ("count", "<u4"), ("reserved", "<u4", (2,))])                                           # sa_hip_token_all
+MATCH_HEAD_DTYPE = np.dtype([("written", "<u4"), ("maximal", "<u4"), ("longest", "<u4"), ("covered", "<u4")])  # sa_hip_token_match_head
 TOKEN_ALL_MAX = 16                                                                                          # SA_HIP_TOKEN_ALL_MAX
 SHARDS_NEXT_DTYPE = np.dtype([("written", "<u4"), ("length", "<u4"), ("covered", "<u8"), ("total", "<u8")])  # sa_hip_token_shards_next
 SHARDS_MAX = 64
@@ -50,6 +51,8 @@ EXPORTS = [
     "sa_hip_token_index_prepare_doc_ranks", "sa_hip_token_index_get_doc_ranks", "sa_hip_token_index_doc_ranks_info",
     "sa_hip_token_index_doc_counts_batch_device", "sa_hip_token_index_doc_counts_batch", "sa_hip_token_index_all_batch_device",
     "sa_hip_token_index_all_batch",
+    "sa_hip_token_index_match_batch_device", "sa_hip_token_index_match_docs_batch_device", "sa_hip_token_index_match_batch",
+    "sa_hip_token_index_match_docs_batch", "sa_hip_token_index_match_info",
     "sa_hip_token_shards_create", "sa_hip_token_shards_destroy", "sa_hip_token_shards_shard", "sa_hip_token_shards_sync",
     "sa_hip_token_shards_info", "sa_hip_token_shards_query_batch", "sa_hip_token_shards_query_batch_device",
     "sa_hip_token_shards_spans_batch", "sa_hip_token_shards_spans_batch_device", "sa_hip_token_shards_next_batch",
@@ -220,6 +223,18 @@ class TokenDocRanksInfo(C.Structure):
     """sa_hip_token_doc_ranks_info: the rank-by-document array of a token index and its last doc_counts and all launches."""
     _fields_ = [("present", C.c_uint32), ("sort_passes", C.c_uint32), ("bytes", C.c_uint64), ("prepare_ms", C.c_double),
                 ("counts_q", C.c_uint64), ("counts_ms", C.c_double), ("all_q", C.c_uint64), ("all_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenMatchHead(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("maximal", C.c_uint32), ("longest", C.c_uint32), ("covered", C.c_uint32)]
+
+
+class TokenMatchInfo(C.Structure):
+    """sa_hip_token_match_info: the last match and match-docs launches of a token index."""
+    _fields_ = [("q", C.c_uint64), ("positions", C.c_uint64), ("match_ms", C.c_double), ("docs_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -537,6 +552,16 @@ def lib():
     L.sa_hip_token_index_all_batch_device.argtypes = [vp, vp, u64, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.sa_hip_token_index_all_batch.restype = C.c_int
     L.sa_hip_token_index_all_batch.argtypes = [vp, vp, vp, u64, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_index_match_batch_device.restype = C.c_int
+    L.sa_hip_token_index_match_batch_device.argtypes = [vp, vp, vp, u64, u64, C.c_uint32, vp]
+    L.sa_hip_token_index_match_docs_batch_device.restype = C.c_int
+    L.sa_hip_token_index_match_docs_batch_device.argtypes = [vp, vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_index_match_batch.restype = C.c_int
+    L.sa_hip_token_index_match_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, vp]
+    L.sa_hip_token_index_match_docs_batch.restype = C.c_int
+    L.sa_hip_token_index_match_docs_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_index_match_info.restype = C.c_int
+    L.sa_hip_token_index_match_info.argtypes = [vp, C.POINTER(TokenMatchInfo)]
     L.sa_hip_token_shards_create.restype = C.c_int
     L.sa_hip_token_shards_create.argtypes = [C.POINTER(vp), vp, C.c_uint32]
     L.sa_hip_token_shards_destroy.restype = None
@@ -1450,6 +1475,45 @@ class TokenIndex(_TokenHandle):
         self._call(g, self._lib.sa_hip_token_index_all_batch, _ptr(buf), _ptr(off), s, go.ctypes.data, g, int(mode), int(max_length),
                    int(bool(need_next)), cap, int(budget), _ptr(spans), _ptr(docs), _ptr(offs), _ptr(heads))
         return {"spans": spans[:s], "docs": docs[:g], "offsets": offs[:g], "heads": heads[:g]}
+
+    def match_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, total, max_length, spans_dev_ptr):
+        """The match of every one of the `total` = offsets[q] positions of q device documents (max_length 0: no cap) into
+        spans_dev_ptr[total]; asynchronous on the handle's stream until sync()."""
+        check(self._lib.sa_hip_token_index_match_batch_device(self._h, patterns_dev_ptr, offsets_dev_ptr, q, int(total), int(max_length),
+                                                              spans_dev_ptr))
+
+    def match_docs_batch_device(self, spans_dev_ptr, offsets_dev_ptr, q, min_length, cap, positions_dev_ptr, out_spans_dev_ptr, heads_dev_ptr):
+        """The maximal matches of at least min_length symbols of q device documents from the spans match_batch_device wrote (cap 0:
+        heads only, positions and out_spans may be None); asynchronous until sync()."""
+        check(self._lib.sa_hip_token_index_match_docs_batch_device(self._h, spans_dev_ptr, offsets_dev_ptr, q, int(min_length), int(cap),
+                                                                   positions_dev_ptr, out_spans_dev_ptr, heads_dev_ptr))
+
+    def match_batch(self, docs, max_length=0):
+        """docs as the patterns of query_batch: query documents.  -> structured array (first, count, length, ended)[offsets[Q]]: for
+        every position of the packed documents the longest prefix of what follows in its document (at most max_length symbols, 0: no
+        cap) that the text holds."""
+        buf, off, q = self._contexts(docs)
+        total = int(off[q]) if q else 0
+        out = _rows(total, SPAN_DTYPE)
+        self._call(q, self._lib.sa_hip_token_index_match_batch, _ptr(buf), _ptr(off), q, int(max_length), _ptr(out))
+        return out[:total]
+
+    def match_docs_batch(self, docs, min_length=1, max_length=0, cap=64, fill=0):
+        """Matches as in match_batch, then per document its maximal matches of at least min_length symbols.  -> dict: spans
+        [offsets[Q]], positions uint32[Q, cap] (offsets inside the document), out_spans [Q, cap], heads (written, maximal, longest,
+        covered)[Q].  Cells beyond heads['written'] keep `fill`."""
+        buf, off, q = self._contexts(docs)
+        cap = int(cap)
+        total = int(off[q]) if q else 0
+        spans, heads = _rows(total, SPAN_DTYPE), _rows(q, MATCH_HEAD_DTYPE)
+        pos = _rows(q, np.uint32, cap, fill)
+        outs = _rows(q, np.uint32, cap * 4, fill).view(SPAN_DTYPE)
+        self._call(q, self._lib.sa_hip_token_index_match_docs_batch, _ptr(buf), _ptr(off), q, int(max_length), int(min_length), cap,
+                   _ptr(spans), _ptr(pos), _ptr(outs), _ptr(heads))
+        return {"spans": spans[:total], "positions": pos[:q], "out_spans": outs[:q], "heads": heads[:q]}
+
+    def match_info(self):
+        return self._info(self._lib.sa_hip_token_index_match_info, TokenMatchInfo)
 
 
 class _BorrowedTokenIndex(TokenIndex):

@@ -11,6 +11,9 @@
     ti.documents(ngrams, cap=16)           # which documents, in order of first appearance by rank
     ti.term_counts(ngrams, docs)           # how often every n-gram occurs in every one of these documents: uint32[Q, len(docs)]
     ti.documents_with_all([[[464, 2068], [11]]], cap=16)    # per group of n-grams: the documents that hold all of them
+    ti.matching_statistics([text])         # per position of a query text: the longest prefix of what follows that the corpus holds
+    ti.matched_spans([text], min_length=8)    # its maximal verbatim spans as (position, length, count, first)
+    ti.coverage([text], min_length=8)      # how many of its tokens lie inside such a span, the longest one, how many there are
 
 On top of the handle API of include/sa_hip.h section 6 (suffixarray_amd._capi.TokenIndex).  No CPU fallback.
 """
@@ -159,6 +162,34 @@ class TokenIndex:
         r = self.next_tokens([list(ngram)], cap=cap, longest_suffix=longest_suffix, max_length=max_length)
         w = int(r["written"][0])
         return {int(s): int(c) for s, c in zip(r["symbols"][0, :w], r["counts"][0, :w])}
+
+    def matching_statistics(self, docs, max_length=None):
+        """Which parts of query texts stand verbatim in the corpus.  docs: a list of int sequences.  -> one (length, count, first)
+        per document, uint32 arrays over its positions: length[i] = the longest prefix of doc[i:] (at most max_length symbols)
+        that the corpus holds, count[i] its occurrences, SA[first[i] .. first[i] + count[i]) where.  length 0: {first 0, count n}."""
+        buf, off, q = self._idx._contexts(docs)
+        s = self._idx.match_batch((buf, off), max_length=max_length or 0)
+        cut = [(int(off[d]), int(off[d + 1])) for d in range(q)]
+        return [(s["length"][a:b].copy(), s["count"][a:b].copy(), s["first"][a:b].copy()) for a, b in cut]
+
+    def matched_spans(self, docs, min_length, max_length=None, cap=64):
+        """The maximal verbatim spans of every document: the matches of at least min_length symbols that no other position's match
+        contains, in position order.  -> one (spans, complete) per document: spans = a list of (position, length, count, first),
+        at most cap of them; complete = these are all."""
+        r = self._idx.match_docs_batch(docs, min_length=min_length, max_length=max_length or 0, cap=max(int(cap), 1))
+        out = []
+        for d, h in enumerate(r["heads"]):
+            w = min(int(h["written"]), int(cap))
+            o = r["out_spans"][d, :w]
+            out.append(([(int(p), int(l), int(c), int(f)) for p, l, c, f in zip(r["positions"][d, :w], o["length"], o["count"], o["first"])],
+                        int(h["maximal"]) <= int(cap)))
+        return out
+
+    def coverage(self, docs, min_length, max_length=None):
+        """-> dict of uint32[Q] arrays: covered = the tokens of every document that lie inside a match of at least min_length
+        symbols, longest = its longest match (whatever min_length is), maximal = the number of its maximal spans."""
+        h = self._idx.match_docs_batch(docs, min_length=min_length, max_length=max_length or 0, cap=0)["heads"]
+        return {"covered": h["covered"].copy(), "longest": h["longest"].copy(), "maximal": h["maximal"].copy()}
 
     def info(self):
         return self._idx.info()
