@@ -710,7 +710,10 @@ int sa_hip_token_index_next_info(const sa_hip_token_index* t, sa_hip_token_next_
  * owns a non-blocking stream and a mutex; the device forms are asynchronous on that stream until sa_hip_token_shards_sync and
  * chain without a host trip.  The per-shard lists of the next-symbol calls live in scratch of the set, S * cap * 8 bytes per
  * context: the batch is worked through in chunks of contexts sized by a scratch budget (sa_hip_token_shards_stats.chunk: the
- * contexts per chunk of the last such call). */
+ * contexts per chunk of the last such call).
+ *
+ * Matching statistics of a query text over the set -- sa_hip_token_shards_match_* -- stand behind (6f), whose terms and head
+ * record they use: see "(6c, matching statistics)" there.  Documents (locate, document counts) over a set are not built. */
 typedef struct sa_hip_token_shards sa_hip_token_shards;
 
 typedef struct sa_hip_token_shards_next {
@@ -724,7 +727,7 @@ typedef struct sa_hip_token_shards_stats {
     uint32_t shards;       /* S                                                                            */
     uint32_t chunk;        /* contexts per chunk of the last next-symbol call (0: none yet)                */
     uint64_t tokens;       /* sum of the shards' lengths                                                   */
-    uint64_t q;            /* patterns / contexts of the last launch of any kind                           */
+    uint64_t q;            /* patterns / contexts of the last ranges, spans or next-symbol launch          */
     double   ranges_ms;    /* HIP-event time of the last ranges launch (the call waits for it)             */
     double   spans_ms;     /* ... of the last spans launch                                                 */
     double   next_ms;      /* ... of the per-shard next-symbol launches of the last call, over its chunks  */
@@ -980,6 +983,65 @@ int sa_hip_token_index_match_docs_batch(sa_hip_token_index* t, const int32_t* pa
                                         uint32_t max_length, uint32_t min_length, uint32_t cap, sa_hip_token_span* spans,
                                         uint32_t* positions, sa_hip_token_span* out_spans, sa_hip_token_match_head* heads);
 int sa_hip_token_index_match_info(const sa_hip_token_index* t, sa_hip_token_match_info* out);
+
+/* (6c, matching statistics) the calls of (6f) over a shard set (csrc/token_shard_match.hpp, csrc/capi_token_shard_match.hpp).  The
+ * batch layout, M = max_length, avail(j), the flat positions and total = offsets[Q] are those of (6f); n_s is the length of shard s.
+ *   ms(j)      the largest L <= min(avail(j), M) such that patterns[j .. j + L) occurs in SOME shard: the maximum over s of what
+ *              shard s's own sa_hip_token_index_match_batch answers for j.  Shards are cut at document boundaries and a match never
+ *              spans a cut, so this is the matching statistic of the corpus as the set defines it; end(j) = j + ms(j) is
+ *              non-decreasing and a match is maximal iff end(j) > end(j - 1), as in (6f);
+ *   per_shard  [s * total + j], shard-major like every per-shard array of the set: what shard s's own spans_batch answers in mode 0
+ *              for patterns[j .. j + ms(j)) -- count 0 with the exact lower bound where the shard does not hold it, {first, 1, L, 1}
+ *              where it only ends the shard's text, {0, n_s, 0, 0} for L = 0, zeros from an empty shard and, in every shard, for a
+ *              position outside every document (j < offsets[0]);
+ *   merged     [j] = {length = ms(j), shards = how many shards have a count > 0, count = the sum over s of the per-shard counts};
+ *              a position outside every document, or a set of empty shards, gives zeros;
+ *   docs step  over merged, as in (6f): positions[d * cap + k] the offset inside the document, out_matches[d * cap + k] the merged
+ *              record of the k-th maximal match of at least min_length (>= 1) symbols, the head as in (6f).  Cells beyond `written`
+ *              are not written; cap == 0 computes the heads alone and touches neither array; an empty document has a head of zeros.
+ * With S == 1 length, count, per_shard, positions and heads equal the single index's answers.
+ *
+ * A position costs one range search and two neighbour comparisons per shard, then one more range search in every shard but the
+ * one that found the whole capped prefix.  The searches of a position's S shards run in neighbouring lanes.
+ *
+ * Errors returned as -1 before the set is dereferenced and before any HIP call: a NULL set or a NULL required pointer,
+ * min_length == 0, total >= 2^31, Q * cap >= 2^31, and in the host forms (which compute total) descending offsets; Q == 0 is a
+ * no-op returning 0; no usable device -3.  The device forms are asynchronous on the set's stream until sa_hip_token_shards_sync
+ * and chain without a host trip: merged_dev of the first is the input of the second, and per_shard_dev (required there,
+ * sa_hip_token_span[S * total]) has the layout of the set's span output with Q = total, so sa_hip_token_shards_next_batch_device(set,
+ * per_shard_dev, total, cap, ...) gives the tokens that follow the longest match at every position.  They trust nothing: every loop
+ * is bounded, a document's end is clamped to total, a length to what is left of its document.  A scratch of S * total uint32 belongs
+ * to the set and grows on demand.  The host forms stage through buffers of the set and copy out only the written cells of a row;
+ * per_shard (match_batch) and merged (match_docs_batch) are copied back only when given. */
+typedef struct sa_hip_token_shards_match {
+    uint32_t length;    /* ms(j): the longest match over all shards                            */
+    uint32_t shards;    /* shards that hold it (count > 0)                                     */
+    uint64_t count;     /* its occurrences over all shards                                     */
+} sa_hip_token_shards_match;
+
+typedef struct sa_hip_token_shards_match_stats {
+    uint64_t q;            /* documents of the last launch of either kind                        */
+    uint64_t positions;    /* positions of the last match launches                               */
+    double   match_ms;     /* HIP-event time of the last three match launches together           */
+    double   docs_ms;      /* ... of the last docs launch                                        */
+} sa_hip_token_shards_match_stats;
+
+/* merged_dev: sa_hip_token_shards_match[total]; per_shard_dev: sa_hip_token_span[S * total]; total = offsets[Q]. */
+int sa_hip_token_shards_match_batch_device(sa_hip_token_shards* set, const void* patterns_dev, const void* offsets_dev, uint64_t Q,
+                                           uint64_t total, uint32_t max_length, void* merged_dev, void* per_shard_dev);
+/* merged_dev as the call above writes it; positions_dev: uint32[Q * cap] and out_matches_dev: sa_hip_token_shards_match[Q * cap]
+ * (may be NULL when cap == 0); heads_dev: sa_hip_token_match_head[Q]. */
+int sa_hip_token_shards_match_docs_batch_device(sa_hip_token_shards* set, const void* merged_dev, const void* offsets_dev, uint64_t Q,
+                                                uint32_t min_length, uint32_t cap, void* positions_dev, void* out_matches_dev,
+                                                void* heads_dev);
+/* Host pointers; merged[offsets[Q]] out, per_shard[S * offsets[Q]] out or NULL. */
+int sa_hip_token_shards_match_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                    uint32_t max_length, sa_hip_token_shards_match* merged, sa_hip_token_span* per_shard);
+/* Both steps from host documents: merged[offsets[Q]] (may be NULL), positions, out_matches and heads[Q] out. */
+int sa_hip_token_shards_match_docs_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                         uint32_t max_length, uint32_t min_length, uint32_t cap, sa_hip_token_shards_match* merged,
+                                         uint32_t* positions, sa_hip_token_shards_match* out_matches, sa_hip_token_match_head* heads);
+int sa_hip_token_shards_match_info(const sa_hip_token_shards* set, sa_hip_token_shards_match_stats* out);
 
 /* ---- instrumentation ---------------------------------------------------------------------- */
 

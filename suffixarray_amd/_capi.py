@@ -22,6 +22,7 @@ ALL_DTYPE = np.dtype([("written", "<u4"), ("examined", "<u4"), ("matched", "<u4"
 MATCH_HEAD_DTYPE = np.dtype([("written", "<u4"), ("maximal", "<u4"), ("longest", "<u4"), ("covered", "<u4")])  # sa_hip_token_match_head
 TOKEN_ALL_MAX = 16                                                                                          # SA_HIP_TOKEN_ALL_MAX
 SHARDS_NEXT_DTYPE = np.dtype([("written", "<u4"), ("length", "<u4"), ("covered", "<u8"), ("total", "<u8")])  # sa_hip_token_shards_next
+SHARDS_MATCH_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("count", "<u8")])                      # sa_hip_token_shards_match
 SHARDS_MAX = 64
 UINT32_MAX = 0xFFFFFFFF
 
@@ -57,6 +58,8 @@ EXPORTS = [
     "sa_hip_token_shards_info", "sa_hip_token_shards_query_batch", "sa_hip_token_shards_query_batch_device",
     "sa_hip_token_shards_spans_batch", "sa_hip_token_shards_spans_batch_device", "sa_hip_token_shards_next_batch",
     "sa_hip_token_shards_next_batch_device", "sa_hip_token_shards_merge_device",
+    "sa_hip_token_shards_match_batch_device", "sa_hip_token_shards_match_docs_batch_device", "sa_hip_token_shards_match_batch",
+    "sa_hip_token_shards_match_docs_batch", "sa_hip_token_shards_match_info",
     "sa_hip_last_call_breakdown", "sa_hip_release_workspace",
     "sa_hip_construct_truncated_suffix_array", "sa_hip_get_substring_positions",
     "sa_hip_device_count", "sa_hip_index_create", "sa_hip_index_destroy", "sa_hip_index_build",
@@ -248,6 +251,18 @@ class TokenShardsStats(C.Structure):
     """sa_hip_token_shards_stats: a shard set and its last ranges, spans and next-symbol launches."""
     _fields_ = [("shards", C.c_uint32), ("chunk", C.c_uint32), ("tokens", C.c_uint64), ("q", C.c_uint64), ("ranges_ms", C.c_double),
                 ("spans_ms", C.c_double), ("next_ms", C.c_double), ("merge_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenShardsMatch(C.Structure):
+    _fields_ = [("length", C.c_uint32), ("shards", C.c_uint32), ("count", C.c_uint64)]
+
+
+class TokenShardsMatchStats(C.Structure):
+    """sa_hip_token_shards_match_stats: the last match and match-docs launches of a shard set."""
+    _fields_ = [("q", C.c_uint64), ("positions", C.c_uint64), ("match_ms", C.c_double), ("docs_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -586,6 +601,16 @@ def lib():
     L.sa_hip_token_shards_next_batch_device.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, vp]
     L.sa_hip_token_shards_merge_device.restype = C.c_int
     L.sa_hip_token_shards_merge_device.argtypes = [vp, vp, vp, vp, u64, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_shards_match_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_match_batch_device.argtypes = [vp, vp, vp, u64, u64, C.c_uint32, vp, vp]
+    L.sa_hip_token_shards_match_docs_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_match_docs_batch_device.argtypes = [vp, vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_shards_match_batch.restype = C.c_int
+    L.sa_hip_token_shards_match_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, vp]
+    L.sa_hip_token_shards_match_docs_batch.restype = C.c_int
+    L.sa_hip_token_shards_match_docs_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_shards_match_info.restype = C.c_int
+    L.sa_hip_token_shards_match_info.argtypes = [vp, C.POINTER(TokenShardsMatchStats)]
     L.sa_hip_sort_pairs.restype = C.c_int
     L.sa_hip_sort_pairs.argtypes = [vp, vp, u64, C.c_int, C.c_int, C.c_int]
     L.sa_hip_synth_uniform27.restype = None
@@ -1617,6 +1642,47 @@ class TokenShards(_TokenHandle):
         """The merge step alone, on S * q device lists; asynchronous on the set's stream until sync()."""
         check(self._lib.sa_hip_token_shards_merge_device(self._h, symbols_dev_ptr, counts_dev_ptr, heads_dev_ptr, q, int(cap),
                                                          out_symbols_dev_ptr, out_counts_dev_ptr, out_heads_dev_ptr))
+
+    def match_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, total, max_length, merged_dev_ptr, per_shard_dev_ptr):
+        """The longest match over all shards at every one of the `total` = offsets[q] positions of q device documents (max_length 0:
+        no cap) into merged_dev_ptr[total] and its span in every shard into per_shard_dev_ptr[S * total]; asynchronous on the set's
+        stream until sync()."""
+        check(self._lib.sa_hip_token_shards_match_batch_device(self._h, patterns_dev_ptr, offsets_dev_ptr, q, int(total), int(max_length),
+                                                               merged_dev_ptr, per_shard_dev_ptr))
+
+    def match_docs_batch_device(self, merged_dev_ptr, offsets_dev_ptr, q, min_length, cap, positions_dev_ptr, out_matches_dev_ptr, heads_dev_ptr):
+        """The maximal matches of at least min_length symbols of q device documents from the records match_batch_device wrote (cap 0:
+        heads only, positions and out_matches may be None); asynchronous until sync()."""
+        check(self._lib.sa_hip_token_shards_match_docs_batch_device(self._h, merged_dev_ptr, offsets_dev_ptr, q, int(min_length), int(cap),
+                                                                    positions_dev_ptr, out_matches_dev_ptr, heads_dev_ptr))
+
+    def match_batch(self, docs, max_length=0, per_shard=True):
+        """docs as the patterns of query_batch: query documents.  -> (merged structured (length, shards, count)[offsets[Q]], per_shard
+        structured (first, count, length, ended)[S, offsets[Q]] or None): for every position of the packed documents the longest
+        prefix of what follows in its document (at most max_length symbols, 0: no cap) that some shard holds."""
+        buf, off, q = self._contexts(docs)
+        total = int(off[q]) if q else 0
+        merged = _rows(total, SHARDS_MATCH_DTYPE)
+        per = self._shard_rows(total, SPAN_DTYPE) if per_shard else None
+        self._call(q, self._lib.sa_hip_token_shards_match_batch, _ptr(buf), _ptr(off), q, int(max_length), _ptr(merged), _ptr(per))
+        return merged[:total], (per[:, :total] if per_shard else None)
+
+    def match_docs_batch(self, docs, min_length=1, max_length=0, cap=64, fill=0):
+        """Matches as in match_batch, then per document its maximal matches of at least min_length symbols.  -> dict: merged
+        [offsets[Q]], positions uint32[Q, cap] (offsets inside the document), out_matches [Q, cap], heads (written, maximal, longest,
+        covered)[Q].  Cells beyond heads['written'] keep `fill`."""
+        buf, off, q = self._contexts(docs)
+        cap = int(cap)
+        total = int(off[q]) if q else 0
+        merged, heads = _rows(total, SHARDS_MATCH_DTYPE), _rows(q, MATCH_HEAD_DTYPE)
+        pos = _rows(q, np.uint32, cap, fill)
+        outs = _rows(q, np.uint32, cap * 4, fill).view(SHARDS_MATCH_DTYPE)
+        self._call(q, self._lib.sa_hip_token_shards_match_docs_batch, _ptr(buf), _ptr(off), q, int(max_length), int(min_length), cap,
+                   _ptr(merged), _ptr(pos), _ptr(outs), _ptr(heads))
+        return {"merged": merged[:total], "positions": pos[:q], "out_matches": outs[:q], "heads": heads[:q]}
+
+    def match_info(self):
+        return self._info(self._lib.sa_hip_token_shards_match_info, TokenShardsMatchStats)
 
 
 def construct_truncated_suffix_array(text, max_suffix_length):

@@ -29,7 +29,7 @@ int token_launch_match(sa_hip_token_index* t, const int32_t* pat, const u64* off
 
 int token_launch_match_docs(sa_hip_token_index* t, const sa_hip_token_span* spans, const u64* off, u64 Q, u32 min_length, u32 cap,
                             u32* positions, sa_hip_token_span* out_spans, sa_hip_token_match_head* heads) {
-    const tq::MatchDocsArgs g{spans, off, Q, min_length, cap, positions, out_spans, heads};
+    const tq::MatchDocsArgs<sa_hip_token_span> g{spans, off, Q, min_length, cap, positions, out_spans, heads};
     int rc;
     if ((rc = t->tm_md.begin(t->stream)) || (rc = tq::launch_match_docs(t->stream, g)) || (rc = t->tm_md.end(t->stream, Q))) return rc;
     t->m_last = Q;

@@ -1,5 +1,6 @@
 // capi_token_shards.hpp -- the C ABI of the shard set (include/sa_hip.h section 6c), included by sa_capi.hip behind capi_token.hpp
 // (same translation unit).  The kernels are csrc/token_shards.hpp; the per-shard next symbols are tq::launch_next of every shard.
+// Matching statistics over the set: capi_token_shard_match.hpp.
 // The stopwatches, the upload of a host batch and the row copy are capi_token.hpp's; the per-chunk events of the next symbols, summed
 // into two figures, are the set's own.
 #pragma once
@@ -28,6 +29,12 @@ struct sa_hip_token_shards {
     u64 q_last = 0;                          // contexts of the last launch of any kind
     u32 chunk_last = 0;
     double nx_ms = 0.0, mg_ms = 0.0;
+    // matching statistics (token_shard_match.hpp, capi_token_shard_match.hpp)
+    DevBuf m_ms;                             // u32[total * S]: the per-shard lengths of the last match launch, position-major
+    DevBuf m_per, m_merged;                  // staging of the host forms
+    DevBuf m_pos, m_out, m_heads;
+    LaunchTimer tm_mt, tm_md;                // the last match launches (q: positions) / match docs launch (q: documents)
+    u64 m_last = 0;                          // documents of the last launch of either kind
 
     const tq::View* table() const { return tab.as<tq::View>(); }
 };
@@ -136,7 +143,8 @@ void sa_hip_token_shards_destroy(sa_hip_token_shards* g) {
     g->s_spans.release(); g->s_len.release(); g->s_tot.release();
     g->l_sym.release(); g->l_cnt.release(); g->l_heads.release(); g->l_list.release();
     g->o_sym.release(); g->o_cnt.release(); g->o_heads.release();
-    g->tm_r.destroy(); g->tm_sp.destroy();
+    g->m_ms.release(); g->m_per.release(); g->m_merged.release(); g->m_pos.release(); g->m_out.release(); g->m_heads.release();
+    g->tm_r.destroy(); g->tm_sp.destroy(); g->tm_mt.destroy(); g->tm_md.destroy();
     for (hipEvent_t e : g->nx_ev) (void)hipEventDestroy(e);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
@@ -163,6 +171,8 @@ int sa_hip_token_shards_create(sa_hip_token_shards** out, sa_hip_token_index* co
         SA_HIP_CHECK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
         SA_HIP_CHECK(g->tm_r.create());
         SA_HIP_CHECK(g->tm_sp.create());
+        SA_HIP_CHECK(g->tm_mt.create());
+        SA_HIP_CHECK(g->tm_md.create());
         tq::View v[tq::SHARDS_MAX];
         for (u32 s = 0; s < S; ++s) {
             std::lock_guard<std::mutex> lk(shards[s]->mu);

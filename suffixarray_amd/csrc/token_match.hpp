@@ -23,7 +23,9 @@
 //
 //   tq_match_kernel       one lane per position, BLOCK threads.  The document's end by an upper bound over offsets (<= 64 steps),
 //                         then fact 1: a range search, two neighbour LCPs (tq_lcp), and a second range search when 1 <= ms < |P|.
-//   tq_match_docs_kernel  one wave per document, NEXT_WAVES per workgroup, no LDS.  The document's positions in windows of 64,
+//   tq_match_docs_kernel  a template over the position's 16-byte record (here sa_hip_token_span; over a shard set the merged
+//                         record of token_shard_match.hpp), of which it reads .length and which it copies out whole.
+//                         One wave per document, NEXT_WAVES per workgroup, no LDS.  The document's positions in windows of 64,
 //                         spans[j] read coalesced (16 bytes per lane, the next window's load in flight); the predecessor's end by
 //                         lane_shift_up with prev_end carried across windows (fact 2), E by wave_scan_incl with max and a carried
 //                         value (fact 3); a ballot and a popcount prefix give the output slots of the maximal matches of at least
@@ -42,7 +44,8 @@
 // that no match launch wrote, give unspecified answers, never a spin or a read outside the buffers.
 //
 // Not built: carrying the LCPs of the search's two ends so that a probe's comparison starts behind them (Manber-Myers); starting
-// position j + 1 from ms(j) - 1; one very long document split over several waves; the same over shard sets.
+// position j + 1 from ms(j) - 1; one very long document split over several waves.  (The same over shard sets is
+// token_shard_match.hpp, which says what is not built there.)
 #pragma once
 #include "token_next.hpp"
 
@@ -103,40 +106,55 @@ __global__ __launch_bounds__(BLOCK) void tq_match_kernel(View x, MatchArgs g) {
     g.spans[j] = s;
 }
 
+// Rec: the 16-byte record of a position, read for its .length and copied out whole -- sa_hip_token_span here,
+// sa_hip_token_shards_match over a shard set (token_shard_match.hpp).  A lane holds it as four words, whatever its fields are.
+typedef u32 MatchRecWords __attribute__((ext_vector_type(4)));
+
+template <class Rec>
+__device__ __forceinline__ MatchRecWords tq_match_rec_load(const Rec* p) {
+    static_assert(sizeof(Rec) == sizeof(MatchRecWords) && offsetof(Rec, length) % 4 == 0, "a record is four words");
+    MatchRecWords w;
+    __builtin_memcpy(&w, p, sizeof w);
+    return w;
+}
+
+template <class Rec>
 struct MatchDocsArgs {
-    const sa_hip_token_span* spans;    // [offsets[Q]], by position
+    const Rec* spans;                  // [offsets[Q]], by position
     const u64* off;                    // [Q + 1]
     u64 Q;
     u32 min_length;                    // >= 1
     u32 cap;                           // 0: heads only
     u32* positions;                    // [Q * cap]; never touched when cap == 0
-    sa_hip_token_span* out_spans;      // [Q * cap]
+    Rec* out_spans;                    // [Q * cap]
     sa_hip_token_match_head* heads;    // [Q]
 };
 
 // One wave per document.  Every trip of the walk advances by one window of 64 positions.
-__global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_match_docs_kernel(MatchDocsArgs g) {
+template <class Rec>
+__global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_match_docs_kernel(MatchDocsArgs<Rec> g) {
     const u32 lane = threadIdx.x & (WAVE - 1);
     const u64 waves = (u64)gridDim.x * NEXT_WAVES;
     for (u64 d = (u64)blockIdx.x * NEXT_WAVES + (threadIdx.x >> 6); d < g.Q; d += waves) {
         const u64 o0 = g.off[d], o1r = g.off[d + 1];
         const u64 o1 = o1r > o0 ? o1r : o0;
         u32* const pos = g.positions + d * g.cap;
-        sa_hip_token_span* const outs = g.out_spans + d * g.cap;
+        Rec* const outs = g.out_spans + d * g.cap;
         u64 prev_end = o0;         // end(j - 1) of the window's first position: no match before the document reaches into it
         u64 E = 0;                 // the largest end of a qualifying position so far
         u64 covered = 0;           // this lane's share
         u32 longest = 0;           // this lane's share
         u32 maximal = 0;
-        sa_hip_token_span nxt{0u, 0u, 0u, 0u};
-        if (o0 + lane < o1) nxt = g.spans[o0 + lane];
+        MatchRecWords nxt = {0u, 0u, 0u, 0u};
+        if (o0 + lane < o1) nxt = tq_match_rec_load(g.spans + o0 + lane);
         for (u64 a = o0; a < o1; a += (u64)WAVE) {
             const u64 j = a + lane;
             const bool act = j < o1;
-            const sa_hip_token_span sp = nxt;
-            if (j + WAVE < o1) nxt = g.spans[j + WAVE];
+            const MatchRecWords sp = nxt;
+            if (j + WAVE < o1) nxt = tq_match_rec_load(g.spans + j + WAVE);
+            const u32 sp_length = sp[offsetof(Rec, length) / 4];
             const u64 left = act ? o1 - j : 0;
-            const u32 len = act ? (sp.length < left ? sp.length : (u32)left) : 0u;   // a match never passes its document's end
+            const u32 len = act ? (sp_length < left ? sp_length : (u32)left) : 0u;   // a match never passes its document's end
             const u64 end = act ? j + len : o1;
             u64 pe = lane_shift_up(end, 1);
             if (lane == 0) pe = prev_end;
@@ -153,7 +171,7 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_match_docs_kernel(MatchD
             const u32 slot = maximal + (u32)__popcll(hb & lanemask_lt());
             if (out && slot < g.cap) {
                 pos[slot] = (u32)(j - o0);
-                outs[slot] = sp;
+                __builtin_memcpy(outs + slot, &sp, sizeof sp);
             }
             maximal += (u32)__popcll(hb);
             const u64 top = __shfl(incl, WAVE - 1);
@@ -184,10 +202,11 @@ inline int launch_match(const Index& x, hipStream_t stream, const MatchArgs& g) 
 }
 
 // Q >= 1 documents, Q * cap < 2^31 (cap may be 0); every pointer on the device; asynchronous on `stream`
-inline int launch_match_docs(hipStream_t stream, const MatchDocsArgs& g) {
+template <class Rec>
+inline int launch_match_docs(hipStream_t stream, const MatchDocsArgs<Rec>& g) {
     const u64 wave_grid = (g.Q + NEXT_WAVES - 1) / NEXT_WAVES;
     const u32 grid = (u32)(wave_grid < 256u * 16u ? wave_grid : 256u * 16u);
-    hipLaunchKernelGGL(tq_match_docs_kernel, dim3(grid), dim3(NEXT_WAVES * WAVE), 0, stream, g);
+    hipLaunchKernelGGL(tq_match_docs_kernel<Rec>, dim3(grid), dim3(NEXT_WAVES * WAVE), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -5,6 +5,8 @@
     sti.positions([464, 2068], limit=10)           # (shard, position) pairs
     sti.next_token_counts([464, 2068])             # {token: count} of what follows the n-gram anywhere
     sti.next_tokens(contexts, cap=64, longest_suffix=True)    # backing off to the longest suffix that ANY shard holds
+    sti.matching_statistics([doc])                 # per position: the longest match in any shard, its count, the shards that hold it
+    sti.matched_spans([doc], min_length=8)         # the maximal verbatim spans of a text; sti.coverage([doc], 8): how much they cover
 
 The corpus is cut by the caller, at document boundaries: an n-gram never spans two shards, so its count is the sum of the shards'
 counts.  On top of include/sa_hip.h section 6c (suffixarray_amd._capi.TokenShards).  No CPU fallback.
@@ -73,6 +75,35 @@ class ShardedTokenIndex:
         r = self.next_tokens([list(ngram)], cap=cap, longest_suffix=longest_suffix, max_length=max_length)
         w = int(r["written"][0])
         return {int(s): int(c) for s, c in zip(r["symbols"][0, :w], r["counts"][0, :w])}
+
+    def matching_statistics(self, docs, max_length=None):
+        """Which parts of query texts stand verbatim in some shard.  docs: a list of int sequences.  -> one (length, count, shards)
+        per document, arrays over its positions: length[i] (uint32) = the longest prefix of doc[i:] (at most max_length symbols)
+        that a shard holds, count[i] (uint64) its occurrences over all shards, shards[i] (uint32) the shards that hold it.  A match
+        never spans two shards."""
+        buf, off, q = self._set._contexts(docs)
+        m, _ = self._set.match_batch((buf, off), max_length=max_length or 0, per_shard=False)
+        cut = [(int(off[d]), int(off[d + 1])) for d in range(q)]
+        return [(m["length"][a:b].copy(), m["count"][a:b].copy(), m["shards"][a:b].copy()) for a, b in cut]
+
+    def matched_spans(self, docs, min_length, max_length=None, cap=64):
+        """The maximal verbatim spans of every document: the matches of at least min_length symbols that no other position's match
+        contains, in position order.  -> one (spans, complete) per document: spans = a list of (position, length, count, shards),
+        at most cap of them; complete = these are all."""
+        r = self._set.match_docs_batch(docs, min_length=min_length, max_length=max_length or 0, cap=max(int(cap), 1))
+        out = []
+        for d, h in enumerate(r["heads"]):
+            w = min(int(h["written"]), int(cap))
+            o = r["out_matches"][d, :w]
+            out.append(([(int(p), int(l), int(c), int(k)) for p, l, c, k in zip(r["positions"][d, :w], o["length"], o["count"], o["shards"])],
+                        int(h["maximal"]) <= int(cap)))
+        return out
+
+    def coverage(self, docs, min_length, max_length=None):
+        """-> dict of uint32[Q] arrays: covered = the tokens of every document that lie inside a match of at least min_length
+        symbols, longest = its longest match (whatever min_length is), maximal = the number of its maximal spans."""
+        h = self._set.match_docs_batch(docs, min_length=min_length, max_length=max_length or 0, cap=0)["heads"]
+        return {"covered": h["covered"].copy(), "longest": h["longest"].copy(), "maximal": h["maximal"].copy()}
 
     def info(self):
         return self._set.info()
