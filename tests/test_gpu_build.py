@@ -599,3 +599,40 @@ def test_wide_sort_from_the_text_matches_key_array(gpu, oracle, monkeypatch):
         assert np.array_equal(got["1"], exp), name
     monkeypatch.delenv("SA_HIP_WIDE_TEXT_PASS", raising=False)
     monkeypatch.delenv("SA_HIP_NARROW48", raising=False)
+
+
+def test_one_handle_builds_different_plans_in_turn(gpu, oracle):
+    """What a build keeps about itself must not reach the next build on the same handle.  One index of capacity 2^22 builds,
+    in turn: (A) uniform text (8-byte records, three-pass plan, first flags pass inside the sort's local pass), (B) a block
+    repeated 12 times (long repeats: doubling rounds or the periodic-run shortcut), (C) word text (10-byte records), (A)
+    again and (A) with the int64 copy.  Every suffix array is the oracle's, the statistics show the intended plan, and the
+    second (A) reports what the first did on every field but the event times.  2^22 is the smallest n at which
+    narrow_sort_applies / narrow48_applies admit the narrow plans."""
+    import torch
+    from suffixarray_amd import synth
+    n = 1 << 22
+    a, b, c = synth.d1_uniform27(n), cases.small_texts()["repeat_block"], synth.d2_words(n)
+    ref = {name: oracle.sais(t) for name, t in (("a", a), ("b", b), ("c", c))}
+    timed = ("radix_ms", "total_ms", "pass_ms", "widen_ms")
+    with gpu.DeviceIndex(n, 0) as idx:
+        def build(name, t):
+            idx.build(t)
+            st = idx.build_stats()
+            assert np.array_equal(idx.sa_u32(), ref[name].astype(np.uint32)), (name, st)
+            return st
+        a1 = build("a", a)
+        assert a1["split_plan"] > 0 and a1["lite_flags"] == 2, a1
+        st = build("b", b)
+        assert st["doubling_rounds"] + st["period_resolved"] > 0, st
+        st = build("c", c)
+        assert st["narrow48"] == 1, st
+        a2 = build("a", a)
+        assert {k: v for k, v in a2.items() if k not in timed} == {k: v for k, v in a1.items() if k not in timed}
+        out = torch.full((n + 2,), -7, dtype=torch.int64, device="cuda:0")
+        torch.cuda.synchronize()
+        idx.build_device64(idx.text_dev, n, out.data_ptr())
+        idx.sync()
+        got = out.cpu().numpy()
+        assert np.array_equal(got[:n], ref["a"].astype(np.int64)), idx.build_stats()
+        assert (got[n:] == -7).all()
+        assert np.array_equal(idx.sa_u32(), ref["a"].astype(np.uint32))
