@@ -713,7 +713,9 @@ int sa_hip_token_index_next_info(const sa_hip_token_index* t, sa_hip_token_next_
  * contexts per chunk of the last such call).
  *
  * Matching statistics of a query text over the set -- sa_hip_token_shards_match_* -- stand behind (6f), whose terms and head
- * record they use: see "(6c, matching statistics)" there.  Documents (locate, document counts) over a set are not built. */
+ * record they use: see "(6c, matching statistics)" there.  Documents over a set -- locate, the distinct documents of an n-gram and
+ * its document frequency, sa_hip_token_shards_locate_* and _docs_* -- are (6g).  Per-document counts and AND groups (6e) over a set
+ * are not built. */
 typedef struct sa_hip_token_shards sa_hip_token_shards;
 
 typedef struct sa_hip_token_shards_next {
@@ -1042,6 +1044,98 @@ int sa_hip_token_shards_match_docs_batch(sa_hip_token_shards* set, const int32_t
                                          uint32_t max_length, uint32_t min_length, uint32_t cap, sa_hip_token_shards_match* merged,
                                          uint32_t* positions, sa_hip_token_shards_match* out_matches, sa_hip_token_match_head* heads);
 int sa_hip_token_shards_match_info(const sa_hip_token_shards* set, sa_hip_token_shards_match_stats* out);
+
+/* (6g) documents over a shard set (csrc/token_shard_docs.hpp, csrc/capi_token_shard_docs.hpp): the calls of (6d) answered for the
+ * whole corpus.  All results are exact.
+ *
+ * The set is one corpus cut at document boundaries, so a document lives in exactly one shard.  With D_s documents in shard s, empty
+ * ones included, base[0] = 0 and base[s + 1] = base[s] + D_s; the global id of document d of shard s is base[s] + d, a uint64.  The
+ * hits of a context are the concatenation of the shards' rank ranges in shard order, suffix order inside a shard.  For context i the
+ * span step of the set gives spans[s * Q + i]; c_s is its count clamped to the shard and C = the sum of the c_s, a uint64.
+ *
+ *   locate  the first min(C, cap) hits of that concatenation as (global document, offset inside it) to docs[i * cap ..] and
+ *           offsets[i * cap ..]; the head is {written, count = C}.
+ *   docs    examined = budget ? min(C, budget) : C ranks are taken from the front of the concatenation: shard s examines
+ *           e_s = clamp(budget - (c_0 + .. + c_(s-1)), 0, c_s) ranks of its span, c_s without a budget.  distinct = the sum over s
+ *           of the distinct documents among those e_s ranks -- two shards never share a document, so nothing is de-duplicated
+ *           across them.  The list is the shards' lists of (6d) one after another, global ids, cut at cap.  The head is {written =
+ *           min(distinct, cap), examined, distinct, count = C}; distinct is the exact document frequency iff examined == count.
+ *           cap == 0 counts only; docs and offsets may then be NULL and are never touched.
+ * Slots beyond `written` are not written.  With S == 1 every answer equals the single index's, the document ids widened.
+ *
+ * sa_hip_token_shards_set_documents gives every shard its table through sa_hip_token_index_set_documents: starts[s] is the table
+ * of shard s, D[s] >= 1 its length, every entry required; all S tables are checked by the rules of (6d) before the first shard is
+ * touched.  NULL starts and NULL D remove the documents from all shards.  sa_hip_token_shards_adopt_documents builds the set's
+ * table from documents the shards already have (set through the borrowed handle, or before the handle joined the set); -1 if a
+ * shard has none.  A shard's documents can be replaced behind the set's back through sa_hip_token_shards_shard: every handle
+ * counts its set_documents calls, and every call below compares the counts the set recorded before any launch; where they differ
+ * it returns -1 and the message names sa_hip_token_shards_adopt_documents.  As with every use of a borrowed handle, the caller
+ * synchronises the set before it changes a shard.
+ *
+ * The per-shard lists of the docs calls live in scratch of the set, S * cap * 8 bytes plus 16 per shard and context (the heads
+ * alone when cap == 0), worked through in chunks of contexts exactly as the next-symbol calls of (6c) are.
+ *
+ * Errors returned as -1 before any HIP call: those of (6c) and (6d) -- a NULL set or a NULL required pointer, mode or need_next
+ * other than 0 / 1, cap == 0 in locate, Q * cap >= 2^31, descending offsets -- and a set without documents or whose shards'
+ * documents changed; Q == 0 is a no-op returning 0.  The device forms take sa_hip_token_span[S * Q] exactly as
+ * sa_hip_token_shards_spans_batch_device writes them, chain with it without a host trip and are asynchronous until
+ * sa_hip_token_shards_sync; they trust nothing: first and count are clamped to the shard, every loop is bounded.  The host forms
+ * run the span step first (locate always in mode 0) and stage through buffers of the set. */
+typedef struct sa_hip_token_shards_locate {
+    uint32_t written;    /* entries written for this context: min(count, cap)                   */
+    uint32_t reserved;   /* 0                                                                   */
+    uint64_t count;      /* hits over all shards                                                */
+} sa_hip_token_shards_locate;
+
+typedef struct sa_hip_token_shards_docs {
+    uint32_t written;    /* entries written for this context: min(distinct, cap)                */
+    uint32_t reserved;   /* 0                                                                   */
+    uint64_t examined;   /* ranks walked over all shards: budget ? min(count, budget) : count   */
+    uint64_t distinct;   /* distinct documents among them                                       */
+    uint64_t count;      /* hits over all shards                                                */
+} sa_hip_token_shards_docs;
+
+typedef struct sa_hip_token_shards_docs_stats {
+    uint64_t documents;    /* of the set: base[S]; 0: the set has no documents                             */
+    uint32_t chunk;        /* contexts per chunk of the last docs call (0: none yet)                       */
+    uint32_t reserved;     /* 0                                                                            */
+    uint64_t locate_q;     /* contexts of the last locate launch                                           */
+    double   locate_ms;    /* HIP-event time of it (the call waits for it)                                 */
+    uint64_t pairs_q;      /* (context, shard) pairs of the last docs call                                 */
+    double   pairs_ms;     /* HIP-event time of its pair launches, over its chunks                         */
+    uint64_t merge_q;      /* contexts of the last merge launches                                          */
+    double   merge_ms;     /* HIP-event time of them, over the chunks                                      */
+    uint64_t streamed;     /* sum of the pairs' examined: the ranks the last docs call streamed            */
+} sa_hip_token_shards_docs_stats;
+
+/* starts[S] host tables, D[S] their lengths; both NULL: remove the documents. */
+int sa_hip_token_shards_set_documents(sa_hip_token_shards* set, const int32_t* const* starts, const uint32_t* D);
+int sa_hip_token_shards_adopt_documents(sa_hip_token_shards* set);
+/* out: uint64[S + 1], base[S] = the documents of the set. */
+int sa_hip_token_shards_doc_bases(sa_hip_token_shards* set, uint64_t* out);
+int sa_hip_token_shards_docs_info(const sa_hip_token_shards* set, sa_hip_token_shards_docs_stats* out);
+/* spans_dev: sa_hip_token_span[S * Q]; docs_dev: uint64[Q * cap]; offsets_dev: int32[Q * cap]; heads_dev:
+ * sa_hip_token_shards_locate[Q]. */
+int sa_hip_token_shards_locate_batch_device(sa_hip_token_shards* set, const void* spans_dev, uint64_t Q, uint32_t cap, void* docs_dev,
+                                            void* offsets_dev, void* heads_dev);
+/* Both steps from host patterns: spans[S * Q] (may be NULL), docs, offs and heads out. */
+int sa_hip_token_shards_locate_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                     uint32_t cap, sa_hip_token_span* spans, uint64_t* docs, int32_t* offs,
+                                     sa_hip_token_shards_locate* heads);
+/* heads_dev: sa_hip_token_shards_docs[Q]; docs_dev and offsets_dev may be NULL when cap == 0. */
+int sa_hip_token_shards_docs_batch_device(sa_hip_token_shards* set, const void* spans_dev, uint64_t Q, uint32_t cap, uint64_t budget,
+                                          void* docs_dev, void* offsets_dev, void* heads_dev);
+int sa_hip_token_shards_docs_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t Q, int mode,
+                                   uint32_t max_length, int need_next, uint32_t cap, uint64_t budget, sa_hip_token_span* spans,
+                                   uint64_t* docs, int32_t* offs, sa_hip_token_shards_docs* heads);
+/* The last step of the two calls above on its own: S lists per context as the pair launch writes them -- docs_dev int32[S * Q * cap]
+ * (row (s * Q + i) * cap, ids local to the shard), offsets_dev int32[S * Q * cap], heads_dev sa_hip_token_docs[S * Q] (written is
+ * clamped to cap) -- into out_docs_dev uint64[Q * cap], out_offsets_dev int32[Q * cap], out_heads_dev sa_hip_token_shards_docs[Q].
+ * bases_dev: uint64[S + 1] on the device, or NULL for the set's own (which needs the set's documents).  With cap == 0 the four list
+ * pointers may be NULL.  Asynchronous on the set's stream. */
+int sa_hip_token_shards_docs_merge_device(sa_hip_token_shards* set, const void* docs_dev, const void* offsets_dev, const void* heads_dev,
+                                          const void* bases_dev, uint64_t Q, uint32_t cap, void* out_docs_dev, void* out_offsets_dev,
+                                          void* out_heads_dev);
 
 /* ---- instrumentation ---------------------------------------------------------------------- */
 

@@ -23,6 +23,9 @@ MATCH_HEAD_DTYPE = np.dtype([("written", "<u4"), ("maximal", "<u4"), ("longest",
 TOKEN_ALL_MAX = 16                                                                                          # SA_HIP_TOKEN_ALL_MAX
 SHARDS_NEXT_DTYPE = np.dtype([("written", "<u4"), ("length", "<u4"), ("covered", "<u8"), ("total", "<u8")])  # sa_hip_token_shards_next
 SHARDS_MATCH_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("count", "<u8")])                      # sa_hip_token_shards_match
+SHARDS_LOCATE_DTYPE = np.dtype([("written", "<u4"), ("reserved", "<u4"), ("count", "<u8")])                  # sa_hip_token_shards_locate
+SHARDS_DOCS_DTYPE = np.dtype([("written", "<u4"), ("reserved", "<u4"), ("examined", "<u8"), ("distinct", "<u8"),
+                              ("count", "<u8")])                                                            # sa_hip_token_shards_docs
 SHARDS_MAX = 64
 UINT32_MAX = 0xFFFFFFFF
 
@@ -60,6 +63,9 @@ EXPORTS = [
     "sa_hip_token_shards_next_batch_device", "sa_hip_token_shards_merge_device",
     "sa_hip_token_shards_match_batch_device", "sa_hip_token_shards_match_docs_batch_device", "sa_hip_token_shards_match_batch",
     "sa_hip_token_shards_match_docs_batch", "sa_hip_token_shards_match_info",
+    "sa_hip_token_shards_set_documents", "sa_hip_token_shards_adopt_documents", "sa_hip_token_shards_doc_bases",
+    "sa_hip_token_shards_docs_info", "sa_hip_token_shards_locate_batch_device", "sa_hip_token_shards_locate_batch",
+    "sa_hip_token_shards_docs_batch_device", "sa_hip_token_shards_docs_batch", "sa_hip_token_shards_docs_merge_device",
     "sa_hip_last_call_breakdown", "sa_hip_release_workspace",
     "sa_hip_construct_truncated_suffix_array", "sa_hip_get_substring_positions",
     "sa_hip_device_count", "sa_hip_index_create", "sa_hip_index_destroy", "sa_hip_index_build",
@@ -263,6 +269,25 @@ class TokenShardsMatch(C.Structure):
 class TokenShardsMatchStats(C.Structure):
     """sa_hip_token_shards_match_stats: the last match and match-docs launches of a shard set."""
     _fields_ = [("q", C.c_uint64), ("positions", C.c_uint64), ("match_ms", C.c_double), ("docs_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenShardsLocate(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("reserved", C.c_uint32), ("count", C.c_uint64)]
+
+
+class TokenShardsDocs(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("reserved", C.c_uint32), ("examined", C.c_uint64), ("distinct", C.c_uint64),
+                ("count", C.c_uint64)]
+
+
+class TokenShardsDocsStats(C.Structure):
+    """sa_hip_token_shards_docs_stats: the documents of a shard set and its last locate, pair and merge launches."""
+    _fields_ = [("documents", C.c_uint64), ("chunk", C.c_uint32), ("reserved", C.c_uint32), ("locate_q", C.c_uint64),
+                ("locate_ms", C.c_double), ("pairs_q", C.c_uint64), ("pairs_ms", C.c_double), ("merge_q", C.c_uint64),
+                ("merge_ms", C.c_double), ("streamed", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -611,6 +636,24 @@ def lib():
     L.sa_hip_token_shards_match_docs_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.sa_hip_token_shards_match_info.restype = C.c_int
     L.sa_hip_token_shards_match_info.argtypes = [vp, C.POINTER(TokenShardsMatchStats)]
+    L.sa_hip_token_shards_set_documents.restype = C.c_int
+    L.sa_hip_token_shards_set_documents.argtypes = [vp, vp, vp]
+    L.sa_hip_token_shards_adopt_documents.restype = C.c_int
+    L.sa_hip_token_shards_adopt_documents.argtypes = [vp]
+    L.sa_hip_token_shards_doc_bases.restype = C.c_int
+    L.sa_hip_token_shards_doc_bases.argtypes = [vp, vp]
+    L.sa_hip_token_shards_docs_info.restype = C.c_int
+    L.sa_hip_token_shards_docs_info.argtypes = [vp, C.POINTER(TokenShardsDocsStats)]
+    L.sa_hip_token_shards_locate_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_locate_batch_device.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_shards_locate_batch.restype = C.c_int
+    L.sa_hip_token_shards_locate_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_shards_docs_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_docs_batch_device.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, vp, vp]
+    L.sa_hip_token_shards_docs_batch.restype = C.c_int
+    L.sa_hip_token_shards_docs_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, u64, vp, vp, vp, vp]
+    L.sa_hip_token_shards_docs_merge_device.restype = C.c_int
+    L.sa_hip_token_shards_docs_merge_device.argtypes = [vp, vp, vp, vp, vp, u64, C.c_uint32, vp, vp, vp]
     L.sa_hip_sort_pairs.restype = C.c_int
     L.sa_hip_sort_pairs.argtypes = [vp, vp, u64, C.c_int, C.c_int, C.c_int]
     L.sa_hip_synth_uniform27.restype = None
@@ -1683,6 +1726,78 @@ class TokenShards(_TokenHandle):
 
     def match_info(self):
         return self._info(self._lib.sa_hip_token_shards_match_info, TokenShardsMatchStats)
+
+    def set_documents(self, starts):
+        """starts: one table per shard as TokenIndex.set_documents takes it (every table is checked before a shard is touched);
+        None removes the documents from all shards."""
+        if starts is None:
+            check(self._lib.sa_hip_token_shards_set_documents(self._h, None, None))
+            return
+        tabs = []
+        for t in starts:
+            a = np.ascontiguousarray(t)
+            if a.ndim != 1 or a.size == 0 or a.size > 0xFFFFFFFF or (a.dtype.kind not in "iu") or int(a.min()) < 0 or int(a.max()) > 2 ** 31 - 1:
+                raise ValueError("doc_starts: a non-empty 1-d sequence of text positions per shard")
+            tabs.append(a.astype(np.int32))
+        if len(tabs) != self.shards:
+            raise ValueError("one doc_starts table per shard")
+        ptrs = (C.c_void_p * self.shards)(*[a.ctypes.data for a in tabs])
+        sizes = (C.c_uint32 * self.shards)(*[a.size for a in tabs])
+        check(self._lib.sa_hip_token_shards_set_documents(self._h, ptrs, sizes))
+
+    def adopt_documents(self):
+        """Build the set's document table from the documents the shards hold now (set through shard(s), or before create())."""
+        check(self._lib.sa_hip_token_shards_adopt_documents(self._h))
+
+    def doc_bases(self):
+        """-> uint64[S + 1]: the global id of document d of shard s is bases[s] + d; bases[S] = the documents of the set"""
+        out = np.zeros(self.shards + 1, np.uint64)
+        check(self._lib.sa_hip_token_shards_doc_bases(self._h, out.ctypes.data))
+        return out
+
+    def docs_info(self):
+        return self._info(self._lib.sa_hip_token_shards_docs_info, TokenShardsDocsStats)
+
+    def locate_batch_device(self, spans_dev_ptr, q, cap, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr):
+        """(global document uint64, offset int32) of the first cap hits of q contexts from their S * q device spans; asynchronous on
+        the set's stream until sync()."""
+        check(self._lib.sa_hip_token_shards_locate_batch_device(self._h, spans_dev_ptr, q, int(cap), docs_dev_ptr, offsets_dev_ptr,
+                                                                heads_dev_ptr))
+
+    def locate_batch(self, patterns, cap=16, fill=0):
+        """The exact spans of every pattern, then its first cap hits over the shards in shard order.  -> dict: spans [S, Q], docs
+        uint64[Q, cap], offsets int32[Q, cap], heads (written, reserved, count)[Q].  Cells beyond heads['written'] keep `fill`."""
+        buf, off, q = self._contexts(patterns)
+        cap = int(cap)
+        spans, heads = self._shard_rows(q, SPAN_DTYPE), _rows(q, SHARDS_LOCATE_DTYPE)
+        docs, offs = _rows(q, np.uint64, cap, fill), _rows(q, np.int32, cap, fill)
+        self._call(q, self._lib.sa_hip_token_shards_locate_batch, _ptr(buf), _ptr(off), q, cap, _ptr(spans), _ptr(docs), _ptr(offs), _ptr(heads))
+        return {"spans": spans[:, :q], "docs": docs[:q], "offsets": offs[:q], "heads": heads[:q]}
+
+    def docs_batch_device(self, spans_dev_ptr, q, cap, budget, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr):
+        """Distinct documents of q contexts from their S * q device spans (cap 0: counts only, docs and offsets may be None);
+        asynchronous until sync()."""
+        check(self._lib.sa_hip_token_shards_docs_batch_device(self._h, spans_dev_ptr, q, int(cap), int(budget), docs_dev_ptr, offsets_dev_ptr,
+                                                              heads_dev_ptr))
+
+    def docs_batch(self, patterns, cap=16, budget=0, mode=0, max_length=0, need_next=False, fill=0):
+        """Spans as in spans_batch, then the distinct documents among the first `budget` ranks (0: all) of the shards' spans in
+        shard order.  -> dict: spans [S, Q], docs uint64[Q, cap], offsets int32[Q, cap], heads (written, reserved, examined,
+        distinct, count)[Q].  Cells beyond heads['written'] keep `fill`."""
+        buf, off, q = self._contexts(patterns)
+        cap = int(cap)
+        spans, heads = self._shard_rows(q, SPAN_DTYPE), _rows(q, SHARDS_DOCS_DTYPE)
+        docs, offs = _rows(q, np.uint64, cap, fill), _rows(q, np.int32, cap, fill)
+        self._call(q, self._lib.sa_hip_token_shards_docs_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)), cap,
+                   int(budget), _ptr(spans), _ptr(docs), _ptr(offs), _ptr(heads))
+        return {"spans": spans[:, :q], "docs": docs[:q], "offsets": offs[:q], "heads": heads[:q]}
+
+    def docs_merge_device(self, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr, q, cap, out_docs_dev_ptr, out_offsets_dev_ptr, out_heads_dev_ptr,
+                          bases_dev_ptr=None):
+        """The merge step alone, on S * q device lists with shard-local ids (bases_dev_ptr None: the set's own bases); asynchronous
+        on the set's stream until sync()."""
+        check(self._lib.sa_hip_token_shards_docs_merge_device(self._h, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr, bases_dev_ptr, q, int(cap),
+                                                              out_docs_dev_ptr, out_offsets_dev_ptr, out_heads_dev_ptr))
 
 
 def construct_truncated_suffix_array(text, max_suffix_length):

@@ -35,6 +35,7 @@ struct sa_hip_token_index {
     DevBuf d_docs, d_offs, d_heads;          // staging of the host forms
     LaunchTimer tm_lc, tm_dc;                // the last locate / documents launch
     u64 dc_examined = 0;
+    u64 docs_gen = 0;                        // bumped by every set_documents: a shard set compares it with the one it recorded
     // the rank-by-document array, per-document counts and AND groups (token_all.hpp, capi_token_all.hpp)
     tq::DocRanks ranks;
     DevBuf a_goff, a_cnt, a_wr;              // group offsets of the last all launch; staging of the host doc_counts form

@@ -65,6 +65,7 @@ int sa_hip_token_index_set_documents(sa_hip_token_index* t, const int32_t* doc_s
     if (D && (rc = tq::docs_table_check(who, doc_starts_host, D))) return rc;
     std::lock_guard<std::mutex> g(t->mu);
     if (D && (u32)doc_starts_host[D - 1] > t->x.n) return fail(SA_HIP_EINVAL, who, "doc_starts beyond the text");
+    ++t->docs_gen;                                       // whatever follows: a shard set that recorded the old one asks again
     if (D == 0 && t->docs.D == 0) return 0;
     if ((rc = set_device(t->device))) return rc;
     if (D == 0) {

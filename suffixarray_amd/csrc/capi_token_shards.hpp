@@ -1,6 +1,6 @@
 // capi_token_shards.hpp -- the C ABI of the shard set (include/sa_hip.h section 6c), included by sa_capi.hip behind capi_token.hpp
 // (same translation unit).  The kernels are csrc/token_shards.hpp; the per-shard next symbols are tq::launch_next of every shard.
-// Matching statistics over the set: capi_token_shard_match.hpp.
+// Matching statistics over the set: capi_token_shard_match.hpp; documents over the set: capi_token_shard_docs.hpp.
 // The stopwatches, the upload of a host batch and the row copy are capi_token.hpp's; the per-chunk events of the next symbols, summed
 // into two figures, are the set's own.
 #pragma once
@@ -35,6 +35,21 @@ struct sa_hip_token_shards {
     DevBuf m_pos, m_out, m_heads;
     LaunchTimer tm_mt, tm_md;                // the last match launches (q: positions) / match docs launch (q: documents)
     u64 m_last = 0;                          // documents of the last launch of either kind
+    // documents (token_shard_docs.hpp, capi_token_shard_docs.hpp)
+    bool has_docs = false;                   // dtab and dbase describe the shards' documents as of doc_gen
+    u64 doc_gen[tq::SHARDS_MAX] = {};        // every shard's docs_gen when the table was built
+    u64 doc_base[tq::SHARDS_MAX + 1] = {};   // base[s]: documents of the shards in front of s; base[S]: of the set
+    DevBuf dtab, dbase;                      // tq::DocView[S], u64[S + 1]
+    DevBuf d_docs, d_offs, d_heads, d_sum;   // the per-pair lists and heads of one chunk; the counter of the streamed ranks
+    DevBuf od_docs, od_offs, od_heads;       // merged output of one chunk / the locate output (host forms)
+    LaunchTimer tm_lc;                       // the last locate launch
+    std::vector<hipEvent_t> dc_ev;           // 3 per chunk, as nx_ev: before the pair launch, behind it, behind the merge
+    size_t dc_used = 0;
+    bool dc_pending = false;
+    u64 dc_q = 0, dm_q = 0;                  // pairs / contexts of the last pair / merge launches
+    u32 dc_chunk = 0;
+    double dc_ms = 0.0, dm_ms = 0.0;
+    u64 dc_streamed = 0;
 
     const tq::View* table() const { return tab.as<tq::View>(); }
 };
@@ -63,15 +78,17 @@ int shards_launch_spans(sa_hip_token_shards* g, const int32_t* pat, const u64* o
     return 0;
 }
 
-int shards_event(sa_hip_token_shards* g, size_t k) {
-    while (g->nx_ev.size() <= k) {
+// event k of a per-chunk list (nx_ev, dc_ev), created on demand, recorded on the set's stream
+int shards_event(sa_hip_token_shards* g, std::vector<hipEvent_t>& list, size_t k) {
+    while (list.size() <= k) {
         hipEvent_t e = nullptr;
         SA_HIP_CHECK(hipEventCreate(&e));
-        g->nx_ev.push_back(e);
+        list.push_back(e);
     }
-    SA_HIP_CHECK(hipEventRecord(g->nx_ev[k], g->stream));
+    SA_HIP_CHECK(hipEventRecord(list[k], g->stream));
     return 0;
 }
+int shards_event(sa_hip_token_shards* g, size_t k) { return shards_event(g, g->nx_ev, k); }
 
 // Next symbols of the device spans [S * Q], chunk by chunk: every shard's launch_next on its slice, then the merge.  Device
 // outputs (to_host false): written in place.  Host outputs: every chunk is merged into o_* and its written entries copied out.
@@ -144,8 +161,11 @@ void sa_hip_token_shards_destroy(sa_hip_token_shards* g) {
     g->l_sym.release(); g->l_cnt.release(); g->l_heads.release(); g->l_list.release();
     g->o_sym.release(); g->o_cnt.release(); g->o_heads.release();
     g->m_ms.release(); g->m_per.release(); g->m_merged.release(); g->m_pos.release(); g->m_out.release(); g->m_heads.release();
-    g->tm_r.destroy(); g->tm_sp.destroy(); g->tm_mt.destroy(); g->tm_md.destroy();
+    g->dtab.release(); g->dbase.release(); g->d_docs.release(); g->d_offs.release(); g->d_heads.release(); g->d_sum.release();
+    g->od_docs.release(); g->od_offs.release(); g->od_heads.release();
+    g->tm_r.destroy(); g->tm_sp.destroy(); g->tm_mt.destroy(); g->tm_md.destroy(); g->tm_lc.destroy();
     for (hipEvent_t e : g->nx_ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : g->dc_ev) (void)hipEventDestroy(e);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -173,6 +193,7 @@ int sa_hip_token_shards_create(sa_hip_token_shards** out, sa_hip_token_index* co
         SA_HIP_CHECK(g->tm_sp.create());
         SA_HIP_CHECK(g->tm_mt.create());
         SA_HIP_CHECK(g->tm_md.create());
+        SA_HIP_CHECK(g->tm_lc.create());
         tq::View v[tq::SHARDS_MAX];
         for (u32 s = 0; s < S; ++s) {
             std::lock_guard<std::mutex> lk(shards[s]->mu);

@@ -34,8 +34,9 @@
 // [0, D) whatever SA holds (it comes from the binary search), SA entries were range-checked when the handle was prepared.  An
 // in-range array that is not the suffix array gives unspecified entries, never a spin or a read outside the buffers.
 //
-// Not here: one very long span split over several waves.  A wave streams one coalesced array with no gather on the counting
-// path; `budget` is the caller's lever.
+// Not here: one very long span split over several waves inside one index.  A wave streams one coalesced array with no gather on the
+// counting path; `budget` is the caller's lever.  A shard set walks the S pieces of a span by one wave each
+// (token_shard_docs.hpp).
 #pragma once
 #include "token_next.hpp"
 #include "radix_sort.hpp"
@@ -127,7 +128,40 @@ struct DocsArgs {
     unsigned long long* examined;  // one counter: the sum of the heads' examined, what the launch streamed
 };
 
-// One wave per span.  Every trip of the walk advances by DOC_UNROLL windows (the last one by what is left, >= 1 rank).
+// The walk of one wave over the ranks [a0, a0 + examined) of a span (a0 + examined <= n < 2^31): the distinct documents among them,
+// the first min(distinct, cap) of them to docs / offs (never touched when cap == 0).  Every trip advances by DOC_UNROLL windows
+// (the last one by what is left, >= 1 rank).  Shared with tq_shard_docs_kernel (token_shard_docs.hpp).
+__device__ __forceinline__ u32 tq_docs_walk(const View& x, const DocView& d, u32 a0, u32 examined, u32 cap, int32_t* docs, int32_t* offs,
+                                            u32 lane) {
+    const u32 end = a0 + examined;
+    const int32_t first = (int32_t)a0;
+    u32 distinct = 0;
+    for (u32 a = a0; a < end; a += (u32)(DOC_UNROLL * WAVE)) {   // (a + 256 < 2^32: no wrap)
+        int32_t pv[DOC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < DOC_UNROLL; ++u) {
+            const u32 r = a + (u32)u * WAVE + lane;
+            pv[u] = r < end ? d.pv[r] : 0x7FFFFFFF;    // beyond the range: never a head
+        }
+#pragma unroll
+        for (int u = 0; u < DOC_UNROLL; ++u) {
+            const u32 r = a + (u32)u * WAVE + lane;
+            const bool head = r < end && pv[u] < first;
+            const u64 hb = __ballot(head);
+            if (hb == 0) continue;
+            const u32 slot = distinct + (u32)__popcll(hb & lanemask_lt());
+            if (head && slot < cap) {
+                const int32_t doc = d.da[r];
+                docs[slot] = doc;
+                offs[slot] = (int32_t)(x.sa[r] - (u32)d.starts[doc]);
+            }
+            distinct += (u32)__popcll(hb);
+        }
+    }
+    return distinct;
+}
+
+// One wave per span.
 __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_docs_kernel(View x, DocView d, DocsArgs g) {
     const u32 lane = threadIdx.x & (WAVE - 1);
     const u64 waves = (u64)gridDim.x * NEXT_WAVES;
@@ -136,33 +170,7 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_docs_kernel(View x, DocV
         const Walk k = tq_walk_of(x, g.spans[w]);
         const u32 count = k.end - k.a;
         const u32 examined = (g.budget && g.budget < count) ? g.budget : count;
-        const u32 end = k.a + examined;                    // <= n < 2^31
-        const int32_t first = (int32_t)k.a;
-        int32_t* const docs = g.docs + w * g.cap;
-        int32_t* const offs = g.offsets + w * g.cap;
-        u32 distinct = 0;
-        for (u32 a = k.a; a < end; a += (u32)(DOC_UNROLL * WAVE)) {   // (a + 256 < 2^32: no wrap)
-            int32_t pv[DOC_UNROLL];
-#pragma unroll
-            for (int u = 0; u < DOC_UNROLL; ++u) {
-                const u32 r = a + (u32)u * WAVE + lane;
-                pv[u] = r < end ? d.pv[r] : 0x7FFFFFFF;    // beyond the range: never a head
-            }
-#pragma unroll
-            for (int u = 0; u < DOC_UNROLL; ++u) {
-                const u32 r = a + (u32)u * WAVE + lane;
-                const bool head = r < end && pv[u] < first;
-                const u64 hb = __ballot(head);
-                if (hb == 0) continue;
-                const u32 slot = distinct + (u32)__popcll(hb & lanemask_lt());
-                if (head && slot < g.cap) {
-                    const int32_t doc = d.da[r];
-                    docs[slot] = doc;
-                    offs[slot] = (int32_t)(x.sa[r] - (u32)d.starts[doc]);
-                }
-                distinct += (u32)__popcll(hb);
-            }
-        }
+        const u32 distinct = tq_docs_walk(x, d, k.a, examined, g.cap, g.docs + w * g.cap, g.offsets + w * g.cap, lane);
         if (lane == 0) {
             sa_hip_token_docs h;
             h.written = distinct < g.cap ? distinct : g.cap;

@@ -7,9 +7,13 @@
     sti.next_tokens(contexts, cap=64, longest_suffix=True)    # backing off to the longest suffix that ANY shard holds
     sti.matching_statistics([doc])                 # per position: the longest match in any shard, its count, the shards that hold it
     sti.matched_spans([doc], min_length=8)         # the maximal verbatim spans of a text; sti.coverage([doc], 8): how much they cover
+    sti = ShardedTokenIndex([tokens_a, tokens_b], doc_starts=[starts_a, starts_b])     # documents: one table per shard
+    sti.locate([464, 2068], limit=10)              # (document uint64, offset int32): ids count through the shards in order
+    sti.documents([[464, 2068]], cap=16)           # the distinct documents that hold an n-gram, over all shards
+    sti.document_counts([[464, 2068], [11]])       # (document frequency uint64[Q], exact flags)
 
 The corpus is cut by the caller, at document boundaries: an n-gram never spans two shards, so its count is the sum of the shards'
-counts.  On top of include/sa_hip.h section 6c (suffixarray_amd._capi.TokenShards).  No CPU fallback.
+counts.  On top of include/sa_hip.h sections 6c and 6g (suffixarray_amd._capi.TokenShards).  No CPU fallback.
 """
 import numpy as np
 
@@ -17,8 +21,9 @@ from . import _capi
 
 
 class ShardedTokenIndex:
-    def __init__(self, shards, k=None, device=0):
-        """shards: a list of 1 to 64 int sequences or arrays with symbols in [0, k) (k defaults to each shard's max + 1)."""
+    def __init__(self, shards, k=None, device=0, doc_starts=None):
+        """shards: a list of 1 to 64 int sequences or arrays with symbols in [0, k) (k defaults to each shard's max + 1).
+        doc_starts: one table per shard of the first position of every document inside it (see set_documents)."""
         shards = list(shards)
         if not 1 <= len(shards) <= _capi.SHARDS_MAX:
             raise ValueError("a shard set holds 1 to %d shards" % _capi.SHARDS_MAX)
@@ -26,6 +31,12 @@ class ShardedTokenIndex:
         self.shards = self._set.shards
         self._sizes = np.array([self._set.shard(s).info()["n"] for s in range(self.shards)], dtype=np.uint64)
         self.n = int(self._sizes.sum())
+        if doc_starts is not None:
+            try:
+                self.set_documents(doc_starts)
+            except Exception:
+                self._set.close()
+                raise
 
     def shard_sizes(self):
         """tokens of every shard: uint64[S]"""
@@ -104,6 +115,39 @@ class ShardedTokenIndex:
         symbols, longest = its longest match (whatever min_length is), maximal = the number of its maximal spans."""
         h = self._set.match_docs_batch(docs, min_length=min_length, max_length=max_length or 0, cap=0)["heads"]
         return {"covered": h["covered"].copy(), "longest": h["longest"].copy(), "maximal": h["maximal"].copy()}
+
+    def set_documents(self, doc_starts):
+        """doc_starts: per shard, the first position inside the shard of every document (starts[0] == 0, non-decreasing, <= the
+        shard's length; equal neighbours are empty documents).  The documents of the corpus are numbered through the shards in order:
+        document d of shard s is document_bases()[s] + d.  None removes the documents."""
+        self._set.set_documents(None if doc_starts is None else list(doc_starts))
+
+    def document_bases(self):
+        """uint64[S + 1]: the global id of the first document of every shard; the last entry is the number of documents"""
+        return self._set.doc_bases()
+
+    def locate(self, ngram, limit=16):
+        """-> (document uint64, offset int32): where one n-gram occurs (at most `limit` places), in the order of positions():
+        shard-major, suffix order inside a shard"""
+        r = self._set.locate_batch([list(ngram)], cap=max(int(limit), 1))
+        w = min(int(r["heads"]["written"][0]), int(limit))
+        return r["docs"][0, :w].copy(), r["offsets"][0, :w].copy()
+
+    def documents(self, ngrams, cap=16, budget=None, longest_suffix=False, max_length=None):
+        """As TokenIndex.documents over all shards: docs uint64[Q, cap] (global ids: the shards' lists one after another, each in
+        order of first appearance by rank), offsets int32[Q, cap], written, examined, distinct, count (uint64) and exact = the walk
+        saw the whole span, so `distinct` is the document frequency.  budget: the ranks examined, taken from the front of the
+        shards' spans in shard order (None: all)."""
+        r = self._set.docs_batch(ngrams, cap=cap, budget=budget or 0, mode=1 if longest_suffix else 0, max_length=max_length or 0)
+        h = r["heads"]
+        return {"docs": r["docs"], "offsets": r["offsets"], "written": h["written"].copy(), "examined": h["examined"].copy(),
+                "distinct": h["distinct"].copy(), "count": h["count"].copy(), "exact": h["examined"] == h["count"]}
+
+    def document_counts(self, ngrams, budget=None):
+        """-> (document frequency uint64[Q], exact bool[Q]): in how many documents of the corpus every n-gram occurs; with a budget,
+        among its first `budget` hits, and exact says whether those were all"""
+        h = self._set.docs_batch(ngrams, cap=0, budget=budget or 0)["heads"]
+        return h["distinct"].copy(), h["examined"] == h["count"]
 
     def info(self):
         return self._set.info()
