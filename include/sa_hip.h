@@ -714,8 +714,8 @@ int sa_hip_token_index_next_info(const sa_hip_token_index* t, sa_hip_token_next_
  *
  * Matching statistics of a query text over the set -- sa_hip_token_shards_match_* -- stand behind (6f), whose terms and head
  * record they use: see "(6c, matching statistics)" there.  Documents over a set -- locate, the distinct documents of an n-gram and
- * its document frequency, sa_hip_token_shards_locate_* and _docs_* -- are (6g).  Per-document counts and AND groups (6e) over a set
- * are not built. */
+ * its document frequency, sa_hip_token_shards_locate_* and _docs_* -- are (6g).  Per-document counts and AND groups over a set --
+ * sa_hip_token_shards_doc_counts_* and _all_* -- are (6h). */
 typedef struct sa_hip_token_shards sa_hip_token_shards;
 
 typedef struct sa_hip_token_shards_next {
@@ -1136,6 +1136,110 @@ int sa_hip_token_shards_docs_batch(sa_hip_token_shards* set, const int32_t* patt
 int sa_hip_token_shards_docs_merge_device(sa_hip_token_shards* set, const void* docs_dev, const void* offsets_dev, const void* heads_dev,
                                           const void* bases_dev, uint64_t Q, uint32_t cap, void* out_docs_dev, void* out_offsets_dev,
                                           void* out_heads_dev);
+
+/* (6h) per-document counts and AND groups over a shard set (csrc/token_shard_all.hpp, csrc/capi_token_shard_all.hpp): the calls of
+ * (6e) answered for the whole corpus of (6g).  All results are exact.
+ *
+ * Notation of (6g): S shards, base[s] the global id of shard s's first document, a document lives in one shard.  P patterns have the
+ * spans spans[s * P + p] as sa_hip_token_shards_spans_batch_device writes them; c_{s,p} is the count clamped to shard s and
+ * C_p = the sum of the c_{s,p}, a uint64.
+ *
+ * Every shard carries RK of (6e).  sa_hip_token_shards_prepare_doc_ranks(set, 1) calls sa_hip_token_index_prepare_doc_ranks for
+ * every shard, one after another (the sort scratch, 24 n_s bytes, is held for one shard at a time; a no-op per shard where RK is
+ * there), then builds the set's table of the shards' arrays; (set, 0) frees RK in all shards and drops the table.  A set without
+ * documents returns -1.  RK of a shard can be freed or rebuilt through sa_hip_token_shards_shard: every handle counts the
+ * prepare_doc_ranks calls that build or free and the drops caused by set_documents, and every call below compares the counts the set
+ * recorded -- beside the document counts of (6g) -- before any launch; where they differ it returns -1 and the message names
+ * sa_hip_token_shards_prepare_doc_ranks (sa_hip_token_shards_adopt_documents for the documents).  (set, 1) again re-adopts.
+ *
+ *   doc_counts  counts[i * cap + j] = the number of ranks of context i's spans that belong to the document with the global id
+ *               docs[i * cap + j] (uint64), for j below the row's length: written[i] (a uint32 per context, written_stride bytes
+ *               apart: the `written` field of a sa_hip_token_shards_docs[Q] or sa_hip_token_shards_all[G] can be passed as it stands
+ *               with the struct's size as the stride), or cap when written is NULL.  Global id g lives in the shard s with
+ *               base[s] <= g < base[s + 1]; its count is that of (6e) for document g - base[s] of that shard against
+ *               spans[s * Q + i], a uint32.  An id >= base[S] gives 0.  Slots at or beyond a row's length are neither read nor
+ *               written.
+ *   all         the P patterns are cut into G groups by group_offsets[G + 1] (a HOST array in both forms, copied by the call) under
+ *               the rules of (6e).  The driver of a group is its pattern with the smallest C_j over ALL shards, the lowest index on
+ *               a tie: one driver per group, not one per shard.  examined = budget ? min(C_driver, budget) : C_driver ranks are
+ *               taken from the front of the concatenation of the driver's ranges in shard order: shard s examines
+ *               e_s = clamp(budget - (c_{0,driver} + .. + c_{s-1,driver}), 0, c_{s,driver}) ranks.  Per shard the candidates and
+ *               the matches are those of (6e) over these e_s ranks, probing the group's other spans of the same shard; matched and
+ *               candidates are the plain sums over the shards (two shards never share a document).  The list is the shards' lists
+ *               one after another, each in the driver's rank order, global ids, every entry with the offset of the driver's
+ *               smallest-rank occurrence in that document, cut at cap.  cap == 0 counts only; docs and offsets may then be NULL
+ *               and are never touched.  matched is the exact number of documents that hold all n-grams of the group iff
+ *               examined == count.  A group whose driver is empty has an all-zero head apart from `driver`.
+ * Slots beyond `written` are not written.  With S == 1 every answer equals the single index's, the document ids widened.
+ *
+ * The per-pair lists of the all calls live in scratch of the set, S * cap * 8 bytes plus 16 per shard and group (the heads and the
+ * plan alone when cap == 0), worked through in chunks of groups exactly as the docs calls of (6g) are.
+ *
+ * Errors returned as -1 before any HIP call: those of (6e) and (6g) -- a NULL set or a NULL required pointer, a set without
+ * documents or whose shards' documents changed, a bad group table, cap == 0 in doc_counts, a written_stride below 4 or no multiple
+ * of 4, mode or need_next other than 0 / 1, descending offsets -- a set without rank arrays (the message names
+ * sa_hip_token_shards_prepare_doc_ranks), rank arrays that changed behind the set, and P, G * cap or Q * cap >= 2^31; Q == 0 and
+ * G == 0 are no-ops returning 0.  The device forms chain with sa_hip_token_shards_spans_batch_device and
+ * sa_hip_token_shards_docs_batch_device without a host trip and are asynchronous until sa_hip_token_shards_sync; they trust nothing:
+ * first and count are clamped to the shard, every search and every loop is bounded.  The host forms run the span step first (in
+ * mode 1 it gives one length per context for all shards, so a group's n-grams are the same in every shard) and stage through buffers
+ * of the set. */
+typedef struct sa_hip_token_shards_all {
+    uint32_t written;      /* entries written for this group: min(matched, cap)                          */
+    uint32_t driver;       /* index inside the group of the pattern that was walked                      */
+    uint64_t examined;     /* ranks of the driver walked over all shards: budget ? min(count, budget) : count */
+    uint64_t matched;      /* candidates whose document holds every other n-gram of the group            */
+    uint64_t candidates;   /* distinct documents among the examined ranks of the driver                  */
+    uint64_t count;        /* occurrences of the driver over all shards                                  */
+} sa_hip_token_shards_all;
+
+typedef struct sa_hip_token_shards_ranks_stats {
+    uint32_t present;      /* 1: the set holds a table of its shards' RK                                   */
+    uint32_t chunk;        /* groups per chunk of the last all call (0: none yet)                          */
+    uint64_t bytes;        /* of the shards' RK, summed                                                    */
+    double   prepare_ms;   /* device time of the shards' last prepares, summed                             */
+    uint64_t counts_q;     /* contexts of the last doc_counts launch                                       */
+    double   counts_ms;    /* HIP-event time of it (the call waits for it)                                 */
+    uint64_t plan_q;       /* groups of the last all call                                                  */
+    double   plan_ms;      /* HIP-event time of its plan launches, over its chunks                         */
+    uint64_t pairs_q;      /* (group, shard) pairs of the last all call                                    */
+    double   pairs_ms;     /* HIP-event time of its pair launches, over its chunks                         */
+    uint64_t merge_q;      /* groups of the last merge launches                                            */
+    double   merge_ms;     /* HIP-event time of them, over the chunks                                      */
+    uint64_t streamed;     /* sum of the pairs' examined: the ranks the last all call streamed             */
+} sa_hip_token_shards_ranks_stats;
+
+int sa_hip_token_shards_prepare_doc_ranks(sa_hip_token_shards* set, int on);
+int sa_hip_token_shards_doc_ranks_info(const sa_hip_token_shards* set, sa_hip_token_shards_ranks_stats* out);
+/* spans_dev: sa_hip_token_span[S * Q]; docs_dev: uint64[Q * cap]; written_dev: NULL or a uint32 per context, written_stride bytes
+ * apart; counts_dev: uint32[Q * cap]. */
+int sa_hip_token_shards_doc_counts_batch_device(sa_hip_token_shards* set, const void* spans_dev, uint64_t Q, uint32_t cap,
+                                                const void* docs_dev, const void* written_dev, uint64_t written_stride,
+                                                void* counts_dev);
+/* Both steps from host patterns: docs uint64[Q * cap] and written uint32[Q] (may be NULL) in, counts uint32[Q * cap] and
+ * spans[S * Q] (may be NULL) out. */
+int sa_hip_token_shards_doc_counts_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                         int mode, uint32_t max_length, int need_next, uint32_t cap, const uint64_t* docs,
+                                         const uint32_t* written, uint32_t* counts, sa_hip_token_span* spans);
+/* spans_dev: sa_hip_token_span[S * P]; group_offsets_host: uint64[G + 1]; docs_dev: uint64[G * cap], offsets_dev: int32[G * cap]
+ * (may be NULL when cap == 0); heads_dev: sa_hip_token_shards_all[G]. */
+int sa_hip_token_shards_all_batch_device(sa_hip_token_shards* set, const void* spans_dev, uint64_t P,
+                                         const uint64_t* group_offsets_host, uint64_t G, uint32_t cap, uint64_t budget,
+                                         void* docs_dev, void* offsets_dev, void* heads_dev);
+/* Both steps from P host patterns: spans[S * P] (may be NULL), docs, offs and heads[G] out. */
+int sa_hip_token_shards_all_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t P,
+                                  const uint64_t* group_offsets, uint64_t G, int mode, uint32_t max_length, int need_next,
+                                  uint32_t cap, uint64_t budget, sa_hip_token_span* spans, uint64_t* docs, int32_t* offs,
+                                  sa_hip_token_shards_all* heads);
+/* The last step of the two calls above on its own: S lists per group as the pair launch writes them -- docs_dev int32[S * G * cap]
+ * (row (s * G + g) * cap, ids local to the shard), offsets_dev int32[S * G * cap], heads_dev uint32[S * G][4] = {written (clamped
+ * to cap), examined, matched, candidates} -- and plan_dev, per group {uint32 driver, uint32 0, uint64 count} as the plan launch
+ * writes it, into out_docs_dev uint64[G * cap], out_offsets_dev int32[G * cap], out_heads_dev sa_hip_token_shards_all[G].
+ * bases_dev: uint64[S + 1] on the device, or NULL for the set's own (which needs the set's documents).  With cap == 0 the four list
+ * pointers may be NULL.  Needs no rank arrays.  Asynchronous on the set's stream. */
+int sa_hip_token_shards_all_merge_device(sa_hip_token_shards* set, const void* docs_dev, const void* offsets_dev, const void* heads_dev,
+                                         const void* plan_dev, const void* bases_dev, uint64_t G, uint32_t cap, void* out_docs_dev,
+                                         void* out_offsets_dev, void* out_heads_dev);
 
 /* ---- instrumentation ---------------------------------------------------------------------- */
 

@@ -26,6 +26,10 @@ SHARDS_MATCH_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("count", "
 SHARDS_LOCATE_DTYPE = np.dtype([("written", "<u4"), ("reserved", "<u4"), ("count", "<u8")])                  # sa_hip_token_shards_locate
 SHARDS_DOCS_DTYPE = np.dtype([("written", "<u4"), ("reserved", "<u4"), ("examined", "<u8"), ("distinct", "<u8"),
                               ("count", "<u8")])                                                            # sa_hip_token_shards_docs
+SHARDS_ALL_DTYPE = np.dtype([("written", "<u4"), ("driver", "<u4"), ("examined", "<u8"), ("matched", "<u8"), ("candidates", "<u8"),
+                             ("count", "<u8")])                                                             # sa_hip_token_shards_all
+SHARDS_ALL_PAIR_DTYPE = np.dtype([("written", "<u4"), ("examined", "<u4"), ("matched", "<u4"), ("candidates", "<u4")])   # heads_dev of all_merge_device
+SHARDS_ALL_PLAN_DTYPE = np.dtype([("driver", "<u4"), ("reserved", "<u4"), ("count", "<u8")])                  # plan_dev of all_merge_device
 SHARDS_MAX = 64
 UINT32_MAX = 0xFFFFFFFF
 
@@ -66,6 +70,9 @@ EXPORTS = [
     "sa_hip_token_shards_set_documents", "sa_hip_token_shards_adopt_documents", "sa_hip_token_shards_doc_bases",
     "sa_hip_token_shards_docs_info", "sa_hip_token_shards_locate_batch_device", "sa_hip_token_shards_locate_batch",
     "sa_hip_token_shards_docs_batch_device", "sa_hip_token_shards_docs_batch", "sa_hip_token_shards_docs_merge_device",
+    "sa_hip_token_shards_prepare_doc_ranks", "sa_hip_token_shards_doc_ranks_info", "sa_hip_token_shards_doc_counts_batch_device",
+    "sa_hip_token_shards_doc_counts_batch", "sa_hip_token_shards_all_batch_device", "sa_hip_token_shards_all_batch",
+    "sa_hip_token_shards_all_merge_device",
     "sa_hip_last_call_breakdown", "sa_hip_release_workspace",
     "sa_hip_construct_truncated_suffix_array", "sa_hip_get_substring_positions",
     "sa_hip_device_count", "sa_hip_index_create", "sa_hip_index_destroy", "sa_hip_index_build",
@@ -288,6 +295,22 @@ class TokenShardsDocsStats(C.Structure):
     _fields_ = [("documents", C.c_uint64), ("chunk", C.c_uint32), ("reserved", C.c_uint32), ("locate_q", C.c_uint64),
                 ("locate_ms", C.c_double), ("pairs_q", C.c_uint64), ("pairs_ms", C.c_double), ("merge_q", C.c_uint64),
                 ("merge_ms", C.c_double), ("streamed", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenShardsAll(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("driver", C.c_uint32), ("examined", C.c_uint64), ("matched", C.c_uint64),
+                ("candidates", C.c_uint64), ("count", C.c_uint64)]
+
+
+class TokenShardsRanksStats(C.Structure):
+    """sa_hip_token_shards_ranks_stats: the rank-by-document arrays of a shard set and its last doc_counts and all calls."""
+    _fields_ = [("present", C.c_uint32), ("chunk", C.c_uint32), ("bytes", C.c_uint64), ("prepare_ms", C.c_double),
+                ("counts_q", C.c_uint64), ("counts_ms", C.c_double), ("plan_q", C.c_uint64), ("plan_ms", C.c_double),
+                ("pairs_q", C.c_uint64), ("pairs_ms", C.c_double), ("merge_q", C.c_uint64), ("merge_ms", C.c_double),
+                ("streamed", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -654,6 +677,20 @@ def lib():
     L.sa_hip_token_shards_docs_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, u64, vp, vp, vp, vp]
     L.sa_hip_token_shards_docs_merge_device.restype = C.c_int
     L.sa_hip_token_shards_docs_merge_device.argtypes = [vp, vp, vp, vp, vp, u64, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_shards_prepare_doc_ranks.restype = C.c_int
+    L.sa_hip_token_shards_prepare_doc_ranks.argtypes = [vp, C.c_int]
+    L.sa_hip_token_shards_doc_ranks_info.restype = C.c_int
+    L.sa_hip_token_shards_doc_ranks_info.argtypes = [vp, C.POINTER(TokenShardsRanksStats)]
+    L.sa_hip_token_shards_doc_counts_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_doc_counts_batch_device.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, u64, vp]
+    L.sa_hip_token_shards_doc_counts_batch.restype = C.c_int
+    L.sa_hip_token_shards_doc_counts_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_shards_all_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_all_batch_device.argtypes = [vp, vp, u64, vp, u64, C.c_uint32, u64, vp, vp, vp]
+    L.sa_hip_token_shards_all_batch.restype = C.c_int
+    L.sa_hip_token_shards_all_batch.argtypes = [vp, vp, vp, u64, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, u64, vp, vp, vp, vp]
+    L.sa_hip_token_shards_all_merge_device.restype = C.c_int
+    L.sa_hip_token_shards_all_merge_device.argtypes = [vp, vp, vp, vp, vp, vp, u64, C.c_uint32, vp, vp, vp]
     L.sa_hip_sort_pairs.restype = C.c_int
     L.sa_hip_sort_pairs.argtypes = [vp, vp, u64, C.c_int, C.c_int, C.c_int]
     L.sa_hip_synth_uniform27.restype = None
@@ -1798,6 +1835,67 @@ class TokenShards(_TokenHandle):
         on the set's stream until sync()."""
         check(self._lib.sa_hip_token_shards_docs_merge_device(self._h, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr, bases_dev_ptr, q, int(cap),
                                                               out_docs_dev_ptr, out_offsets_dev_ptr, out_heads_dev_ptr))
+
+    def prepare_doc_ranks(self, on=True):
+        """Build the rank-by-document array of every shard, one after another, and the set's table of them (or, with on=False,
+        free them all); a no-op per shard where the array is there.  Replacing or removing the documents drops them."""
+        check(self._lib.sa_hip_token_shards_prepare_doc_ranks(self._h, int(bool(on))))
+
+    def doc_ranks_info(self):
+        return self._info(self._lib.sa_hip_token_shards_doc_ranks_info, TokenShardsRanksStats)
+
+    def doc_counts_batch_device(self, spans_dev_ptr, q, cap, docs_dev_ptr, written_dev_ptr, written_stride, counts_dev_ptr):
+        """counts[i, j] = occurrences of context i (its S device spans) inside the document with the global id docs[i, j] (uint64),
+        j below the row's length (written_dev_ptr None: cap); asynchronous on the set's stream until sync()."""
+        check(self._lib.sa_hip_token_shards_doc_counts_batch_device(self._h, spans_dev_ptr, q, int(cap), docs_dev_ptr, written_dev_ptr,
+                                                                    int(written_stride), counts_dev_ptr))
+
+    def doc_counts_batch(self, patterns, docs, written=None, mode=0, max_length=0, need_next=False, fill=0):
+        """Spans as in spans_batch, then how often every context occurs in the documents of its row.  docs: uint64[Q, cap] global
+        ids; written: uint32[Q] row lengths or None.  -> dict: spans [S, Q], counts uint32[Q, cap].  Cells beyond a row's length
+        keep `fill`."""
+        buf, off, q = self._contexts(patterns)
+        docs = np.ascontiguousarray(docs, dtype=np.uint64)
+        if docs.ndim != 2 or docs.shape[0] != q:
+            raise ValueError("docs: one row of document ids per pattern")
+        cap = docs.shape[1]
+        if written is not None:
+            written = np.ascontiguousarray(written, dtype=np.uint32)
+            if written.shape != (q,):
+                raise ValueError("written: one row length per pattern")
+        spans, counts = self._shard_rows(q, SPAN_DTYPE), _rows(q, np.uint32, cap, fill)
+        self._call(q, self._lib.sa_hip_token_shards_doc_counts_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)),
+                   cap, docs.ctypes.data, _ptr(written), counts.ctypes.data, _ptr(spans))
+        return {"spans": spans[:, :q], "counts": counts[:q]}
+
+    def all_batch_device(self, spans_dev_ptr, p, group_offsets, cap, budget, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr):
+        """Documents of the corpus holding all patterns of every group, from the S * p device spans; group_offsets is a HOST
+        uint64[G + 1] (copied by the call), everything else on the device (cap 0: counts only, docs and offsets may be None);
+        asynchronous until sync()."""
+        go = np.ascontiguousarray(group_offsets, dtype=np.uint64)
+        check(self._lib.sa_hip_token_shards_all_batch_device(self._h, spans_dev_ptr, int(p), go.ctypes.data, go.size - 1, int(cap), int(budget),
+                                                             docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr))
+
+    def all_batch(self, patterns, group_offsets, cap=16, budget=0, mode=0, max_length=0, need_next=False, fill=0):
+        """Spans as in spans_batch, cut into groups by group_offsets (uint64[G + 1]: 0 .. P, 1 .. TOKEN_ALL_MAX patterns each), then
+        the documents that hold every pattern of a group.  -> dict: spans [S, P], docs uint64[G, cap], offsets int32[G, cap], heads
+        (written, driver, examined, matched, candidates, count)[G].  Cells beyond heads['written'] keep `fill`."""
+        buf, off, p = self._contexts(patterns)
+        go = np.ascontiguousarray(group_offsets, dtype=np.uint64)
+        g = max(go.size - 1, 0)
+        cap = int(cap)
+        spans, heads = self._shard_rows(p, SPAN_DTYPE), _rows(g, SHARDS_ALL_DTYPE)
+        docs, offs = _rows(g, np.uint64, cap, fill), _rows(g, np.int32, cap, fill)
+        self._call(g, self._lib.sa_hip_token_shards_all_batch, _ptr(buf), _ptr(off), p, go.ctypes.data, g, int(mode), int(max_length),
+                   int(bool(need_next)), cap, int(budget), _ptr(spans), _ptr(docs), _ptr(offs), _ptr(heads))
+        return {"spans": spans[:, :p], "docs": docs[:g], "offsets": offs[:g], "heads": heads[:g]}
+
+    def all_merge_device(self, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr, plan_dev_ptr, g, cap, out_docs_dev_ptr, out_offsets_dev_ptr,
+                         out_heads_dev_ptr, bases_dev_ptr=None):
+        """The merge step of all_batch alone, on S * g device lists with shard-local ids, their heads (SHARDS_ALL_PAIR_DTYPE) and the
+        per-group plan (SHARDS_ALL_PLAN_DTYPE); bases_dev_ptr None: the set's own bases.  Asynchronous until sync()."""
+        check(self._lib.sa_hip_token_shards_all_merge_device(self._h, docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr, plan_dev_ptr, bases_dev_ptr,
+                                                             g, int(cap), out_docs_dev_ptr, out_offsets_dev_ptr, out_heads_dev_ptr))
 
 
 def construct_truncated_suffix_array(text, max_suffix_length):

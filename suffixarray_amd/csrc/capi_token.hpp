@@ -38,6 +38,7 @@ struct sa_hip_token_index {
     u64 docs_gen = 0;                        // bumped by every set_documents: a shard set compares it with the one it recorded
     // the rank-by-document array, per-document counts and AND groups (token_all.hpp, capi_token_all.hpp)
     tq::DocRanks ranks;
+    u64 ranks_gen = 0;                       // bumped whenever RK is built, freed or dropped: a shard set compares it as it does docs_gen
     DevBuf a_goff, a_cnt, a_wr;              // group offsets of the last all launch; staging of the host doc_counts form
     u32* a_goff_pin = nullptr;               // pinned: what the asynchronous copy into a_goff reads
     size_t a_goff_pin_cap = 0;               // ... in entries

@@ -41,10 +41,10 @@ int token_launch_tf(sa_hip_token_index* t, const sa_hip_token_span* spans, u64 Q
     return t->tm_tf.end(t->stream, Q);
 }
 
-// the checked table goes through a pinned buffer of the handle, so the caller's array is free when the call returns and the
-// launch stays asynchronous
-int token_launch_all(sa_hip_token_index* t, const sa_hip_token_span* spans, const uint64_t* goff, u64 G, u32 cap, u32 budget,
-                     int32_t* docs, int32_t* offs, sa_hip_token_all* heads) {
+// The checked group table of a handle or of a shard set (both name the members alike) into a_goff through its pinned buffer, so
+// the caller's array is free when the call returns and the launch stays asynchronous.
+template <class Owner>
+int token_stage_groups(Owner* t, const uint64_t* goff, u64 G) {
     int rc;
     if (t->a_copy_pending) {
         SA_HIP_CHECK(hipEventSynchronize(t->a_copied));
@@ -61,6 +61,13 @@ int token_launch_all(sa_hip_token_index* t, const sa_hip_token_span* spans, cons
     SA_HIP_CHECK(hipMemcpyAsync(t->a_goff.p, t->a_goff_pin, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, t->stream));
     SA_HIP_CHECK(hipEventRecord(t->a_copied, t->stream));
     t->a_copy_pending = true;
+    return 0;
+}
+
+int token_launch_all(sa_hip_token_index* t, const sa_hip_token_span* spans, const uint64_t* goff, u64 G, u32 cap, u32 budget,
+                     int32_t* docs, int32_t* offs, sa_hip_token_all* heads) {
+    int rc;
+    if ((rc = token_stage_groups(t, goff, G))) return rc;
     const tq::AllArgs g{spans, t->a_goff.as<u32>(), G, cap, budget, docs, offs, heads};
     if ((rc = t->tm_al.begin(t->stream)) || (rc = tq::launch_all(t->x, t->docs, t->ranks, t->stream, g))) return rc;
     return t->tm_al.end(t->stream, G);
@@ -80,12 +87,14 @@ int sa_hip_token_index_prepare_doc_ranks(sa_hip_token_index* t, int on) {
         if (!t->ranks.have) return 0;
         if ((rc = set_device(t->device))) return rc;
         SA_HIP_CHECK(hipStreamSynchronize(t->stream));   // launches that read the array
+        ++t->ranks_gen;
         t->ranks.clear();
         return 0;
     }
     if ((rc = token_has_docs(t, who))) return rc;
     if (t->ranks.have) return 0;
     if ((rc = set_device(t->device))) return rc;
+    ++t->ranks_gen;                                      // whatever follows: a shard set that recorded the old one asks again
     return t->ranks.build(t->x, t->docs, t->stream, who);
 }
 

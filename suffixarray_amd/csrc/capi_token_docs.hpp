@@ -71,10 +71,12 @@ int sa_hip_token_index_set_documents(sa_hip_token_index* t, const int32_t* doc_s
     if (D == 0) {
         SA_HIP_CHECK(hipStreamSynchronize(t->stream));   // launches that read the table
         t->docs.clear();
+        if (t->ranks.have) ++t->ranks_gen;
         t->ranks.clear();
         return 0;
     }
     SA_HIP_CHECK(hipStreamSynchronize(t->stream));       // launches that read the rank-by-document array of the table being replaced
+    if (t->ranks.have) ++t->ranks_gen;
     t->ranks.clear();
     return t->docs.build(t->x, t->stream, doc_starts_host, D, who);
 }

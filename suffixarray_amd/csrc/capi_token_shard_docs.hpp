@@ -155,6 +155,7 @@ int sa_hip_token_shards_set_documents(sa_hip_token_shards* g, const int32_t* con
     if ((rc = set_device(g->device))) return rc;
     SA_HIP_CHECK(hipStreamSynchronize(g->stream));       // launches of the set that read the tables being replaced
     g->has_docs = false;
+    g->has_ranks = false;                                // every shard drops its rank-by-document array with its documents
     for (u32 s = 0; s < g->S; ++s)
         if ((rc = sa_hip_token_index_set_documents(g->shard[s], starts ? starts[s] : nullptr, starts ? D[s] : 0))) return rc;
     if (!starts) { g->doc_base[g->S] = 0; return 0; }

@@ -1,6 +1,7 @@
 // capi_token_shards.hpp -- the C ABI of the shard set (include/sa_hip.h section 6c), included by sa_capi.hip behind capi_token.hpp
 // (same translation unit).  The kernels are csrc/token_shards.hpp; the per-shard next symbols are tq::launch_next of every shard.
-// Matching statistics over the set: capi_token_shard_match.hpp; documents over the set: capi_token_shard_docs.hpp.
+// Matching statistics over the set: capi_token_shard_match.hpp; documents over the set: capi_token_shard_docs.hpp; per-document
+// counts and AND groups over the set: capi_token_shard_all.hpp.
 // The stopwatches, the upload of a host batch and the row copy are capi_token.hpp's; the per-chunk events of the next symbols, summed
 // into two figures, are the set's own.
 #pragma once
@@ -50,6 +51,27 @@ struct sa_hip_token_shards {
     u32 dc_chunk = 0;
     double dc_ms = 0.0, dm_ms = 0.0;
     u64 dc_streamed = 0;
+    // per-document counts and AND groups (token_shard_all.hpp, capi_token_shard_all.hpp)
+    bool has_ranks = false;                  // rtab describes the shards' rank-by-document arrays as of rank_gen
+    u64 rank_gen[tq::SHARDS_MAX] = {};       // every shard's ranks_gen when the table was built
+    DevBuf rtab;                             // tq::RankView[S]
+    DevBuf a_docs, a_offs, a_heads;          // the per-pair lists and heads of one chunk
+    DevBuf a_plan, a_groups, a_sum;          // the plan of one chunk: per pair, per group; the counter of the streamed ranks
+    DevBuf oa_heads;                         // merged heads of one chunk (host form; the lists go through od_docs / od_offs)
+    DevBuf c_docs, c_cnt, c_wr;              // staging of the host doc_counts form
+    DevBuf a_goff;                           // group offsets of the last all call
+    u32* a_goff_pin = nullptr;               // pinned: what the asynchronous copy into a_goff reads
+    size_t a_goff_pin_cap = 0;               // ... in entries
+    hipEvent_t a_copied = nullptr;           // that copy is done: the pinned buffer may be rewritten
+    bool a_copy_pending = false;
+    LaunchTimer tm_tf;                       // the last doc_counts launch
+    std::vector<hipEvent_t> al_ev;           // 4 per chunk: before the plan launch, behind it, behind the pair launch, behind the merge
+    size_t al_used = 0;
+    bool al_pending = false;
+    u64 al_q = 0, al_pairs_q = 0;            // groups / pairs of the last all call
+    u32 al_chunk = 0;
+    double al_plan_ms = 0.0, al_pairs_ms = 0.0, al_merge_ms = 0.0;
+    u64 al_streamed = 0;
 
     const tq::View* table() const { return tab.as<tq::View>(); }
 };
@@ -163,6 +185,12 @@ void sa_hip_token_shards_destroy(sa_hip_token_shards* g) {
     g->m_ms.release(); g->m_per.release(); g->m_merged.release(); g->m_pos.release(); g->m_out.release(); g->m_heads.release();
     g->dtab.release(); g->dbase.release(); g->d_docs.release(); g->d_offs.release(); g->d_heads.release(); g->d_sum.release();
     g->od_docs.release(); g->od_offs.release(); g->od_heads.release();
+    g->rtab.release(); g->a_docs.release(); g->a_offs.release(); g->a_heads.release(); g->a_plan.release(); g->a_groups.release();
+    g->a_sum.release(); g->oa_heads.release(); g->c_docs.release(); g->c_cnt.release(); g->c_wr.release(); g->a_goff.release();
+    if (g->a_goff_pin) (void)hipHostFree(g->a_goff_pin);
+    if (g->a_copied) (void)hipEventDestroy(g->a_copied);
+    g->tm_tf.destroy();
+    for (hipEvent_t e : g->al_ev) (void)hipEventDestroy(e);
     g->tm_r.destroy(); g->tm_sp.destroy(); g->tm_mt.destroy(); g->tm_md.destroy(); g->tm_lc.destroy();
     for (hipEvent_t e : g->nx_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : g->dc_ev) (void)hipEventDestroy(e);
@@ -194,6 +222,8 @@ int sa_hip_token_shards_create(sa_hip_token_shards** out, sa_hip_token_index* co
         SA_HIP_CHECK(g->tm_mt.create());
         SA_HIP_CHECK(g->tm_md.create());
         SA_HIP_CHECK(g->tm_lc.create());
+        SA_HIP_CHECK(g->tm_tf.create());
+        SA_HIP_CHECK(hipEventCreate(&g->a_copied));
         tq::View v[tq::SHARDS_MAX];
         for (u32 s = 0; s < S; ++s) {
             std::lock_guard<std::mutex> lk(shards[s]->mu);

@@ -26,7 +26,7 @@
 // lands at its segment's end is never dereferenced (in the last document that end is RK[n]).
 //
 // Not here: OR clauses (CNF with more than one literal), one very long driver split over several waves, a per-wave queue of
-// candidates probed 64 at a time, the shard sets.
+// candidates probed 64 at a time.  The shard sets: token_shard_all.hpp.
 #pragma once
 #include "token_docs.hpp"
 #include "scan.hpp"
@@ -103,7 +103,55 @@ struct AllArgs {
     sa_hip_token_all* heads;          // [G]
 };
 
-// One wave per group.  Every trip of the walk advances by DOC_UNROLL windows (the last one by what is left, >= 1 rank).
+// The walk of one wave over the ranks [first_u, first_u + examined) of a group's driver (first_u + examined <= n < 2^31): the
+// candidates among them are counted into `candidates`, the matches are returned and the first min(matched, cap) of them go to docs /
+// offs (never touched when cap == 0).  sp: the group's m <= ALL_MAX spans.  Every trip advances by DOC_UNROLL windows (the last one
+// by what is left, >= 1 rank).  Shared with tq_shard_all_kernel (token_shard_all.hpp).
+__device__ __forceinline__ u32 tq_all_walk(const View& x, const RankView& d, const sa_hip_token_span* sp, u32 m, u32 driver, u32 first_u,
+                                           u32 examined, u32 cap, int32_t* docs, int32_t* offs, u32 lane, u32& candidates) {
+    const u32 end = first_u + examined;                    // <= n < 2^31
+    const int32_t first = (int32_t)first_u;
+    u32 matched = 0;
+    for (u32 a = first_u; a < end; a += (u32)(DOC_UNROLL * WAVE)) {   // (a + 256 < 2^32: no wrap)
+        int32_t pv[DOC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < DOC_UNROLL; ++u) {
+            const u32 r = a + (u32)u * WAVE + lane;
+            pv[u] = r < end ? d.pv[r] : 0x7FFFFFFF;        // beyond the range: never a candidate
+        }
+#pragma unroll
+        for (int u = 0; u < DOC_UNROLL; ++u) {
+            const u32 r = a + (u32)u * WAVE + lane;
+            const bool cand = r < end && pv[u] < first;
+            const u64 cb = __ballot(cand);
+            if (cb == 0) continue;
+            candidates += (u32)__popcll(cb);
+            bool match = cand;
+            int32_t doc = 0;
+            if (cand) {                                    // no cross-lane operation inside: the lanes diverge here
+                doc = d.da[r];
+                const u32 g0 = (u32)d.starts[doc], g1 = (u32)d.starts[doc + 1];
+                for (u32 j = 0; j < m && match; ++j) {
+                    if (j == driver) continue;
+                    const Walk o = tq_walk_of(x, sp[j]);   // the same address in every lane
+                    const u32 at = tq_seg_lower(d.rk, g0, g1, o.a);
+                    match = at < g1 && (u32)d.rk[at] < o.end;
+                }
+            }
+            const u64 mb = __ballot(match);
+            if (mb == 0) continue;
+            const u32 slot = matched + (u32)__popcll(mb & lanemask_lt());
+            if (match && slot < cap) {
+                docs[slot] = doc;
+                offs[slot] = (int32_t)(x.sa[r] - (u32)d.starts[doc]);
+            }
+            matched += (u32)__popcll(mb);
+        }
+    }
+    return matched;
+}
+
+// One wave per group.
 __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_all_kernel(View x, RankView d, AllArgs g) {
     const u32 lane = threadIdx.x & (WAVE - 1);
     const u64 waves = (u64)gridDim.x * NEXT_WAVES;
@@ -120,47 +168,9 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_all_kernel(View x, RankV
         const u32 driver = m ? (u32)best : 0u, count = m ? (u32)(best >> 32) : 0u;   // (m == 0: the host refused such a table)
         const u32 first_u = __shfl(mine.a, (int)driver);
         const u32 examined = (g.budget && g.budget < count) ? g.budget : count;
-        const u32 end = first_u + examined;                // <= n < 2^31
-        const int32_t first = (int32_t)first_u;
-        int32_t* const docs = g.docs + w * g.cap;
-        int32_t* const offs = g.offsets + w * g.cap;
-        u32 candidates = 0, matched = 0;
-        for (u32 a = first_u; a < end; a += (u32)(DOC_UNROLL * WAVE)) {   // (a + 256 < 2^32: no wrap)
-            int32_t pv[DOC_UNROLL];
-#pragma unroll
-            for (int u = 0; u < DOC_UNROLL; ++u) {
-                const u32 r = a + (u32)u * WAVE + lane;
-                pv[u] = r < end ? d.pv[r] : 0x7FFFFFFF;    // beyond the range: never a candidate
-            }
-#pragma unroll
-            for (int u = 0; u < DOC_UNROLL; ++u) {
-                const u32 r = a + (u32)u * WAVE + lane;
-                const bool cand = r < end && pv[u] < first;
-                const u64 cb = __ballot(cand);
-                if (cb == 0) continue;
-                candidates += (u32)__popcll(cb);
-                bool match = cand;
-                int32_t doc = 0;
-                if (cand) {                                // no cross-lane operation inside: the lanes diverge here
-                    doc = d.da[r];
-                    const u32 g0 = (u32)d.starts[doc], g1 = (u32)d.starts[doc + 1];
-                    for (u32 j = 0; j < m && match; ++j) {
-                        if (j == driver) continue;
-                        const Walk o = tq_walk_of(x, sp[j]);   // the same address in every lane
-                        const u32 at = tq_seg_lower(d.rk, g0, g1, o.a);
-                        match = at < g1 && (u32)d.rk[at] < o.end;
-                    }
-                }
-                const u64 mb = __ballot(match);
-                if (mb == 0) continue;
-                const u32 slot = matched + (u32)__popcll(mb & lanemask_lt());
-                if (match && slot < g.cap) {
-                    docs[slot] = doc;
-                    offs[slot] = (int32_t)(x.sa[r] - (u32)d.starts[doc]);
-                }
-                matched += (u32)__popcll(mb);
-            }
-        }
+        u32 candidates = 0;
+        const u32 matched = tq_all_walk(x, d, sp, m, driver, first_u, examined, g.cap, g.docs + w * g.cap, g.offsets + w * g.cap, lane,
+                                        candidates);
         if (lane == 0) {
             sa_hip_token_all h;
             h.written = matched < g.cap ? matched : g.cap;

@@ -11,9 +11,12 @@
     sti.locate([464, 2068], limit=10)              # (document uint64, offset int32): ids count through the shards in order
     sti.documents([[464, 2068]], cap=16)           # the distinct documents that hold an n-gram, over all shards
     sti.document_counts([[464, 2068], [11]])       # (document frequency uint64[Q], exact flags)
+    sti.term_counts([[464, 2068]], [0, 7, 2 ** 33])              # occurrences per document (global ids): uint32[Q, len(docs)]
+    sti.documents_with_all([[[464, 2068], [11]]], cap=16)        # AND: documents of the corpus holding every n-gram of a group
+    sti.count_documents_with_all([[[464, 2068], [11]]])          # (matched uint64[G], exact flags)
 
 The corpus is cut by the caller, at document boundaries: an n-gram never spans two shards, so its count is the sum of the shards'
-counts.  On top of include/sa_hip.h sections 6c and 6g (suffixarray_amd._capi.TokenShards).  No CPU fallback.
+counts.  On top of include/sa_hip.h sections 6c, 6g and 6h (suffixarray_amd._capi.TokenShards).  No CPU fallback.
 """
 import numpy as np
 
@@ -148,6 +151,56 @@ class ShardedTokenIndex:
         among its first `budget` hits, and exact says whether those were all"""
         h = self._set.docs_batch(ngrams, cap=0, budget=budget or 0)["heads"]
         return h["distinct"].copy(), h["examined"] == h["count"]
+
+    def prepare_document_ranks(self):
+        """Build every shard's rank-by-document array (4 bytes per token) and the set's table of them, which term_counts and
+        documents_with_all need; they call this on first use.  set_documents drops the arrays."""
+        self._set.prepare_doc_ranks(True)
+
+    def term_counts(self, ngrams, docs):
+        """-> uint32[len(ngrams), len(docs)]: how often n-gram i occurs in document docs[j] (global ids, as document_bases()
+        numbers them); an id at or beyond the number of documents counts 0."""
+        ids = [int(d) for d in np.asarray(docs, dtype=object).reshape(-1)]
+        if any(d < 0 or d >= 2 ** 64 for d in ids):
+            raise ValueError("docs: document ids are uint64")
+        ids = np.array(ids, dtype=np.uint64)
+        buf, off = self._set._packed(ngrams)
+        q = max(off.size - 1, 0)
+        if q == 0 or ids.size == 0:
+            return np.zeros((q, ids.size), np.uint32)
+        self.prepare_document_ranks()
+        rows = np.ascontiguousarray(np.broadcast_to(ids, (q, ids.size)))
+        return self._set.doc_counts_batch((buf, off), rows)["counts"]
+
+    def documents_with_all(self, groups, cap=16, budget=None, longest_suffix=False, max_length=None):
+        """As TokenIndex.documents_with_all over all shards.  -> one dict per group: documents (uint64 global ids) and offsets (int32),
+        at most cap entries: the shards' matches one after another, each in the rank order of the group's rarest n-gram over the
+        whole corpus, with the offset of that n-gram's smallest-rank occurrence in the document; matched (a Python int: documents
+        matched among the first `budget` occurrences of that n-gram, taken in shard order), exact (these were all its occurrences,
+        so matched is the number of documents that hold all n-grams), driver (the index of that n-gram inside the group)."""
+        from .token_index import TokenIndex
+        flat, goff = TokenIndex._grouped(groups)
+        if not len(groups):
+            return []
+        self.prepare_document_ranks()
+        r = self._set.all_batch(flat, goff, cap=cap, budget=budget or 0, mode=1 if longest_suffix else 0, max_length=max_length or 0,
+                                need_next=False)
+        out = []
+        for i, h in enumerate(r["heads"]):
+            w = int(h["written"])
+            out.append({"documents": r["docs"][i, :w].copy(), "offsets": r["offsets"][i, :w].copy(), "matched": int(h["matched"]),
+                        "exact": bool(h["examined"] == h["count"]), "driver": int(h["driver"])})
+        return out
+
+    def count_documents_with_all(self, groups, budget=None):
+        """-> (matched uint64[G], exact bool[G]): in how many documents of the corpus all n-grams of every group occur"""
+        from .token_index import TokenIndex
+        flat, goff = TokenIndex._grouped(groups)
+        if not len(groups):
+            return np.zeros(0, np.uint64), np.zeros(0, np.bool_)
+        self.prepare_document_ranks()
+        h = self._set.all_batch(flat, goff, cap=0, budget=budget or 0)["heads"]
+        return h["matched"].copy(), h["examined"] == h["count"]
 
     def info(self):
         return self._set.info()
