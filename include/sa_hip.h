@@ -1241,6 +1241,76 @@ int sa_hip_token_shards_all_merge_device(sa_hip_token_shards* set, const void* d
                                          const void* plan_dev, const void* bases_dev, uint64_t G, uint32_t cap, void* out_docs_dev,
                                          void* out_offsets_dev, void* out_heads_dev);
 
+/* (6i) infinity-gram scores (csrc/token_score.hpp, csrc/capi_token_score.hpp): the probability the corpus gives every token of a
+ * query text under the model "the longest context that occurs, and what followed it".  For every position the length of that
+ * context, how often it occurs with a token behind it, and how often that token is the one in the text; per query document the
+ * sums a perplexity needs.  All results are exact; no floating point is computed on the device.
+ *
+ * The batch layout is that of (6f): Q query documents, document d = patterns[offsets[d] .. offsets[d + 1]), offsets non-decreasing,
+ * a position a flat index j, total = offsets[Q], M = max_length (0: no cap), s(j) the start of j's document.  The effective count
+ * of a context is count - ended as in mode 1 of (6b) with need_next = 1: its occurrences that have a token behind them; the empty
+ * context has n.  For a position j inside a document, scores[j] =
+ *   length         L(j): the largest L <= min(j - s(j), M, n) such that patterns[j - L .. j) has an effective count >= 1;
+ *   context_count  that effective count: >= 1 whenever n >= 1;
+ *   token_count    the occurrences of patterns[j - L .. j], the same context with the token at j appended: <= context_count, and 0
+ *                  for a token outside the alphabet;
+ *   first          the `first` of that (L + 1)-gram's range as sa_hip_token_index_query_batch gives it, exact also when token_count
+ *                  is 0: {first, token_count, L + 1} is a span that sa_hip_token_index_locate_* and _next_* take.
+ * The token's probability is token_count / context_count.  With n == 0 every record is {0, 0, 0, 0}, as is that of a position
+ * outside every document (j < offsets[0]).  Per document the docs step gives the head {scored = its positions, seen = those with
+ * token_count > 0, certain = those with token_count == context_count, longest = the largest length, length_sum = the sum of the
+ * lengths}; an empty document has a head of zeros (and with n == 0, where every record is zero, certain == scored).
+ *
+ * spans_dev of the score call is NULL, or the matches sa_hip_token_index_match_batch_device wrote for the SAME batch and the SAME
+ * max_length.  With them the start of the context comes from a binary search over these records and one range search (where the
+ * context is the corpus's tail and occurs nowhere else, a search over the shorter contexts follows); without them, from a binary
+ * search over L with one range search per probe.  Both give the same records, byte for byte.  The host form takes the first way
+ * and runs the match launch itself, into a buffer of the handle.
+ *
+ * Cost: as in (6f) a search step compares as many symbols as its suffix shares with the context, so a text copied verbatim from
+ * the corpus costs about m * min(m, M) * log2 n symbol reads for its m positions.  max_length is the caller's lever.
+ *
+ * Errors returned as -1 before any HIP call: a NULL handle or a NULL required pointer, total >= 2^31, in the host form descending
+ * offsets and scores and heads both NULL; Q == 0 is a no-op returning 0; no usable device -3.  The device forms are asynchronous
+ * on the handle's stream until sa_hip_token_index_sync and chain behind sa_hip_token_index_match_batch_device without a host trip;
+ * they trust nothing: every loop is bounded, a context's start is clamped to its document and to the batch, and records that no
+ * match launch wrote or an array that is not the suffix array give unspecified answers.  The host form stages through buffers of
+ * the handle. */
+typedef struct sa_hip_token_score {
+    uint32_t length;          /* L(j): symbols of the context                                         */
+    uint32_t context_count;   /* occurrences of the context that have a token behind them             */
+    uint32_t token_count;     /* occurrences of the context followed by the token at j                */
+    uint32_t first;           /* suffixes that sort before the context followed by the token at j     */
+} sa_hip_token_score;
+
+typedef struct sa_hip_token_score_head {
+    uint32_t scored;          /* positions of the document                                            */
+    uint32_t seen;            /* those with token_count > 0                                           */
+    uint32_t certain;         /* those with token_count == context_count                              */
+    uint32_t longest;         /* the largest length                                                   */
+    uint64_t length_sum;      /* the sum of the lengths                                               */
+} sa_hip_token_score_head;
+
+typedef struct sa_hip_token_score_info {
+    uint64_t q;               /* documents of the last launch of either kind                          */
+    uint64_t positions;       /* positions of the last score launch                                   */
+    double   match_ms;        /* HIP-event time of the last match launch (the call waits for it)      */
+    double   score_ms;        /* ... of the last score launch                                         */
+    double   docs_ms;         /* ... of the last score docs launch                                    */
+} sa_hip_token_score_info;
+
+/* spans_dev: NULL, or sa_hip_token_span[total] as sa_hip_token_index_match_batch_device wrote them for this batch and max_length;
+ * scores_dev: sa_hip_token_score[total], total = offsets[Q], index = position in patterns. */
+int sa_hip_token_index_score_batch_device(sa_hip_token_index* t, const void* patterns_dev, const void* offsets_dev, uint64_t Q,
+                                          uint64_t total, uint32_t max_length, const void* spans_dev, void* scores_dev);
+/* scores_dev as the call above writes them (may be NULL when every document is empty); heads_dev: sa_hip_token_score_head[Q]. */
+int sa_hip_token_index_score_docs_batch_device(sa_hip_token_index* t, const void* scores_dev, const void* offsets_dev, uint64_t Q,
+                                               void* heads_dev);
+/* Host pointers; scores[offsets[Q]] and heads[Q] out, either may be NULL, not both. */
+int sa_hip_token_index_score_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                   uint32_t max_length, sa_hip_token_score* scores, sa_hip_token_score_head* heads);
+int sa_hip_token_index_score_info(const sa_hip_token_index* t, sa_hip_token_score_info* out);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 
 /* Per-build statistics of the last build on this handle (roofline accounting). */

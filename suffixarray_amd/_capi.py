@@ -20,6 +20,9 @@ DOCS_DTYPE = np.dtype([("written", "<u4"), ("examined", "<u4"), ("distinct", "<u
 ALL_DTYPE = np.dtype([("written", "<u4"), ("examined", "<u4"), ("matched", "<u4"), ("candidates", "<u4"), ("driver", "<u4"),
                       ("count", "<u4"), ("reserved", "<u4", (2,))])                                           # sa_hip_token_all
 MATCH_HEAD_DTYPE = np.dtype([("written", "<u4"), ("maximal", "<u4"), ("longest", "<u4"), ("covered", "<u4")])  # sa_hip_token_match_head
+SCORE_DTYPE = np.dtype([("length", "<u4"), ("context_count", "<u4"), ("token_count", "<u4"), ("first", "<u4")])  # sa_hip_token_score
+SCORE_HEAD_DTYPE = np.dtype([("scored", "<u4"), ("seen", "<u4"), ("certain", "<u4"), ("longest", "<u4"),
+                             ("length_sum", "<u8")])                                                       # sa_hip_token_score_head
 TOKEN_ALL_MAX = 16                                                                                          # SA_HIP_TOKEN_ALL_MAX
 SHARDS_NEXT_DTYPE = np.dtype([("written", "<u4"), ("length", "<u4"), ("covered", "<u8"), ("total", "<u8")])  # sa_hip_token_shards_next
 SHARDS_MATCH_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("count", "<u8")])                      # sa_hip_token_shards_match
@@ -61,6 +64,8 @@ EXPORTS = [
     "sa_hip_token_index_all_batch",
     "sa_hip_token_index_match_batch_device", "sa_hip_token_index_match_docs_batch_device", "sa_hip_token_index_match_batch",
     "sa_hip_token_index_match_docs_batch", "sa_hip_token_index_match_info",
+    "sa_hip_token_index_score_batch_device", "sa_hip_token_index_score_docs_batch_device", "sa_hip_token_index_score_batch",
+    "sa_hip_token_index_score_info",
     "sa_hip_token_shards_create", "sa_hip_token_shards_destroy", "sa_hip_token_shards_shard", "sa_hip_token_shards_sync",
     "sa_hip_token_shards_info", "sa_hip_token_shards_query_batch", "sa_hip_token_shards_query_batch_device",
     "sa_hip_token_shards_spans_batch", "sa_hip_token_shards_spans_batch_device", "sa_hip_token_shards_next_batch",
@@ -254,6 +259,24 @@ class TokenMatchInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenScore(C.Structure):
+    _fields_ = [("length", C.c_uint32), ("context_count", C.c_uint32), ("token_count", C.c_uint32), ("first", C.c_uint32)]
+
+
+class TokenScoreHead(C.Structure):
+    _fields_ = [("scored", C.c_uint32), ("seen", C.c_uint32), ("certain", C.c_uint32), ("longest", C.c_uint32),
+                ("length_sum", C.c_uint64)]
+
+
+class TokenScoreInfo(C.Structure):
+    """sa_hip_token_score_info: the last match, score and score-docs launches of a token index."""
+    _fields_ = [("q", C.c_uint64), ("positions", C.c_uint64), ("match_ms", C.c_double), ("score_ms", C.c_double),
+                ("docs_ms", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 class TokenShardsNext(C.Structure):
@@ -625,6 +648,14 @@ def lib():
     L.sa_hip_token_index_match_docs_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.sa_hip_token_index_match_info.restype = C.c_int
     L.sa_hip_token_index_match_info.argtypes = [vp, C.POINTER(TokenMatchInfo)]
+    L.sa_hip_token_index_score_batch_device.restype = C.c_int
+    L.sa_hip_token_index_score_batch_device.argtypes = [vp, vp, vp, u64, u64, C.c_uint32, vp, vp]
+    L.sa_hip_token_index_score_docs_batch_device.restype = C.c_int
+    L.sa_hip_token_index_score_docs_batch_device.argtypes = [vp, vp, vp, u64, vp]
+    L.sa_hip_token_index_score_batch.restype = C.c_int
+    L.sa_hip_token_index_score_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, vp]
+    L.sa_hip_token_index_score_info.restype = C.c_int
+    L.sa_hip_token_index_score_info.argtypes = [vp, C.POINTER(TokenScoreInfo)]
     L.sa_hip_token_shards_create.restype = C.c_int
     L.sa_hip_token_shards_create.argtypes = [C.POINTER(vp), vp, C.c_uint32]
     L.sa_hip_token_shards_destroy.restype = None
@@ -1619,6 +1650,35 @@ class TokenIndex(_TokenHandle):
 
     def match_info(self):
         return self._info(self._lib.sa_hip_token_index_match_info, TokenMatchInfo)
+
+    def score_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, total, max_length, spans_dev_ptr, scores_dev_ptr):
+        """The score of every one of the `total` = offsets[q] positions of q device documents (max_length 0: no cap) into
+        scores_dev_ptr[total].  spans_dev_ptr: what match_batch_device wrote for the same batch and max_length, or None (the search
+        over the context's length instead); asynchronous on the handle's stream until sync()."""
+        check(self._lib.sa_hip_token_index_score_batch_device(self._h, patterns_dev_ptr, offsets_dev_ptr, q, int(total), int(max_length),
+                                                              spans_dev_ptr, scores_dev_ptr))
+
+    def score_docs_batch_device(self, scores_dev_ptr, offsets_dev_ptr, q, heads_dev_ptr):
+        """The heads of q device documents from the scores score_batch_device wrote; asynchronous until sync()."""
+        check(self._lib.sa_hip_token_index_score_docs_batch_device(self._h, scores_dev_ptr, offsets_dev_ptr, q, heads_dev_ptr))
+
+    def score_batch(self, docs, max_length=0, scores=True, heads=True):
+        """docs as the patterns of query_batch: query documents.  -> dict: scores (length, context_count, token_count, first)
+        [offsets[Q]]: for every position of the packed documents the longest context before it in its document (at most max_length
+        symbols, 0: no cap) that the text holds with a token behind it, how often, and how often followed by the token at the
+        position; heads (scored, seen, certain, longest, length_sum)[Q].  scores / heads False: that output is not fetched (None)."""
+        if not scores and not heads:
+            raise ValueError("score_batch: scores or heads")
+        buf, off, q = self._contexts(docs)
+        total = int(off[q]) if q else 0
+        sc = _rows(total, SCORE_DTYPE) if scores else None
+        hd = _rows(q, SCORE_HEAD_DTYPE) if heads else None
+        self._call(q, self._lib.sa_hip_token_index_score_batch, _ptr(buf), _ptr(off), q, int(max_length),
+                   sc.ctypes.data if scores else None, hd.ctypes.data if heads else None)
+        return {"scores": sc[:total] if scores else None, "heads": hd[:q] if heads else None}
+
+    def score_info(self):
+        return self._info(self._lib.sa_hip_token_index_score_info, TokenScoreInfo)
 
 
 class _BorrowedTokenIndex(TokenIndex):

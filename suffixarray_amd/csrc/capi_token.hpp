@@ -1,7 +1,7 @@
 // capi_token.hpp -- the C ABI of the token index (include/sa_hip.h section 6), included by sa_capi.hip (same translation unit).
 // The kernels and the search structures are csrc/token_query.hpp, spans and next symbols csrc/token_next.hpp, documents csrc/token_docs.hpp (their entry points:
 // capi_token_docs.hpp), per-document counts and AND groups csrc/token_all.hpp (capi_token_all.hpp), matching statistics csrc/token_match.hpp
-// (capi_token_match.hpp); the suffix array of sa_hip_token_index_build comes from
+// (capi_token_match.hpp), infinity-gram scores csrc/token_score.hpp (capi_token_score.hpp); the suffix array of sa_hip_token_index_build comes from
 // the build behind sa_hip_libsais_int_device (capi_dropins.hpp: int_device).
 // What the capi_token*.hpp files share is here and in two small headers: the stopwatch of a launch (launch_timer.hpp), the upload of
 // a host batch of contexts (token_upload), and the copy of the written entries of staged rows to the caller (host_rows.hpp).
@@ -49,8 +49,12 @@ struct sa_hip_token_index {
     DevBuf m_spans, m_pos, m_out, m_heads;   // staging of the host forms
     LaunchTimer tm_mt, tm_md;                // the last match launch (q: positions) / match docs launch (q: documents)
     u64 m_last = 0;                          // documents of the last launch of either kind
+    // infinity-gram scores (token_score.hpp, capi_token_score.hpp)
+    DevBuf sc_scores, sc_heads;              // staging of the host form (its matches go to m_spans)
+    LaunchTimer tm_sc, tm_sd;                // the last score launch (q: positions) / score docs launch (q: documents)
+    u64 sc_last = 0;                         // documents of the last launch of either kind
 
-    std::array<LaunchTimer*, 9> timers() { return {&tm_q, &tm_sp, &tm_nx, &tm_lc, &tm_dc, &tm_tf, &tm_al, &tm_mt, &tm_md}; }
+    std::array<LaunchTimer*, 11> timers() { return {&tm_q, &tm_sp, &tm_nx, &tm_lc, &tm_dc, &tm_tf, &tm_al, &tm_mt, &tm_md, &tm_sc, &tm_sd}; }
 };
 
 namespace {
@@ -176,6 +180,7 @@ void sa_hip_token_index_destroy(sa_hip_token_index* t) {
     t->ranks.release();
     t->a_goff.release(); t->a_cnt.release(); t->a_wr.release();
     t->m_spans.release(); t->m_pos.release(); t->m_out.release(); t->m_heads.release();
+    t->sc_scores.release(); t->sc_heads.release();
     if (t->a_goff_pin) (void)hipHostFree(t->a_goff_pin);
     if (t->a_copied) (void)hipEventDestroy(t->a_copied);
     for (LaunchTimer* w : t->timers()) w->destroy();

@@ -14,6 +14,9 @@
     ti.matching_statistics([text])         # per position of a query text: the longest prefix of what follows that the corpus holds
     ti.matched_spans([text], min_length=8)    # its maximal verbatim spans as (position, length, count, first)
     ti.coverage([text], min_length=8)      # how many of its tokens lie inside such a span, the longest one, how many there are
+    ti.infgram([text])                     # per position: the longest context the corpus holds, its count, its count with the token
+    ti.infgram_probs([text])               # the infinity-gram probability of every token: token_count / context_count
+    ti.infgram_summary([text])             # per text: tokens scored, seen, certain, the longest context and the sum of the lengths
 
 On top of the handle API of include/sa_hip.h section 6 (suffixarray_amd._capi.TokenIndex).  No CPU fallback.
 """
@@ -190,6 +193,33 @@ class TokenIndex:
         symbols, longest = its longest match (whatever min_length is), maximal = the number of its maximal spans."""
         h = self._idx.match_docs_batch(docs, min_length=min_length, max_length=max_length or 0, cap=0)["heads"]
         return {"covered": h["covered"].copy(), "longest": h["longest"].copy(), "maximal": h["maximal"].copy()}
+
+    def infgram(self, docs, max_length=None):
+        """The infinity-gram score of query texts.  docs: a list of int sequences.  -> one (length, context_count, token_count) per
+        document, uint32 arrays over its positions: length[i] = the longest doc[i - L : i] (at most max_length symbols) that the
+        corpus holds with a token behind it, context_count[i] how often (length 0: n), token_count[i] how often followed by
+        doc[i]."""
+        buf, off, q = self._idx._contexts(docs)
+        s = self._idx.score_batch((buf, off), max_length=max_length or 0, heads=False)["scores"]
+        cut = [(int(off[d]), int(off[d + 1])) for d in range(q)]
+        return [(s["length"][a:b].copy(), s["context_count"][a:b].copy(), s["token_count"][a:b].copy()) for a, b in cut]
+
+    def infgram_probs(self, docs, max_length=None):
+        """-> one float64 array per document: token_count / context_count of every position (computed on the host; 0 for a token
+        the context was never followed by, and for every token when the corpus is empty)"""
+        out = []
+        for _, cc, tc in self.infgram(docs, max_length=max_length):
+            p = np.zeros(cc.size, np.float64)
+            np.divide(tc, cc, out=p, where=cc > 0)
+            out.append(p)
+        return out
+
+    def infgram_summary(self, docs, max_length=None):
+        """-> dict of per-document arrays: scored = its tokens, seen = those the corpus has behind their context (token_count > 0),
+        certain = those that are the only token ever behind it (token_count == context_count), longest = the longest context,
+        length_sum = the sum of the context lengths (uint64)."""
+        h = self._idx.score_batch(docs, max_length=max_length or 0, scores=False)["heads"]
+        return {k: h[k].copy() for k in ("scored", "seen", "certain", "longest", "length_sum")}
 
     def info(self):
         return self._idx.info()
