@@ -3,8 +3,9 @@
 // capi_token_docs.hpp), per-document counts and AND groups csrc/token_all.hpp (capi_token_all.hpp), matching statistics csrc/token_match.hpp
 // (capi_token_match.hpp), infinity-gram scores csrc/token_score.hpp (capi_token_score.hpp); the suffix array of sa_hip_token_index_build comes from
 // the build behind sa_hip_libsais_int_device (capi_dropins.hpp: int_device).
-// What the capi_token*.hpp files share is here and in two small headers: the stopwatch of a launch (launch_timer.hpp), the upload of
-// a host batch of contexts (token_upload), and the copy of the written entries of staged rows to the caller (host_rows.hpp).
+// What the capi_token*.hpp files share is here and in two small headers: the stopwatches (launch_timer.hpp), the upload of a host
+// batch of contexts (token_upload), and the way of staged heads and rows to the caller (token_rows_out; its row copy is
+// host_rows.hpp).  A handle lists its stopwatches and its staging buffers once (timers(), buffers()): create and destroy walk the lists.
 #pragma once
 #include "launch_timer.hpp"
 #include "host_rows.hpp"
@@ -55,6 +56,10 @@ struct sa_hip_token_index {
     u64 sc_last = 0;                         // documents of the last launch of either kind
 
     std::array<LaunchTimer*, 11> timers() { return {&tm_q, &tm_sp, &tm_nx, &tm_lc, &tm_dc, &tm_tf, &tm_al, &tm_mt, &tm_md, &tm_sc, &tm_sd}; }
+    auto buffers() {                         // every DevBuf member above (x, docs and ranks release their own)
+        return std::array{&q_pat, &q_off, &q_out, &s_spans, &s_sym, &s_cnt, &s_heads, &s_list, &d_docs, &d_offs, &d_heads, &a_goff, &a_cnt,
+                          &a_wr, &m_spans, &m_pos, &m_out, &m_heads, &sc_scores, &sc_heads};
+    }
 };
 
 namespace {
@@ -145,23 +150,50 @@ int token_stage_spans(sa_hip_token_index* t, const int32_t* patterns, const uint
     return token_launch_spans(t, t->q_pat.as<int32_t>(), t->q_off.as<u64>(), Q, mode, max_length, need_next, t->s_spans.as<sa_hip_token_span>());
 }
 
-// next symbols of the spans in s_spans to the host; only the written entries of a row are copied out
+// Host scratch of the two row arrays of one call or, in the chunked forms of a shard set, of one chunk: reserved once per call.
+template <class A, class B>
+struct HostRows {
+    std::vector<A> a;
+    std::vector<B> b;
+    int reserve(const char* who, size_t cells) {
+        try { a.resize(cells); b.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
+        return 0;
+    }
+};
+
+// Staged heads [Q] and two staged [Q, cap] row arrays to the caller: the heads as they are, of every row only the entries that its
+// head says were written (host_rows.hpp).  Synchronises the stream.  h holds at least Q * cap cells.
+template <class Head, class A, class B>
+int token_rows_out(hipStream_t stream, u64 Q, u32 cap, const void* heads_dev, Head* heads, const void* a_dev, A* a, const void* b_dev, B* b,
+                   HostRows<A, B>& h) {
+    const size_t cells = (size_t)Q * cap;
+    SA_HIP_CHECK(hipMemcpyAsync(heads, heads_dev, (size_t)Q * sizeof(Head), hipMemcpyDeviceToHost, stream));
+    if (cells) {
+        SA_HIP_CHECK(hipMemcpyAsync(h.a.data(), a_dev, cells * sizeof(A), hipMemcpyDeviceToHost, stream));
+        SA_HIP_CHECK(hipMemcpyAsync(h.b.data(), b_dev, cells * sizeof(B), hipMemcpyDeviceToHost, stream));
+    }
+    SA_HIP_CHECK(hipStreamSynchronize(stream));
+    const StridedLen written{&heads[0].written, sizeof(Head)};
+    copy_written_rows(a, h.a.data(), Q, cap, written);
+    copy_written_rows(b, h.b.data(), Q, cap, written);
+    return 0;
+}
+// ... of a call that is not chunked: the scratch is its own
+template <class Head, class A, class B>
+int token_rows_out(hipStream_t stream, const char* who, u64 Q, u32 cap, const void* heads_dev, Head* heads, const void* a_dev, A* a,
+                   const void* b_dev, B* b) {
+    HostRows<A, B> h;
+    const int rc = h.reserve(who, (size_t)Q * cap);
+    return rc ? rc : token_rows_out(stream, Q, cap, heads_dev, heads, a_dev, a, b_dev, b, h);
+}
+
+// next symbols of the spans in s_spans to the host
 int token_stage_next(sa_hip_token_index* t, const char* who, u64 Q, u32 cap, int32_t* symbols, u32* counts, sa_hip_token_next* heads) {
     int rc;
     const size_t cells = (size_t)Q * cap;
     if ((rc = t->s_sym.ensure(cells * 4)) || (rc = t->s_cnt.ensure(cells * 4)) || (rc = t->s_heads.ensure((size_t)Q * sizeof(sa_hip_token_next)))) return rc;
     if ((rc = token_launch_next(t, t->s_spans.as<sa_hip_token_span>(), Q, cap, t->s_sym.as<int32_t>(), t->s_cnt.as<u32>(), t->s_heads.as<sa_hip_token_next>()))) return rc;
-    std::vector<int32_t> hs;
-    std::vector<u32> hc;
-    try { hs.resize(cells); hc.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
-    SA_HIP_CHECK(hipMemcpyAsync(heads, t->s_heads.p, (size_t)Q * sizeof(sa_hip_token_next), hipMemcpyDeviceToHost, t->stream));
-    SA_HIP_CHECK(hipMemcpyAsync(hs.data(), t->s_sym.p, cells * 4, hipMemcpyDeviceToHost, t->stream));
-    SA_HIP_CHECK(hipMemcpyAsync(hc.data(), t->s_cnt.p, cells * 4, hipMemcpyDeviceToHost, t->stream));
-    SA_HIP_CHECK(hipStreamSynchronize(t->stream));
-    const StridedLen written{&heads[0].written, sizeof heads[0]};
-    copy_written_rows(symbols, hs.data(), Q, cap, written);
-    copy_written_rows(counts, hc.data(), Q, cap, written);
-    return 0;
+    return token_rows_out(t->stream, who, Q, cap, t->s_heads.p, heads, t->s_sym.p, symbols, t->s_cnt.p, counts);
 }
 
 }  // namespace
@@ -173,14 +205,9 @@ void sa_hip_token_index_destroy(sa_hip_token_index* t) {
     (void)hipSetDevice(t->device);
     if (t->stream) (void)hipStreamSynchronize(t->stream);
     t->x.release();
-    t->q_pat.release(); t->q_off.release(); t->q_out.release();
-    t->s_spans.release(); t->s_sym.release(); t->s_cnt.release(); t->s_heads.release(); t->s_list.release();
     t->docs.release();
-    t->d_docs.release(); t->d_offs.release(); t->d_heads.release();
     t->ranks.release();
-    t->a_goff.release(); t->a_cnt.release(); t->a_wr.release();
-    t->m_spans.release(); t->m_pos.release(); t->m_out.release(); t->m_heads.release();
-    t->sc_scores.release(); t->sc_heads.release();
+    for (DevBuf* b : t->buffers()) b->release();
     if (t->a_goff_pin) (void)hipHostFree(t->a_goff_pin);
     if (t->a_copied) (void)hipEventDestroy(t->a_copied);
     for (LaunchTimer* w : t->timers()) w->destroy();

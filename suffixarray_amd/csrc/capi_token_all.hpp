@@ -3,8 +3,8 @@
 // array and the kernels are csrc/token_all.hpp.
 // Argument checks come first and touch neither the handle nor the device; whether the handle has documents and the array is looked
 // up under its mutex, still before any HIP call.  The two stopwatches are LaunchTimer members of the handle (launch_timer.hpp); the
-// host doc_counts form moves the caller's rows in and the counts out with copy_written_rows (host_rows.hpp), all_batch with
-// capi_token_docs.hpp's token_rows_out.
+// host doc_counts form moves the caller's rows in and the counts out with copy_written_rows (host_rows.hpp), all_batch returns
+// through capi_token.hpp's token_rows_out.
 #pragma once
 #include "capi_token_docs.hpp"
 #include "token_all.hpp"
@@ -208,7 +208,7 @@ int sa_hip_token_index_all_batch(sa_hip_token_index* t, const int32_t* patterns,
     if (spans) SA_HIP_CHECK(hipMemcpyAsync(spans, t->s_spans.p, (size_t)S * sizeof(sa_hip_token_span), hipMemcpyDeviceToHost, t->stream));
     if ((rc = token_launch_all(t, t->s_spans.as<sa_hip_token_span>(), group_offsets, G, cap, budget, cap ? t->d_docs.as<int32_t>() : nullptr,
                                cap ? t->d_offs.as<int32_t>() : nullptr, t->d_heads.as<sa_hip_token_all>()))) return rc;
-    return token_rows_out(t, who, G, cap, docs, offs, heads);
+    return token_rows_out(t->stream, who, G, cap, t->d_heads.p, heads, t->d_docs.p, docs, t->d_offs.p, offs);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // capi_token.hpp (same translation unit).  The structures and the kernels are csrc/token_docs.hpp.
 // Argument checks come first and touch neither the handle nor the device; whether the handle has documents is looked up under its
 // mutex, still before any HIP call.  The two stopwatches are LaunchTimer members of the handle (launch_timer.hpp), the contexts of a
-// host form go up through token_stage_spans, and token_rows_out copies the written rows back with copy_written_rows (host_rows.hpp).
+// host form go up through token_stage_spans, and the heads and written rows come back through token_rows_out (both capi_token.hpp's).
 #pragma once
 #include "capi_token.hpp"
 #include "token_docs.hpp"
@@ -32,24 +32,6 @@ int token_launch_docs(sa_hip_token_index* t, const sa_hip_token_span* spans, u64
     int rc;
     if ((rc = t->tm_dc.begin(t->stream)) || (rc = tq::launch_docs(t->x, t->docs, t->stream, g))) return rc;
     return t->tm_dc.end(t->stream, Q);
-}
-
-// heads and rows of the staged cells to the host: only the written entries of a row are copied out (host_rows.hpp)
-template <class Head>
-int token_rows_out(sa_hip_token_index* t, const char* who, u64 Q, u32 cap, int32_t* docs, int32_t* offs, Head* heads) {
-    const size_t cells = (size_t)Q * cap;
-    std::vector<int32_t> hd, ho;
-    try { hd.resize(cells); ho.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
-    SA_HIP_CHECK(hipMemcpyAsync(heads, t->d_heads.p, (size_t)Q * sizeof(Head), hipMemcpyDeviceToHost, t->stream));
-    if (cells) {
-        SA_HIP_CHECK(hipMemcpyAsync(hd.data(), t->d_docs.p, cells * 4, hipMemcpyDeviceToHost, t->stream));
-        SA_HIP_CHECK(hipMemcpyAsync(ho.data(), t->d_offs.p, cells * 4, hipMemcpyDeviceToHost, t->stream));
-    }
-    SA_HIP_CHECK(hipStreamSynchronize(t->stream));
-    const StridedLen written{&heads[0].written, sizeof(Head)};
-    copy_written_rows(docs, hd.data(), Q, cap, written);
-    copy_written_rows(offs, ho.data(), Q, cap, written);
-    return 0;
 }
 
 }  // namespace
@@ -160,7 +142,7 @@ int sa_hip_token_index_locate_batch(sa_hip_token_index* t, const int32_t* patter
     if (spans) SA_HIP_CHECK(hipMemcpyAsync(spans, t->s_spans.p, (size_t)Q * sizeof(sa_hip_token_span), hipMemcpyDeviceToHost, t->stream));
     if ((rc = token_launch_locate(t, t->s_spans.as<sa_hip_token_span>(), Q, cap, t->d_docs.as<int32_t>(), t->d_offs.as<int32_t>(),
                                   t->d_heads.as<sa_hip_token_locate>()))) return rc;
-    return token_rows_out(t, who, Q, cap, docs, offs, heads);
+    return token_rows_out(t->stream, who, Q, cap, t->d_heads.p, heads, t->d_docs.p, docs, t->d_offs.p, offs);
 }
 
 int sa_hip_token_index_docs_batch_device(sa_hip_token_index* t, const void* spans_dev, uint64_t Q, uint32_t cap, uint32_t budget,
@@ -193,7 +175,7 @@ int sa_hip_token_index_docs_batch(sa_hip_token_index* t, const int32_t* patterns
     if (spans) SA_HIP_CHECK(hipMemcpyAsync(spans, t->s_spans.p, (size_t)Q * sizeof(sa_hip_token_span), hipMemcpyDeviceToHost, t->stream));
     if ((rc = token_launch_docs(t, t->s_spans.as<sa_hip_token_span>(), Q, cap, budget, cap ? t->d_docs.as<int32_t>() : nullptr,
                                 cap ? t->d_offs.as<int32_t>() : nullptr, t->d_heads.as<sa_hip_token_docs>()))) return rc;
-    return token_rows_out(t, who, Q, cap, docs, offs, heads);
+    return token_rows_out(t->stream, who, Q, cap, t->d_heads.p, heads, t->d_docs.p, docs, t->d_offs.p, offs);
 }
 
 }  // extern "C"

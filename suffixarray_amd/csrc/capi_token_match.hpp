@@ -1,8 +1,8 @@
 // capi_token_match.hpp -- the C ABI of matching statistics over a token index (include/sa_hip.h section 6f), included by sa_capi.hip
 // behind capi_token_all.hpp (same translation unit).  The kernels are csrc/token_match.hpp.
 // Argument checks come first and touch neither the handle nor the device.  The two stopwatches are LaunchTimer members of the handle
-// (launch_timer.hpp), the documents of a host form go up through token_upload, and the written rows come back with
-// copy_written_rows (host_rows.hpp).
+// (launch_timer.hpp), the documents of a host form go up through token_upload, and the heads and written rows come back through
+// token_rows_out (capi_token.hpp).
 #pragma once
 #include "capi_token_docs.hpp"
 #include "token_match.hpp"
@@ -119,19 +119,7 @@ int sa_hip_token_index_match_docs_batch(sa_hip_token_index* t, const int32_t* pa
     if ((rc = token_launch_match_docs(t, t->m_spans.as<sa_hip_token_span>(), t->q_off.as<u64>(), Q, min_length, cap,
                                       cap ? t->m_pos.as<u32>() : nullptr, cap ? t->m_out.as<sa_hip_token_span>() : nullptr,
                                       t->m_heads.as<sa_hip_token_match_head>()))) return rc;
-    std::vector<u32> hp;
-    std::vector<sa_hip_token_span> ho;
-    try { hp.resize(cells); ho.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
-    SA_HIP_CHECK(hipMemcpyAsync(heads, t->m_heads.p, (size_t)Q * sizeof(sa_hip_token_match_head), hipMemcpyDeviceToHost, t->stream));
-    if (cells) {
-        SA_HIP_CHECK(hipMemcpyAsync(hp.data(), t->m_pos.p, cells * 4, hipMemcpyDeviceToHost, t->stream));
-        SA_HIP_CHECK(hipMemcpyAsync(ho.data(), t->m_out.p, cells * sizeof(sa_hip_token_span), hipMemcpyDeviceToHost, t->stream));
-    }
-    SA_HIP_CHECK(hipStreamSynchronize(t->stream));
-    const StridedLen written{&heads[0].written, sizeof heads[0]};
-    copy_written_rows(positions, hp.data(), Q, cap, written);
-    copy_written_rows(out_spans, ho.data(), Q, cap, written);
-    return 0;
+    return token_rows_out(t->stream, who, Q, cap, t->m_heads.p, heads, t->m_pos.p, positions, t->m_out.p, out_spans);
 }
 
 int sa_hip_token_index_match_info(const sa_hip_token_index* ct, sa_hip_token_match_info* out) {

@@ -3,11 +3,12 @@
 // shards' own rank-by-document arrays are built by sa_hip_token_index_prepare_doc_ranks (capi_token_all.hpp).
 // Argument checks come first and touch neither the set nor the device; whether the set has documents and a table of rank arrays,
 // and whether the shards' documents and arrays are still the ones the tables describe, is looked up under the mutexes, still before
-// any HIP call.  The doc_counts stopwatch is a LaunchTimer of the set (launch_timer.hpp); the plan, pair and merge launches are timed
-// per chunk by an event list, as the docs calls are.  The contexts of a host form go up through token_upload, the written rows come
-// back with copy_written_rows (host_rows.hpp); the group table goes through a pinned buffer of the set (token_stage_groups of
-// capi_token_all.hpp), so the device form stays asynchronous.  The chunking is shards_docs's: tq::shard_chunk with the same budget
-// and the same knob -- a pair costs cap * 8 bytes of list and a 16-byte head.
+// any HIP call.  The doc_counts stopwatch is a LaunchTimer of the set, the plan, pair and merge launches are the three stages of a
+// ChunkTimer (launch_timer.hpp).  The contexts of a host form go up through shards_stage_spans, the chunks of groups are walked by
+// shards_chunks (both capi_token_shards.hpp's), and the heads and written rows come back through token_rows_out (capi_token.hpp);
+// the host doc_counts form moves the caller's rows in and the counts out with copy_written_rows (host_rows.hpp) as
+// capi_token_all.hpp's does.  The group table goes through a pinned buffer of the set (token_stage_groups of capi_token_all.hpp),
+// so the device form stays asynchronous.
 #pragma once
 #include "capi_token_all.hpp"
 #include "capi_token_shard_docs.hpp"
@@ -85,63 +86,38 @@ int shards_all(sa_hip_token_shards* g, const char* who, const sa_hip_token_span*
                u64 budget, u64* docs, int32_t* offs, sa_hip_token_shards_all* heads, bool to_host) {
     int rc;
     const u32 S = g->S;
-    const u64 chunk = tq::shard_chunk(g->chunk_knob, S, cap, G);
+    const u64 chunk = shards_chunk(g, cap, G);
     const size_t cells = (size_t)chunk * cap;
     if ((rc = g->a_docs.ensure(cells * S * 4)) || (rc = g->a_offs.ensure(cells * S * 4)) ||
         (rc = g->a_heads.ensure((size_t)chunk * S * sizeof(tq::ShardAllPair))) ||
         (rc = g->a_plan.ensure((size_t)chunk * S * sizeof(tq::ShardAllPlan))) ||
         (rc = g->a_groups.ensure((size_t)chunk * sizeof(tq::ShardAllGroup)))) return rc;
-    std::vector<u64> hd;
-    std::vector<int32_t> ho;
-    if (to_host) {
-        if ((rc = g->od_docs.ensure(cells * 8)) || (rc = g->od_offs.ensure(cells * 4)) ||
-            (rc = g->oa_heads.ensure((size_t)chunk * sizeof(sa_hip_token_shards_all)))) return rc;
-        try { hd.resize(cells); ho.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
-    }
     if ((rc = token_stage_groups(g, goff, G))) return rc;
     SA_HIP_CHECK(hipMemsetAsync(g->a_sum.p, 0, sizeof(unsigned long long), g->stream));
-    size_t ev = 0;
-    for (u64 c0 = 0; c0 < G; c0 += chunk) {
-        const u64 gc = G - c0 < chunk ? G - c0 : chunk;
-        if ((rc = shards_event(g, g->al_ev, ev++))) return rc;
+    int32_t* const p_docs = cap ? g->a_docs.as<int32_t>() : nullptr;
+    int32_t* const p_offs = cap ? g->a_offs.as<int32_t>() : nullptr;
+    auto plan = [&](const auto& c) -> int {
         tq::ShardAllPlanArgs p{};
         p.tab = g->table(); p.spans = spans; p.P = P;
-        p.group_offsets = g->a_goff.as<u32>() + c0; p.G = gc; p.S = S; p.budget = budget;
+        p.group_offsets = g->a_goff.as<u32>() + c.c0; p.G = c.n; p.S = S; p.budget = budget;
         p.pairs = g->a_plan.as<tq::ShardAllPlan>(); p.groups = g->a_groups.as<tq::ShardAllGroup>();
-        if ((rc = tq::launch_shard_all_plan(g->stream, p))) return rc;
-        if ((rc = shards_event(g, g->al_ev, ev++))) return rc;
+        return tq::launch_shard_all_plan(g->stream, p);
+    };
+    auto pairs = [&](const auto& c) -> int {
         tq::ShardAllArgs a{};
         a.tab = g->table(); a.rtab = g->rtab.as<tq::RankView>();
-        a.spans = spans; a.P = P; a.group_offsets = p.group_offsets; a.pairs = p.pairs;
-        a.G = gc; a.S = S; a.cap = cap;
-        a.docs = cap ? g->a_docs.as<int32_t>() : nullptr; a.offsets = cap ? g->a_offs.as<int32_t>() : nullptr;
+        a.spans = spans; a.P = P; a.group_offsets = g->a_goff.as<u32>() + c.c0; a.pairs = g->a_plan.as<tq::ShardAllPlan>();
+        a.G = c.n; a.S = S; a.cap = cap;
+        a.docs = p_docs; a.offsets = p_offs;
         a.heads = g->a_heads.as<tq::ShardAllPair>();
         a.streamed = g->a_sum.as<unsigned long long>();
-        if ((rc = tq::launch_shard_all(g->stream, a))) return rc;
-        if ((rc = shards_event(g, g->al_ev, ev++))) return rc;
-        u64* const o_docs = !cap ? nullptr : to_host ? g->od_docs.as<u64>() : docs + c0 * cap;
-        int32_t* const o_offs = !cap ? nullptr : to_host ? g->od_offs.as<int32_t>() : offs + c0 * cap;
-        sa_hip_token_shards_all* const o_heads = to_host ? g->oa_heads.as<sa_hip_token_shards_all>() : heads + c0;
-        if ((rc = shards_launch_all_merge(g, a.docs, a.offsets, a.heads, p.groups, g->dbase.as<u64>(), gc, cap, o_docs, o_offs, o_heads))) return rc;
-        if ((rc = shards_event(g, g->al_ev, ev++))) return rc;
-        g->al_used = ev;
-        g->al_pending = true;
-        if (to_host) {
-            SA_HIP_CHECK(hipMemcpyAsync(heads + c0, g->oa_heads.p, (size_t)gc * sizeof(sa_hip_token_shards_all), hipMemcpyDeviceToHost, g->stream));
-            if (cap) {
-                SA_HIP_CHECK(hipMemcpyAsync(hd.data(), g->od_docs.p, (size_t)gc * cap * 8, hipMemcpyDeviceToHost, g->stream));
-                SA_HIP_CHECK(hipMemcpyAsync(ho.data(), g->od_offs.p, (size_t)gc * cap * 4, hipMemcpyDeviceToHost, g->stream));
-            }
-            SA_HIP_CHECK(hipStreamSynchronize(g->stream));
-            const StridedLen written{&heads[c0].written, sizeof heads[0]};
-            copy_written_rows(docs + c0 * cap, hd.data(), gc, cap, written);
-            copy_written_rows(offs + c0 * cap, ho.data(), gc, cap, written);
-        }
-    }
-    g->al_q = G;
-    g->al_pairs_q = G * S;
-    g->al_chunk = (u32)chunk;
-    return 0;
+        return tq::launch_shard_all(g->stream, a);
+    };
+    auto merge = [&](const auto& c) -> int {
+        return shards_launch_all_merge(g, p_docs, p_offs, g->a_heads.as<tq::ShardAllPair>(), g->a_groups.as<tq::ShardAllGroup>(),
+                                       g->dbase.as<u64>(), c.n, cap, c.a, c.b, c.heads);
+    };
+    return shards_chunks(g, who, g->tm_al, G, cap, chunk, to_host, g->oa_heads, heads, g->od_docs, docs, g->od_offs, offs, plan, pairs, merge);
 }
 
 }  // namespace
@@ -175,30 +151,20 @@ int sa_hip_token_shards_doc_ranks_info(const sa_hip_token_shards* cg, sa_hip_tok
     if (!cg || !out) return fail(SA_HIP_EINVAL, "sa_hip_token_shards_doc_ranks_info", "NULL argument");
     sa_hip_token_shards* g = const_cast<sa_hip_token_shards*>(cg);
     std::lock_guard<std::mutex> lk(g->mu);
-    if (g->tm_tf.pending || g->al_pending) {
+    if (g->tm_tf.pending || g->tm_al.pending) {
         int rc = set_device(g->device);
         if (rc || (rc = g->tm_tf.resolve())) return rc;
-        if (g->al_pending) {
-            float ms = 0.f;
+        if (g->tm_al.pending) {
             unsigned long long sum = 0;
             SA_HIP_CHECK(hipMemcpyAsync(&sum, g->a_sum.p, sizeof sum, hipMemcpyDeviceToHost, g->stream));
             SA_HIP_CHECK(hipStreamSynchronize(g->stream));
-            g->al_plan_ms = g->al_pairs_ms = g->al_merge_ms = 0.0;
-            for (size_t k = 0; k + 4 <= g->al_used; k += 4) {
-                SA_HIP_CHECK(hipEventElapsedTime(&ms, g->al_ev[k], g->al_ev[k + 1]));
-                g->al_plan_ms += ms;
-                SA_HIP_CHECK(hipEventElapsedTime(&ms, g->al_ev[k + 1], g->al_ev[k + 2]));
-                g->al_pairs_ms += ms;
-                SA_HIP_CHECK(hipEventElapsedTime(&ms, g->al_ev[k + 2], g->al_ev[k + 3]));
-                g->al_merge_ms += ms;
-            }
+            if ((rc = g->tm_al.resolve())) return rc;
             g->al_streamed = sum;
-            g->al_pending = false;
         }
     }
     memset(out, 0, sizeof *out);
     out->present = g->has_ranks ? 1u : 0u;
-    out->chunk = g->al_chunk;
+    out->chunk = g->tm_al.chunk;
     for (u32 s = 0; s < g->S; ++s) {
         sa_hip_token_index* t = g->shard[s];
         std::lock_guard<std::mutex> ls(t->mu);
@@ -207,12 +173,12 @@ int sa_hip_token_shards_doc_ranks_info(const sa_hip_token_shards* cg, sa_hip_tok
     }
     out->counts_q = g->tm_tf.q;
     out->counts_ms = g->tm_tf.ms;
-    out->plan_q = g->al_q;
-    out->plan_ms = g->al_plan_ms;
-    out->pairs_q = g->al_pairs_q;
-    out->pairs_ms = g->al_pairs_ms;
-    out->merge_q = g->al_q;
-    out->merge_ms = g->al_merge_ms;
+    out->plan_q = g->tm_al.q;
+    out->plan_ms = g->tm_al.ms[0];
+    out->pairs_q = g->tm_al.q * g->S;
+    out->pairs_ms = g->tm_al.ms[1];
+    out->merge_q = g->tm_al.q;
+    out->merge_ms = g->tm_al.ms[2];
     out->streamed = g->al_streamed;
     return 0;
 }
@@ -250,7 +216,7 @@ int sa_hip_token_shards_doc_counts_batch(sa_hip_token_shards* g, const int32_t* 
     try { hd.assign(cells, 0); hc.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
     auto slots = [&](u64 i) { return written ? written[i] : cap; };
     copy_written_rows(hd.data(), docs, Q, cap, slots);
-    if ((rc = shards_stage_doc_spans(g, patterns, offsets, Q, mode, max_length, need_next, spans))) return rc;
+    if ((rc = shards_stage_spans(g, patterns, offsets, Q, mode, max_length, need_next, spans))) return rc;
     SA_HIP_CHECK(hipMemcpyAsync(g->c_docs.p, hd.data(), cells * 8, hipMemcpyHostToDevice, g->stream));
     if (written) SA_HIP_CHECK(hipMemcpyAsync(g->c_wr.p, written, (size_t)Q * 4, hipMemcpyHostToDevice, g->stream));
     if ((rc = shards_launch_tf(g, g->s_spans.as<sa_hip_token_span>(), Q, cap, g->c_docs.as<u64>(), written ? g->c_wr.p : nullptr, 4,
@@ -287,7 +253,7 @@ int sa_hip_token_shards_all_batch(sa_hip_token_shards* g, const int32_t* pattern
     if ((rc = token_offsets_args(who, patterns, offsets, P))) return rc;
     std::lock_guard<std::mutex> lk(g->mu);
     if ((rc = shards_ranks_current(g, who)) || (rc = set_device(g->device))) return rc;
-    if ((rc = shards_stage_doc_spans(g, patterns, offsets, P, mode, max_length, need_next, spans))) return rc;
+    if ((rc = shards_stage_spans(g, patterns, offsets, P, mode, max_length, need_next, spans))) return rc;
     return shards_all(g, who, g->s_spans.as<sa_hip_token_span>(), P, group_offsets, G, cap, budget, docs, offs, heads, true);
 }
 

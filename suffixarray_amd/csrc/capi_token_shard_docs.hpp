@@ -3,10 +3,10 @@
 // sa_hip_token_index_set_documents (capi_token_docs.hpp).
 // Argument checks come first and touch neither the set nor the device; whether the set has documents, and whether the shards'
 // documents are still the ones its table describes, is looked up under the mutexes, still before any HIP call.  The locate stopwatch
-// is a LaunchTimer of the set (launch_timer.hpp); the pair and merge launches are timed per chunk by an event list, as the next
-// symbols are.  The contexts of a host form go up through token_upload, the written rows come back with copy_written_rows
-// (host_rows.hpp).  The chunking is shards_next's: tq::shard_chunk with the same budget and the same knob -- a pair costs cap * 8
-// bytes of list and a 16-byte head, as a per-shard next-symbol list does.
+// is a LaunchTimer of the set, the pair and merge launches are the two stages of a ChunkTimer (launch_timer.hpp).  The contexts of
+// a host form go up through shards_stage_spans, the chunks are walked by shards_chunks (both capi_token_shards.hpp's), and the
+// heads and written rows come back through token_rows_out (capi_token.hpp).  Only the scratch of a chunk of pairs and the two
+// launches are this file's.
 #pragma once
 #include "capi_token_docs.hpp"
 #include "capi_token_shards.hpp"
@@ -50,19 +50,6 @@ int shards_docs_table(sa_hip_token_shards* g, const char* who) {
     return 0;
 }
 
-// contexts from the host into the set's staging buffers, their spans into s_spans (and to the caller when asked)
-int shards_stage_doc_spans(sa_hip_token_shards* g, const int32_t* patterns, const uint64_t* offsets, u64 Q, int mode, u32 max_length,
-                           int need_next, sa_hip_token_span* spans) {
-    int rc;
-    const size_t span_bytes = (size_t)Q * g->S * sizeof(sa_hip_token_span);
-    if ((rc = token_upload(g->q_pat, g->q_off, g->stream, patterns, offsets, Q)) || (rc = g->s_spans.ensure(span_bytes)) ||
-        (rc = g->s_len.ensure((size_t)Q * 4)) || (rc = g->s_tot.ensure((size_t)Q * 8))) return rc;
-    if ((rc = shards_launch_spans(g, g->q_pat.as<int32_t>(), g->q_off.as<u64>(), Q, mode, max_length, need_next, g->s_len.as<u32>(),
-                                  g->s_tot.as<u64>(), g->s_spans.as<sa_hip_token_span>()))) return rc;
-    if (spans) SA_HIP_CHECK(hipMemcpyAsync(spans, g->s_spans.p, span_bytes, hipMemcpyDeviceToHost, g->stream));
-    return 0;
-}
-
 int shards_launch_locate(sa_hip_token_shards* g, const sa_hip_token_span* spans, u64 Q, u32 cap, u64* docs, int32_t* offs,
                          sa_hip_token_shards_locate* heads) {
     const tq::ShardLocateArgs a{g->table(), g->dtab.as<tq::DocView>(), g->dbase.as<u64>(), spans, Q, g->S, cap, docs, offs, heads};
@@ -84,54 +71,27 @@ int shards_docs(sa_hip_token_shards* g, const char* who, const sa_hip_token_span
                 int32_t* offs, sa_hip_token_shards_docs* heads, bool to_host) {
     int rc;
     const u32 S = g->S;
-    const u64 chunk = tq::shard_chunk(g->chunk_knob, S, cap, Q);
+    const u64 chunk = shards_chunk(g, cap, Q);
     const size_t cells = (size_t)chunk * cap;
     if ((rc = g->d_docs.ensure(cells * S * 4)) || (rc = g->d_offs.ensure(cells * S * 4)) ||
         (rc = g->d_heads.ensure((size_t)chunk * S * sizeof(sa_hip_token_docs)))) return rc;
-    std::vector<u64> hd;
-    std::vector<int32_t> ho;
-    if (to_host) {
-        if ((rc = g->od_docs.ensure(cells * 8)) || (rc = g->od_offs.ensure(cells * 4)) ||
-            (rc = g->od_heads.ensure((size_t)chunk * sizeof(sa_hip_token_shards_docs)))) return rc;
-        try { hd.resize(cells); ho.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
-    }
     SA_HIP_CHECK(hipMemsetAsync(g->d_sum.p, 0, sizeof(unsigned long long), g->stream));
-    size_t ev = 0;
-    for (u64 c0 = 0; c0 < Q; c0 += chunk) {
-        const u64 qc = Q - c0 < chunk ? Q - c0 : chunk;
-        if ((rc = shards_event(g, g->dc_ev, ev++))) return rc;
+    int32_t* const p_docs = cap ? g->d_docs.as<int32_t>() : nullptr;
+    int32_t* const p_offs = cap ? g->d_offs.as<int32_t>() : nullptr;
+    auto pairs = [&](const auto& c) -> int {
         tq::ShardDocsArgs a{};
         a.tab = g->table(); a.dtab = g->dtab.as<tq::DocView>();
-        a.spans = spans + c0; a.span_stride = Q;
-        a.Q = qc; a.S = S; a.cap = cap; a.budget = budget;
-        a.docs = cap ? g->d_docs.as<int32_t>() : nullptr; a.offsets = cap ? g->d_offs.as<int32_t>() : nullptr;
+        a.spans = spans + c.c0; a.span_stride = Q;
+        a.Q = c.n; a.S = S; a.cap = cap; a.budget = budget;
+        a.docs = p_docs; a.offsets = p_offs;
         a.heads = g->d_heads.as<sa_hip_token_docs>();
         a.streamed = g->d_sum.as<unsigned long long>();
-        if ((rc = tq::launch_shard_docs(g->stream, a))) return rc;
-        if ((rc = shards_event(g, g->dc_ev, ev++))) return rc;
-        u64* const o_docs = !cap ? nullptr : to_host ? g->od_docs.as<u64>() : docs + c0 * cap;
-        int32_t* const o_offs = !cap ? nullptr : to_host ? g->od_offs.as<int32_t>() : offs + c0 * cap;
-        sa_hip_token_shards_docs* const o_heads = to_host ? g->od_heads.as<sa_hip_token_shards_docs>() : heads + c0;
-        if ((rc = shards_launch_docs_merge(g, a.docs, a.offsets, a.heads, g->dbase.as<u64>(), qc, cap, o_docs, o_offs, o_heads))) return rc;
-        if ((rc = shards_event(g, g->dc_ev, ev++))) return rc;
-        g->dc_used = ev;
-        g->dc_pending = true;
-        if (to_host) {
-            SA_HIP_CHECK(hipMemcpyAsync(heads + c0, g->od_heads.p, (size_t)qc * sizeof(sa_hip_token_shards_docs), hipMemcpyDeviceToHost, g->stream));
-            if (cap) {
-                SA_HIP_CHECK(hipMemcpyAsync(hd.data(), g->od_docs.p, (size_t)qc * cap * 8, hipMemcpyDeviceToHost, g->stream));
-                SA_HIP_CHECK(hipMemcpyAsync(ho.data(), g->od_offs.p, (size_t)qc * cap * 4, hipMemcpyDeviceToHost, g->stream));
-            }
-            SA_HIP_CHECK(hipStreamSynchronize(g->stream));
-            const StridedLen written{&heads[c0].written, sizeof heads[0]};
-            copy_written_rows(docs + c0 * cap, hd.data(), qc, cap, written);
-            copy_written_rows(offs + c0 * cap, ho.data(), qc, cap, written);
-        }
-    }
-    g->dc_q = Q * S;
-    g->dm_q = Q;
-    g->dc_chunk = (u32)chunk;
-    return 0;
+        return tq::launch_shard_docs(g->stream, a);
+    };
+    auto merge = [&](const auto& c) -> int {
+        return shards_launch_docs_merge(g, p_docs, p_offs, g->d_heads.as<sa_hip_token_docs>(), g->dbase.as<u64>(), c.n, cap, c.a, c.b, c.heads);
+    };
+    return shards_chunks(g, who, g->tm_dc, Q, cap, chunk, to_host, g->od_heads, heads, g->od_docs, docs, g->od_offs, offs, pairs, merge);
 }
 
 }  // namespace
@@ -189,34 +149,26 @@ int sa_hip_token_shards_docs_info(const sa_hip_token_shards* cg, sa_hip_token_sh
     if (!cg || !out) return fail(SA_HIP_EINVAL, "sa_hip_token_shards_docs_info", "NULL argument");
     sa_hip_token_shards* g = const_cast<sa_hip_token_shards*>(cg);
     std::lock_guard<std::mutex> lk(g->mu);
-    if (g->tm_lc.pending || g->dc_pending) {
+    if (g->tm_lc.pending || g->tm_dc.pending) {
         int rc = set_device(g->device);
         if (rc || (rc = g->tm_lc.resolve())) return rc;
-        if (g->dc_pending) {
-            float ms = 0.f;
+        if (g->tm_dc.pending) {
             unsigned long long sum = 0;
             SA_HIP_CHECK(hipMemcpyAsync(&sum, g->d_sum.p, sizeof sum, hipMemcpyDeviceToHost, g->stream));
             SA_HIP_CHECK(hipStreamSynchronize(g->stream));
-            g->dc_ms = g->dm_ms = 0.0;
-            for (size_t k = 0; k + 3 <= g->dc_used; k += 3) {
-                SA_HIP_CHECK(hipEventElapsedTime(&ms, g->dc_ev[k], g->dc_ev[k + 1]));
-                g->dc_ms += ms;
-                SA_HIP_CHECK(hipEventElapsedTime(&ms, g->dc_ev[k + 1], g->dc_ev[k + 2]));
-                g->dm_ms += ms;
-            }
+            if ((rc = g->tm_dc.resolve())) return rc;
             g->dc_streamed = sum;
-            g->dc_pending = false;
         }
     }
     memset(out, 0, sizeof *out);
     out->documents = g->has_docs ? g->doc_base[g->S] : 0;
-    out->chunk = g->dc_chunk;
+    out->chunk = g->tm_dc.chunk;
     out->locate_q = g->tm_lc.q;
     out->locate_ms = g->tm_lc.ms;
-    out->pairs_q = g->dc_q;
-    out->pairs_ms = g->dc_ms;
-    out->merge_q = g->dm_q;
-    out->merge_ms = g->dm_ms;
+    out->pairs_q = g->tm_dc.q * g->S;
+    out->pairs_ms = g->tm_dc.ms[0];
+    out->merge_q = g->tm_dc.q;
+    out->merge_ms = g->tm_dc.ms[1];
     out->streamed = g->dc_streamed;
     return 0;
 }
@@ -250,20 +202,10 @@ int sa_hip_token_shards_locate_batch(sa_hip_token_shards* g, const int32_t* patt
     const size_t cells = (size_t)Q * cap;
     if ((rc = g->od_docs.ensure(cells * 8)) || (rc = g->od_offs.ensure(cells * 4)) ||
         (rc = g->od_heads.ensure((size_t)Q * sizeof(sa_hip_token_shards_docs)))) return rc;
-    if ((rc = shards_stage_doc_spans(g, patterns, offsets, Q, 0, 0, 0, spans))) return rc;
+    if ((rc = shards_stage_spans(g, patterns, offsets, Q, 0, 0, 0, spans))) return rc;
     if ((rc = shards_launch_locate(g, g->s_spans.as<sa_hip_token_span>(), Q, cap, g->od_docs.as<u64>(), g->od_offs.as<int32_t>(),
                                    g->od_heads.as<sa_hip_token_shards_locate>()))) return rc;
-    std::vector<u64> hd;
-    std::vector<int32_t> ho;
-    try { hd.resize(cells); ho.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
-    SA_HIP_CHECK(hipMemcpyAsync(heads, g->od_heads.p, (size_t)Q * sizeof(sa_hip_token_shards_locate), hipMemcpyDeviceToHost, g->stream));
-    SA_HIP_CHECK(hipMemcpyAsync(hd.data(), g->od_docs.p, cells * 8, hipMemcpyDeviceToHost, g->stream));
-    SA_HIP_CHECK(hipMemcpyAsync(ho.data(), g->od_offs.p, cells * 4, hipMemcpyDeviceToHost, g->stream));
-    SA_HIP_CHECK(hipStreamSynchronize(g->stream));
-    const StridedLen written{&heads[0].written, sizeof heads[0]};
-    copy_written_rows(docs, hd.data(), Q, cap, written);
-    copy_written_rows(offs, ho.data(), Q, cap, written);
-    return 0;
+    return token_rows_out(g->stream, who, Q, cap, g->od_heads.p, heads, g->od_docs.p, docs, g->od_offs.p, offs);
 }
 
 int sa_hip_token_shards_docs_batch_device(sa_hip_token_shards* g, const void* spans_dev, uint64_t Q, uint32_t cap, uint64_t budget,
@@ -290,7 +232,7 @@ int sa_hip_token_shards_docs_batch(sa_hip_token_shards* g, const int32_t* patter
     if ((rc = token_offsets_args(who, patterns, offsets, Q))) return rc;
     std::lock_guard<std::mutex> lk(g->mu);
     if ((rc = shards_docs_current(g, who)) || (rc = set_device(g->device))) return rc;
-    if ((rc = shards_stage_doc_spans(g, patterns, offsets, Q, mode, max_length, need_next, spans))) return rc;
+    if ((rc = shards_stage_spans(g, patterns, offsets, Q, mode, max_length, need_next, spans))) return rc;
     return shards_docs(g, who, g->s_spans.as<sa_hip_token_span>(), Q, cap, budget, docs, offs, heads, true);
 }
 

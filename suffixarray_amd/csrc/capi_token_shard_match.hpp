@@ -3,7 +3,7 @@
 // the documents step, csrc/token_match.hpp's tq_match_docs_kernel over the merged record.
 // Argument checks come first and touch neither the set nor the device (token_match_total and token_match_docs_args are
 // capi_token_match.hpp's).  The two stopwatches are LaunchTimer members of the set (launch_timer.hpp), the documents of a host form
-// go up through token_upload, and the written rows come back with copy_written_rows (host_rows.hpp).
+// go up through token_upload, and the heads and written rows come back through token_rows_out (both capi_token.hpp's).
 #pragma once
 #include "capi_token_match.hpp"
 #include "capi_token_shards.hpp"
@@ -120,19 +120,7 @@ int sa_hip_token_shards_match_docs_batch(sa_hip_token_shards* g, const int32_t* 
     if ((rc = shards_launch_match_docs(g, g->m_merged.as<sa_hip_token_shards_match>(), g->q_off.as<u64>(), Q, min_length, cap,
                                        cap ? g->m_pos.as<u32>() : nullptr, cap ? g->m_out.as<sa_hip_token_shards_match>() : nullptr,
                                        g->m_heads.as<sa_hip_token_match_head>()))) return rc;
-    std::vector<u32> hp;
-    std::vector<sa_hip_token_shards_match> ho;
-    try { hp.resize(cells); ho.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
-    SA_HIP_CHECK(hipMemcpyAsync(heads, g->m_heads.p, (size_t)Q * sizeof(sa_hip_token_match_head), hipMemcpyDeviceToHost, g->stream));
-    if (cells) {
-        SA_HIP_CHECK(hipMemcpyAsync(hp.data(), g->m_pos.p, cells * 4, hipMemcpyDeviceToHost, g->stream));
-        SA_HIP_CHECK(hipMemcpyAsync(ho.data(), g->m_out.p, cells * sizeof(sa_hip_token_shards_match), hipMemcpyDeviceToHost, g->stream));
-    }
-    SA_HIP_CHECK(hipStreamSynchronize(g->stream));
-    const StridedLen written{&heads[0].written, sizeof heads[0]};
-    copy_written_rows(positions, hp.data(), Q, cap, written);
-    copy_written_rows(out_matches, ho.data(), Q, cap, written);
-    return 0;
+    return token_rows_out(g->stream, who, Q, cap, g->m_heads.p, heads, g->m_pos.p, positions, g->m_out.p, out_matches);
 }
 
 int sa_hip_token_shards_match_info(const sa_hip_token_shards* cg, sa_hip_token_shards_match_stats* out) {

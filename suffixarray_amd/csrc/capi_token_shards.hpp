@@ -2,8 +2,10 @@
 // (same translation unit).  The kernels are csrc/token_shards.hpp; the per-shard next symbols are tq::launch_next of every shard.
 // Matching statistics over the set: capi_token_shard_match.hpp; documents over the set: capi_token_shard_docs.hpp; per-document
 // counts and AND groups over the set: capi_token_shard_all.hpp.
-// The stopwatches, the upload of a host batch and the row copy are capi_token.hpp's; the per-chunk events of the next symbols, summed
-// into two figures, are the set's own.
+// The stopwatches, the upload of a host batch and token_rows_out are capi_token.hpp's.  What the families of the set share is here:
+// the spans of a host batch (shards_stage_spans) and the walk of a chunked call (shards_chunks: chunk size, per-chunk stopwatch,
+// output pointers of the host and the device form, the way of a chunk's rows to the caller), which the next symbols, the documents
+// and the AND groups hand their launches to.
 #pragma once
 #include "capi_token.hpp"
 #include "token_shards.hpp"
@@ -24,12 +26,8 @@ struct sa_hip_token_shards {
     DevBuf l_sym, l_cnt, l_heads, l_list;    // the per-shard lists of one chunk; l_list as sa_hip_token_index::s_list
     DevBuf o_sym, o_cnt, o_heads;            // merged output of one chunk (host form)
     LaunchTimer tm_r, tm_sp;                 // the last ranges / spans launch
-    std::vector<hipEvent_t> nx_ev;           // 3 per chunk: before the shards' launches, behind them, behind the merge
-    size_t nx_used = 0;                      // events of the last next-symbol call
-    bool nx_pending = false;
+    ChunkTimer<2> tm_nx;                     // the last next-symbol call: the shards' launches, the merge (q: contexts)
     u64 q_last = 0;                          // contexts of the last launch of any kind
-    u32 chunk_last = 0;
-    double nx_ms = 0.0, mg_ms = 0.0;
     // matching statistics (token_shard_match.hpp, capi_token_shard_match.hpp)
     DevBuf m_ms;                             // u32[total * S]: the per-shard lengths of the last match launch, position-major
     DevBuf m_per, m_merged;                  // staging of the host forms
@@ -44,12 +42,7 @@ struct sa_hip_token_shards {
     DevBuf d_docs, d_offs, d_heads, d_sum;   // the per-pair lists and heads of one chunk; the counter of the streamed ranks
     DevBuf od_docs, od_offs, od_heads;       // merged output of one chunk / the locate output (host forms)
     LaunchTimer tm_lc;                       // the last locate launch
-    std::vector<hipEvent_t> dc_ev;           // 3 per chunk, as nx_ev: before the pair launch, behind it, behind the merge
-    size_t dc_used = 0;
-    bool dc_pending = false;
-    u64 dc_q = 0, dm_q = 0;                  // pairs / contexts of the last pair / merge launches
-    u32 dc_chunk = 0;
-    double dc_ms = 0.0, dm_ms = 0.0;
+    ChunkTimer<2> tm_dc;                     // the last docs call: the pair launch, the merge (q: contexts)
     u64 dc_streamed = 0;
     // per-document counts and AND groups (token_shard_all.hpp, capi_token_shard_all.hpp)
     bool has_ranks = false;                  // rtab describes the shards' rank-by-document arrays as of rank_gen
@@ -65,15 +58,17 @@ struct sa_hip_token_shards {
     hipEvent_t a_copied = nullptr;           // that copy is done: the pinned buffer may be rewritten
     bool a_copy_pending = false;
     LaunchTimer tm_tf;                       // the last doc_counts launch
-    std::vector<hipEvent_t> al_ev;           // 4 per chunk: before the plan launch, behind it, behind the pair launch, behind the merge
-    size_t al_used = 0;
-    bool al_pending = false;
-    u64 al_q = 0, al_pairs_q = 0;            // groups / pairs of the last all call
-    u32 al_chunk = 0;
-    double al_plan_ms = 0.0, al_pairs_ms = 0.0, al_merge_ms = 0.0;
+    ChunkTimer<3> tm_al;                     // the last all call: the plan launch, the pair launch, the merge (q: groups)
     u64 al_streamed = 0;
 
     const tq::View* table() const { return tab.as<tq::View>(); }
+    std::array<LaunchTimer*, 6> timers() { return {&tm_r, &tm_sp, &tm_mt, &tm_md, &tm_lc, &tm_tf}; }
+    auto buffers() {                         // every DevBuf member above
+        return std::array{&tab, &q_pat, &q_off, &r_per, &r_tot, &s_spans, &s_len, &s_tot, &l_sym, &l_cnt, &l_heads, &l_list, &o_sym, &o_cnt,
+                          &o_heads, &m_ms, &m_per, &m_merged, &m_pos, &m_out, &m_heads, &dtab, &dbase, &d_docs, &d_offs, &d_heads, &d_sum,
+                          &od_docs, &od_offs, &od_heads, &rtab, &a_docs, &a_offs, &a_heads, &a_plan, &a_groups, &a_sum, &oa_heads, &c_docs,
+                          &c_cnt, &c_wr, &a_goff};
+    }
 };
 
 namespace {
@@ -100,72 +95,93 @@ int shards_launch_spans(sa_hip_token_shards* g, const int32_t* pat, const u64* o
     return 0;
 }
 
-// event k of a per-chunk list (nx_ev, dc_ev), created on demand, recorded on the set's stream
-int shards_event(sa_hip_token_shards* g, std::vector<hipEvent_t>& list, size_t k) {
-    while (list.size() <= k) {
-        hipEvent_t e = nullptr;
-        SA_HIP_CHECK(hipEventCreate(&e));
-        list.push_back(e);
-    }
-    SA_HIP_CHECK(hipEventRecord(list[k], g->stream));
+// contexts from the host into the set's staging buffers, their spans into s_spans (and to the caller when asked), lengths and
+// totals into s_len and s_tot
+int shards_stage_spans(sa_hip_token_shards* g, const int32_t* patterns, const uint64_t* offsets, u64 Q, int mode, u32 max_length,
+                       int need_next, sa_hip_token_span* spans) {
+    int rc;
+    const size_t span_bytes = (size_t)Q * g->S * sizeof(sa_hip_token_span);
+    if ((rc = token_upload(g->q_pat, g->q_off, g->stream, patterns, offsets, Q)) || (rc = g->s_spans.ensure(span_bytes)) ||
+        (rc = g->s_len.ensure((size_t)Q * 4)) || (rc = g->s_tot.ensure((size_t)Q * 8))) return rc;
+    if ((rc = shards_launch_spans(g, g->q_pat.as<int32_t>(), g->q_off.as<u64>(), Q, mode, max_length, need_next, g->s_len.as<u32>(),
+                                  g->s_tot.as<u64>(), g->s_spans.as<sa_hip_token_span>()))) return rc;
+    if (spans) SA_HIP_CHECK(hipMemcpyAsync(spans, g->s_spans.p, span_bytes, hipMemcpyDeviceToHost, g->stream));
     return 0;
 }
-int shards_event(sa_hip_token_shards* g, size_t k) { return shards_event(g, g->nx_ev, k); }
+
+// Rows (contexts, groups) per chunk of a chunked call over Q rows: every family sizes its per-chunk scratch by it.  A (row, shard)
+// pair costs cap * 8 bytes of list and a 16-byte head in each of them.
+u64 shards_chunk(const sa_hip_token_shards* g, u32 cap, u64 Q) { return tq::shard_chunk(g->chunk_knob, g->S, cap, Q); }
+
+// rows [c0, c0 + n) of a chunked call, and where the merge of this chunk writes them: the caller's device arrays in place, or the
+// set's staging of one chunk (host form); a and b are NULL when cap == 0
+template <class Head, class A, class B>
+struct ShardChunk {
+    u64 c0, n;
+    Head* heads;
+    A* a;
+    B* b;
+};
+
+// The walk of a chunked call over Q rows, chunk (from shards_chunk, by which the caller sized its scratch) rows at a time.  Every
+// chunk runs its stages in order, as many as tm counts, with a mark of tm in front of the first and behind each, and is published;
+// in the host form it comes back through token_rows_out before the next chunk overwrites the staging s_heads / s_a / s_b, which
+// grows here with the host scratch, once per call.
+template <class Head, class A, class B, u32 STAGES, class... Stage>
+int shards_chunks(sa_hip_token_shards* g, const char* who, ChunkTimer<STAGES>& tm, u64 Q, u32 cap, u64 chunk, bool to_host, DevBuf& s_heads,
+                  Head* heads, DevBuf& s_a, A* a, DevBuf& s_b, B* b, Stage&&... stage) {
+    static_assert(sizeof...(Stage) == STAGES, "one launch per stage of the stopwatch");
+    int rc;
+    const size_t cells = (size_t)chunk * cap;
+    HostRows<A, B> h;
+    if (to_host && ((rc = s_heads.ensure((size_t)chunk * sizeof(Head))) || (rc = s_a.ensure(cells * sizeof(A))) ||
+                    (rc = s_b.ensure(cells * sizeof(B))) || (rc = h.reserve(who, cells)))) return rc;
+    tm.restart();
+    for (u64 c0 = 0; c0 < Q; c0 += chunk) {
+        const ShardChunk<Head, A, B> c{c0, Q - c0 < chunk ? Q - c0 : chunk, to_host ? s_heads.as<Head>() : heads + c0,
+                                       !cap ? nullptr : to_host ? s_a.as<A>() : a + c0 * cap, !cap ? nullptr : to_host ? s_b.as<B>() : b + c0 * cap};
+        auto timed = [&](auto& launch) { return (rc = launch(c)) || (rc = tm.mark(g->stream)); };   // true: failed, rc says how
+        if ((rc = tm.mark(g->stream)) || (timed(stage) || ...)) return rc;   // the stages from left to right, up to the first that fails
+        tm.publish();
+        if (to_host && (rc = token_rows_out(g->stream, c.n, cap, c.heads, heads + c0, c.a, a + c0 * cap, c.b, b + c0 * cap, h))) return rc;
+    }
+    tm.finish(Q, (u32)chunk);
+    return 0;
+}
 
 // Next symbols of the device spans [S * Q], chunk by chunk: every shard's launch_next on its slice, then the merge.  Device
 // outputs (to_host false): written in place.  Host outputs: every chunk is merged into o_* and its written entries copied out.
 int shards_next(sa_hip_token_shards* g, const sa_hip_token_span* spans, u64 Q, u32 cap, int32_t* symbols, u64* counts,
                 sa_hip_token_shards_next* heads, bool to_host) {
-    const char* who = "sa_hip_token_shards_next_batch";
     int rc;
     const u32 S = g->S;
-    const u64 chunk = tq::shard_chunk(g->chunk_knob, S, cap, Q);
+    const u64 chunk = shards_chunk(g, cap, Q);
     const size_t cells = (size_t)chunk * cap;
     bool lanes = false;
     for (u32 s = 0; s < S; ++s) lanes = lanes || g->shard[s]->next_knobs.lanes;
     if ((rc = g->l_sym.ensure(cells * S * 4)) || (rc = g->l_cnt.ensure(cells * S * 4)) ||
         (rc = g->l_heads.ensure((size_t)chunk * S * sizeof(sa_hip_token_next))) || (lanes && (rc = g->l_list.ensure(64 + (size_t)chunk * 4)))) return rc;
-    std::vector<int32_t> hs;
-    std::vector<u64> hc;
-    if (to_host) {
-        if ((rc = g->o_sym.ensure(cells * 4)) || (rc = g->o_cnt.ensure(cells * 8)) || (rc = g->o_heads.ensure((size_t)chunk * sizeof(sa_hip_token_shards_next)))) return rc;
-        try { hs.resize(cells); hc.resize(cells); } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "host allocation"); }
-    }
     u32* n_list = lanes ? g->l_list.as<u32>() : nullptr;
-    size_t ev = 0;
-    for (u64 c0 = 0; c0 < Q; c0 += chunk) {
-        const u64 qc = Q - c0 < chunk ? Q - c0 : chunk;
-        if ((rc = shards_event(g, ev++))) return rc;
+    auto lists = [&](const auto& c) -> int {
         for (u32 s = 0; s < S; ++s) {
             const sa_hip_token_index* t = g->shard[s];
-            const tq::NextArgs a{spans + (u64)s * Q + c0, qc, cap, g->l_sym.as<int32_t>() + (u64)s * qc * cap, g->l_cnt.as<u32>() + (u64)s * qc * cap,
-                                 g->l_heads.as<sa_hip_token_next>() + (u64)s * qc};
-            if ((rc = tq::launch_next(t->x, g->stream, t->next_knobs, a, n_list ? n_list + 16 : nullptr, n_list))) return rc;
+            const tq::NextArgs a{spans + (u64)s * Q + c.c0, c.n, cap, g->l_sym.as<int32_t>() + (u64)s * c.n * cap,
+                                 g->l_cnt.as<u32>() + (u64)s * c.n * cap, g->l_heads.as<sa_hip_token_next>() + (u64)s * c.n};
+            if (int r = tq::launch_next(t->x, g->stream, t->next_knobs, a, n_list ? n_list + 16 : nullptr, n_list)) return r;
         }
-        if ((rc = shards_event(g, ev++))) return rc;
+        return 0;
+    };
+    auto merge = [&](const auto& c) -> int {
         tq::MergeArgs m{};
         m.sym = g->l_sym.as<int32_t>(); m.cnt = g->l_cnt.as<u32>(); m.heads = g->l_heads.as<sa_hip_token_next>();
-        m.spans = spans + c0; m.span_stride = Q;
-        m.Q = qc; m.S = S; m.cap = cap;
-        m.out_sym = to_host ? g->o_sym.as<int32_t>() : symbols + c0 * cap;
-        m.out_cnt = to_host ? g->o_cnt.as<u64>() : counts + c0 * cap;
-        m.out_heads = to_host ? g->o_heads.as<sa_hip_token_shards_next>() : heads + c0;
-        if ((rc = tq::launch_merge(g->stream, m))) return rc;
-        if ((rc = shards_event(g, ev++))) return rc;
-        g->nx_used = ev;
-        g->nx_pending = true;
-        if (to_host) {
-            SA_HIP_CHECK(hipMemcpyAsync(heads + c0, g->o_heads.p, (size_t)qc * sizeof(sa_hip_token_shards_next), hipMemcpyDeviceToHost, g->stream));
-            SA_HIP_CHECK(hipMemcpyAsync(hs.data(), g->o_sym.p, (size_t)qc * cap * 4, hipMemcpyDeviceToHost, g->stream));
-            SA_HIP_CHECK(hipMemcpyAsync(hc.data(), g->o_cnt.p, (size_t)qc * cap * 8, hipMemcpyDeviceToHost, g->stream));
-            SA_HIP_CHECK(hipStreamSynchronize(g->stream));
-            const StridedLen written{&heads[c0].written, sizeof heads[0]};
-            copy_written_rows(symbols + c0 * cap, hs.data(), qc, cap, written);
-            copy_written_rows(counts + c0 * cap, hc.data(), qc, cap, written);
-        }
-    }
+        m.spans = spans + c.c0; m.span_stride = Q;
+        m.Q = c.n; m.S = S; m.cap = cap;
+        m.out_sym = c.a; m.out_cnt = c.b; m.out_heads = c.heads;
+        return tq::launch_merge(g->stream, m);
+    };
+    if ((rc = shards_chunks(g, "sa_hip_token_shards_next_batch", g->tm_nx, Q, cap, chunk, to_host, g->o_heads, heads, g->o_sym, symbols, g->o_cnt, counts,
+                            lists, merge))) return rc;
     g->q_last = Q;
-    g->chunk_last = (u32)chunk;
     return 0;
 }
 
@@ -178,22 +194,11 @@ void sa_hip_token_shards_destroy(sa_hip_token_shards* g) {
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     for (u32 s = 0; s < g->S; ++s) sa_hip_token_index_destroy(g->shard[s]);
-    g->tab.release(); g->q_pat.release(); g->q_off.release(); g->r_per.release(); g->r_tot.release();
-    g->s_spans.release(); g->s_len.release(); g->s_tot.release();
-    g->l_sym.release(); g->l_cnt.release(); g->l_heads.release(); g->l_list.release();
-    g->o_sym.release(); g->o_cnt.release(); g->o_heads.release();
-    g->m_ms.release(); g->m_per.release(); g->m_merged.release(); g->m_pos.release(); g->m_out.release(); g->m_heads.release();
-    g->dtab.release(); g->dbase.release(); g->d_docs.release(); g->d_offs.release(); g->d_heads.release(); g->d_sum.release();
-    g->od_docs.release(); g->od_offs.release(); g->od_heads.release();
-    g->rtab.release(); g->a_docs.release(); g->a_offs.release(); g->a_heads.release(); g->a_plan.release(); g->a_groups.release();
-    g->a_sum.release(); g->oa_heads.release(); g->c_docs.release(); g->c_cnt.release(); g->c_wr.release(); g->a_goff.release();
+    for (DevBuf* b : g->buffers()) b->release();
     if (g->a_goff_pin) (void)hipHostFree(g->a_goff_pin);
     if (g->a_copied) (void)hipEventDestroy(g->a_copied);
-    g->tm_tf.destroy();
-    for (hipEvent_t e : g->al_ev) (void)hipEventDestroy(e);
-    g->tm_r.destroy(); g->tm_sp.destroy(); g->tm_mt.destroy(); g->tm_md.destroy(); g->tm_lc.destroy();
-    for (hipEvent_t e : g->nx_ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : g->dc_ev) (void)hipEventDestroy(e);
+    for (LaunchTimer* w : g->timers()) w->destroy();
+    g->tm_nx.destroy(); g->tm_dc.destroy(); g->tm_al.destroy();
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -217,12 +222,7 @@ int sa_hip_token_shards_create(sa_hip_token_shards** out, sa_hip_token_index* co
     if (const char* e = diag_env("SA_HIP_TOKEN_SHARD_CHUNK")) g->chunk_knob = strtoull(e, nullptr, 10);
     auto run = [&]() -> int {
         SA_HIP_CHECK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-        SA_HIP_CHECK(g->tm_r.create());
-        SA_HIP_CHECK(g->tm_sp.create());
-        SA_HIP_CHECK(g->tm_mt.create());
-        SA_HIP_CHECK(g->tm_md.create());
-        SA_HIP_CHECK(g->tm_lc.create());
-        SA_HIP_CHECK(g->tm_tf.create());
+        for (LaunchTimer* w : g->timers()) SA_HIP_CHECK(w->create());
         SA_HIP_CHECK(hipEventCreate(&g->a_copied));
         tq::View v[tq::SHARDS_MAX];
         for (u32 s = 0; s < S; ++s) {
@@ -263,31 +263,19 @@ int sa_hip_token_shards_info(const sa_hip_token_shards* cg, sa_hip_token_shards_
     if (!cg || !out) return fail(SA_HIP_EINVAL, "sa_hip_token_shards_info", "NULL argument");
     sa_hip_token_shards* g = const_cast<sa_hip_token_shards*>(cg);
     std::lock_guard<std::mutex> lk(g->mu);
-    if (g->tm_r.pending || g->tm_sp.pending || g->nx_pending) {
+    if (g->tm_r.pending || g->tm_sp.pending || g->tm_nx.pending) {
         int rc = set_device(g->device);
-        if (rc || (rc = g->tm_r.resolve()) || (rc = g->tm_sp.resolve())) return rc;
-        if (g->nx_pending) {
-            float ms = 0.f;
-            SA_HIP_CHECK(hipEventSynchronize(g->nx_ev[g->nx_used - 1]));
-            g->nx_ms = g->mg_ms = 0.0;
-            for (size_t k = 0; k + 3 <= g->nx_used; k += 3) {
-                SA_HIP_CHECK(hipEventElapsedTime(&ms, g->nx_ev[k], g->nx_ev[k + 1]));
-                g->nx_ms += ms;
-                SA_HIP_CHECK(hipEventElapsedTime(&ms, g->nx_ev[k + 1], g->nx_ev[k + 2]));
-                g->mg_ms += ms;
-            }
-            g->nx_pending = false;
-        }
+        if (rc || (rc = g->tm_r.resolve()) || (rc = g->tm_sp.resolve()) || (rc = g->tm_nx.resolve())) return rc;
     }
     memset(out, 0, sizeof *out);
     out->shards = g->S;
-    out->chunk = g->chunk_last;
+    out->chunk = g->tm_nx.chunk;
     out->tokens = g->tokens;
     out->q = g->q_last;
     out->ranges_ms = g->tm_r.ms;
     out->spans_ms = g->tm_sp.ms;
-    out->next_ms = g->nx_ms;
-    out->merge_ms = g->mg_ms;
+    out->next_ms = g->tm_nx.ms[0];
+    out->merge_ms = g->tm_nx.ms[1];
     return 0;
 }
 
@@ -350,14 +338,9 @@ int sa_hip_token_shards_spans_batch(sa_hip_token_shards* g, const int32_t* patte
     if ((rc = token_offsets_args(who, patterns, offsets, Q))) return rc;
     std::lock_guard<std::mutex> lk(g->mu);
     if ((rc = set_device(g->device))) return rc;
-    const size_t span_bytes = (size_t)Q * g->S * sizeof(sa_hip_token_span);
-    if ((rc = token_upload(g->q_pat, g->q_off, g->stream, patterns, offsets, Q)) || (rc = g->s_spans.ensure(span_bytes)) || (rc = g->s_len.ensure((size_t)Q * 4)) ||
-        (rc = g->s_tot.ensure((size_t)Q * 8))) return rc;
-    if ((rc = shards_launch_spans(g, g->q_pat.as<int32_t>(), g->q_off.as<u64>(), Q, mode, max_length, need_next, g->s_len.as<u32>(), g->s_tot.as<u64>(),
-                                  g->s_spans.as<sa_hip_token_span>()))) return rc;
+    if ((rc = shards_stage_spans(g, patterns, offsets, Q, mode, max_length, need_next, spans))) return rc;
     SA_HIP_CHECK(hipMemcpyAsync(length, g->s_len.p, (size_t)Q * 4, hipMemcpyDeviceToHost, g->stream));
     SA_HIP_CHECK(hipMemcpyAsync(totals, g->s_tot.p, (size_t)Q * 8, hipMemcpyDeviceToHost, g->stream));
-    SA_HIP_CHECK(hipMemcpyAsync(spans, g->s_spans.p, span_bytes, hipMemcpyDeviceToHost, g->stream));
     SA_HIP_CHECK(hipStreamSynchronize(g->stream));
     return 0;
 }
@@ -388,12 +371,7 @@ int sa_hip_token_shards_next_batch(sa_hip_token_shards* g, const int32_t* patter
     if ((rc = token_offsets_args(who, patterns, offsets, Q))) return rc;
     std::lock_guard<std::mutex> lk(g->mu);
     if ((rc = set_device(g->device))) return rc;
-    const size_t span_bytes = (size_t)Q * g->S * sizeof(sa_hip_token_span);
-    if ((rc = token_upload(g->q_pat, g->q_off, g->stream, patterns, offsets, Q)) || (rc = g->s_spans.ensure(span_bytes)) || (rc = g->s_len.ensure((size_t)Q * 4)) ||
-        (rc = g->s_tot.ensure((size_t)Q * 8))) return rc;
-    if ((rc = shards_launch_spans(g, g->q_pat.as<int32_t>(), g->q_off.as<u64>(), Q, mode, max_length, need_next, g->s_len.as<u32>(), g->s_tot.as<u64>(),
-                                  g->s_spans.as<sa_hip_token_span>()))) return rc;
-    if (spans) SA_HIP_CHECK(hipMemcpyAsync(spans, g->s_spans.p, span_bytes, hipMemcpyDeviceToHost, g->stream));
+    if ((rc = shards_stage_spans(g, patterns, offsets, Q, mode, max_length, need_next, spans))) return rc;
     return shards_next(g, g->s_spans.as<sa_hip_token_span>(), Q, cap, symbols, counts, heads, true);
 }
 

@@ -462,6 +462,32 @@ def test_chunks(gpu, randoms, monkeypatch, chunk):
         assert int(want["heads"]["matched"].sum()) > 0
 
 
+def test_info_follows_the_last_all_call(gpu, randoms, monkeypatch):
+    """the per-chunk stopwatch: zeros before the first call, the figures of a call in 7 chunks, then of a call in one chunk on the
+    same set; asking twice changes nothing"""
+    name = "r3"
+    cases = sd.random_set(name)
+    pats = sa.frequent_patterns(cases)
+    groups = [[0, 1], [2, 3, 4], [5], [6, 7], [8, 9], [10, 11, 12, 13], [14, 15]]
+    stages = ("plan_ms", "pairs_ms", "merge_ms")
+    monkeypatch.setenv("SA_HIP_TOKEN_SHARD_CHUNK", "1")
+    with _build(gpu, cases) as st:
+        none = st.doc_ranks_info()
+        assert all(none[k] == 0 for k in stages + ("chunk", "plan_q", "pairs_q", "merge_q", "streamed")), none
+        for cap in (1, 3):
+            for some in (groups, groups[:1]):                                                         # 7 chunks, then 1
+                flat_i, goff = sa.flat_groups(some)
+                flat = [pats[i] for i in flat_i]
+                want = randoms[name].all_batch(flat, goff, cap=cap, fill=FILL)
+                got = st.all_batch(flat, goff, cap=cap, fill=FILL)
+                assert all(got[k].tobytes() == want[k].tobytes() for k in want), (cap, len(some))
+                info = st.doc_ranks_info()
+                assert info["chunk"] == 1 and info["plan_q"] == info["merge_q"] == len(some) and info["pairs_q"] == 3 * len(some), info
+                assert info["streamed"] == int(want["heads"]["examined"].sum()), info
+                assert all(np.isfinite(info[k]) and info[k] > 0 for k in stages), info
+                assert st.doc_ranks_info() == info
+
+
 # ---- the merge step alone ------------------------------------------------------------------------------------------------------
 
 def _merge(gpu, st, S, lists, plan, bases, cap):

@@ -365,6 +365,29 @@ def test_chunks(gpu, randoms, monkeypatch, chunk):
         assert randoms[name].docs_info()["chunk"] == 7
 
 
+def test_info_follows_the_last_docs_call(gpu, randoms, monkeypatch):
+    """the per-chunk stopwatch: zeros before the first call, the figures of a call in 7 chunks, then of a call in one chunk on the
+    same set; asking twice changes nothing"""
+    name = "r3"
+    cases = sd.random_set(name)
+    ctx = sd.random_patterns(cases)[4:11]
+    assert len(ctx) == 7
+    monkeypatch.setenv("SA_HIP_TOKEN_SHARD_CHUNK", "1")
+    with _build(gpu, cases) as st:
+        none = st.docs_info()
+        assert none["pairs_ms"] == 0 and none["merge_ms"] == 0 and none["chunk"] == 0 and none["pairs_q"] == 0 and none["streamed"] == 0, none
+        for cap in (1, 3):
+            for part in (ctx, ctx[:1]):                                                               # 7 chunks, then 1
+                want = randoms[name].docs_batch(part, cap=cap, fill=FILL)
+                got = st.docs_batch(part, cap=cap, fill=FILL)
+                assert all(got[k].tobytes() == want[k].tobytes() for k in want), (cap, len(part))
+                info = st.docs_info()
+                assert info["chunk"] == 1 and info["pairs_q"] == 3 * len(part) and info["merge_q"] == len(part), info
+                assert info["streamed"] == int(want["heads"]["examined"].sum()), info
+                assert all(np.isfinite(info[k]) and info[k] > 0 for k in ("pairs_ms", "merge_ms")), info
+                assert st.docs_info() == info
+
+
 # ---- the merge step alone ------------------------------------------------------------------------------------------------------
 
 def _merge(gpu, st, S, lists, bases, cap):

@@ -185,6 +185,28 @@ def test_chunk_edges(gpu, sets, monkeypatch, chunk):
         assert t1.cpu().numpy().tolist() == t2.cpu().numpy().tolist() == e["count"].astype(np.int64).sum(axis=0).tolist()
 
 
+def test_info_follows_the_last_next_call(gpu, sets, monkeypatch):
+    """the per-chunk stopwatch: zeros before the first call, the figures of a call in 7 chunks, then of a call in one chunk on the
+    same set; asking twice changes nothing"""
+    name = "s3_k2"
+    e = sc.expected(name)
+    ctx = e["ctx"][3:10]
+    assert len(ctx) == 7
+    monkeypatch.setenv("SA_HIP_TOKEN_SHARD_CHUNK", "1")
+    with gpu.TokenShards.build(e["shards"]) as st:
+        none = st.info()
+        assert none["next_ms"] == 0 and none["merge_ms"] == 0 and none["chunk"] == 0 and none["q"] == 0, none
+        for cap in (1, 3):
+            for part in (ctx, ctx[:1]):                                                               # 7 chunks, then 1
+                want = sets[name].next_batch(part, cap=cap, mode=1, fill=FILL)
+                got = st.next_batch(part, cap=cap, mode=1, fill=FILL)
+                assert all(got[k].tobytes() == want[k].tobytes() for k in want), (cap, len(part))
+                info = st.info()
+                assert info["chunk"] == 1 and info["q"] == len(part), info
+                assert all(np.isfinite(info[k]) and info[k] > 0 for k in ("next_ms", "merge_ms")), info
+                assert st.info() == info
+
+
 def _merge(gpu, st, S, lists, cap):
     """lists[s][i] = (symbols, counts, written, total) -> the merged (symbols, counts, heads) of the device, canaries kept"""
     import torch
