@@ -715,7 +715,8 @@ int sa_hip_token_index_next_info(const sa_hip_token_index* t, sa_hip_token_next_
  * Matching statistics of a query text over the set -- sa_hip_token_shards_match_* -- stand behind (6f), whose terms and head
  * record they use: see "(6c, matching statistics)" there.  Documents over a set -- locate, the distinct documents of an n-gram and
  * its document frequency, sa_hip_token_shards_locate_* and _docs_* -- are (6g).  Per-document counts and AND groups over a set --
- * sa_hip_token_shards_doc_counts_* and _all_* -- are (6h). */
+ * sa_hip_token_shards_doc_counts_* and _all_* -- are (6h).  Infinity-gram scores of a query text over a set --
+ * sa_hip_token_shards_score_* -- are (6j), behind (6i) whose terms and head record they use. */
 typedef struct sa_hip_token_shards sa_hip_token_shards;
 
 typedef struct sa_hip_token_shards_next {
@@ -1310,6 +1311,71 @@ int sa_hip_token_index_score_docs_batch_device(sa_hip_token_index* t, const void
 int sa_hip_token_index_score_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
                                    uint32_t max_length, sa_hip_token_score* scores, sa_hip_token_score_head* heads);
 int sa_hip_token_index_score_info(const sa_hip_token_index* t, sa_hip_token_score_info* out);
+
+/* (6j) infinity-gram scores over a shard set (csrc/token_shard_score.hpp, csrc/capi_token_shard_score.hpp): the calls of (6i)
+ * answered for the whole corpus of a set.  All results are exact; no floating point is computed on the device.
+ *
+ * The batch layout, M = max_length, s(j), the flat positions and total = offsets[Q] are those of (6i); S shards, n_s the length of
+ * shard s, max_n the longest.  For a context C, eff_s(C) = count_s(C) - ended_s(C) is its effective count in shard s as in (6i)
+ * (the empty context: n_s), and eff(C) the sum over the shards.  For a position j inside a document,
+ *   scores[j]     length         L(j): the largest L <= min(j - s(j), M, max_n) such that eff(patterns[j - L .. j)) >= 1;
+ *                 context_count  that eff: >= 1 whenever some shard is not empty;
+ *                 token_count    the sum over s of the occurrences of patterns[j - L .. j] in shard s: <= context_count, and 0
+ *                                for a token no shard holds behind the context;
+ *                 shards         the shards whose own token_count is > 0;
+ *   per_shard     [s * total + j], shard-major like every per-shard array of the set: what shard s's own spans_batch answers in
+ *                 mode 0 for the (L(j) + 1)-gram patterns[j - L .. j] -- {first, count, L + 1, ended}, count 0 with the exact lower
+ *                 bound where the shard does not hold it (also where it does not hold the context), zeros from an empty shard.
+ * A position outside every document (j < offsets[0]) gives zeros in scores and in every shard's cell; a set of empty shards gives
+ * zeros everywhere.  The token's probability is token_count / context_count.  The docs step gives the head of (6i) per document:
+ * seen = its positions with token_count > 0, certain = those with token_count == context_count; an empty document has a head of
+ * zeros.  With S == 1 length, context_count, token_count, per_shard[..].first / .count and the heads equal the single index's.
+ *
+ * The set defines its corpus as the shards' texts side by side: a context whose only occurrence in the concatenation lies across
+ * a cut is not an occurrence, and the set answers a shorter L there than an unsharded index of the concatenation would.
+ *
+ * merged_dev of the score call is NULL, or the records sa_hip_token_shards_match_batch_device wrote for the SAME batch and the SAME
+ * max_length.  With them the candidate context comes from a binary search over these records and one range search per shard; where
+ * every shard that holds the candidate holds it only as the tail of its text (up to S shards can share a tail), a search over the
+ * shorter contexts follows.  Without them that search starts from the capped context.  Both give the same records, byte for byte.
+ * The host form takes the first way and runs the match launches itself, into buffers of the set.
+ *
+ * Errors returned as -1 before the set is dereferenced and before any HIP call: a NULL set or a NULL required pointer,
+ * total >= 2^31, in the host form descending offsets and scores, per_shard and heads all NULL; Q == 0 is a no-op returning 0; no
+ * usable device -3.  (S <= 64 and total < 2^31 keep the S * total lanes of a launch below 2^31 workgroups; the launch tests it all
+ * the same.)  The device forms are asynchronous on the set's stream until sa_hip_token_shards_sync and chain behind
+ * sa_hip_token_shards_match_batch_device without a host trip; per_shard_dev (required, sa_hip_token_span[S * total]) has the layout
+ * of the set's span output with Q = total, so sa_hip_token_shards_next_batch_device, _locate_batch_device and _docs_batch_device
+ * take it as it is.  They trust nothing: every loop is bounded, a context's start is clamped to its document and to the batch.  A
+ * scratch of 3 * S * total uint32 belongs to the set and grows on demand. */
+typedef struct sa_hip_token_shards_score {
+    uint32_t length;          /* L(j): symbols of the context                                         */
+    uint32_t shards;          /* shards that hold the context followed by the token at j              */
+    uint64_t context_count;   /* occurrences of the context over all shards with a token behind them  */
+    uint64_t token_count;     /* occurrences of the context followed by the token at j, over all      */
+} sa_hip_token_shards_score;
+
+typedef struct sa_hip_token_shards_score_stats {
+    uint64_t q;               /* documents of the last launch of either kind                          */
+    uint64_t positions;       /* positions of the last score launches                                 */
+    double   match_ms;        /* HIP-event time of the last three match launches together             */
+    double   score_ms;        /* ... of the last three score launches together                        */
+    double   docs_ms;         /* ... of the last score docs launch                                    */
+} sa_hip_token_shards_score_stats;
+
+/* merged_dev: NULL, or sa_hip_token_shards_match[total] as sa_hip_token_shards_match_batch_device wrote them for this batch and
+ * max_length; scores_dev: sa_hip_token_shards_score[total]; per_shard_dev: sa_hip_token_span[S * total]; total = offsets[Q]. */
+int sa_hip_token_shards_score_batch_device(sa_hip_token_shards* set, const void* patterns_dev, const void* offsets_dev, uint64_t Q,
+                                           uint64_t total, uint32_t max_length, const void* merged_dev, void* scores_dev,
+                                           void* per_shard_dev);
+/* scores_dev as the call above writes them (may be NULL when every document is empty); heads_dev: sa_hip_token_score_head[Q]. */
+int sa_hip_token_shards_score_docs_batch_device(sa_hip_token_shards* set, const void* scores_dev, const void* offsets_dev, uint64_t Q,
+                                                void* heads_dev);
+/* Host pointers; scores[offsets[Q]], per_shard[S * offsets[Q]] and heads[Q] out, any of them may be NULL, not all three. */
+int sa_hip_token_shards_score_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                    uint32_t max_length, sa_hip_token_shards_score* scores, sa_hip_token_span* per_shard,
+                                    sa_hip_token_score_head* heads);
+int sa_hip_token_shards_score_info(const sa_hip_token_shards* set, sa_hip_token_shards_score_stats* out);
 
 /* ---- instrumentation ---------------------------------------------------------------------- */
 

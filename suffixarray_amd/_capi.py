@@ -26,6 +26,8 @@ SCORE_HEAD_DTYPE = np.dtype([("scored", "<u4"), ("seen", "<u4"), ("certain", "<u
 TOKEN_ALL_MAX = 16                                                                                          # SA_HIP_TOKEN_ALL_MAX
 SHARDS_NEXT_DTYPE = np.dtype([("written", "<u4"), ("length", "<u4"), ("covered", "<u8"), ("total", "<u8")])  # sa_hip_token_shards_next
 SHARDS_MATCH_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("count", "<u8")])                      # sa_hip_token_shards_match
+SHARDS_SCORE_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("context_count", "<u8"),
+                               ("token_count", "<u8")])                                                    # sa_hip_token_shards_score
 SHARDS_LOCATE_DTYPE = np.dtype([("written", "<u4"), ("reserved", "<u4"), ("count", "<u8")])                  # sa_hip_token_shards_locate
 SHARDS_DOCS_DTYPE = np.dtype([("written", "<u4"), ("reserved", "<u4"), ("examined", "<u8"), ("distinct", "<u8"),
                               ("count", "<u8")])                                                            # sa_hip_token_shards_docs
@@ -72,6 +74,8 @@ EXPORTS = [
     "sa_hip_token_shards_next_batch_device", "sa_hip_token_shards_merge_device",
     "sa_hip_token_shards_match_batch_device", "sa_hip_token_shards_match_docs_batch_device", "sa_hip_token_shards_match_batch",
     "sa_hip_token_shards_match_docs_batch", "sa_hip_token_shards_match_info",
+    "sa_hip_token_shards_score_batch_device", "sa_hip_token_shards_score_docs_batch_device", "sa_hip_token_shards_score_batch",
+    "sa_hip_token_shards_score_info",
     "sa_hip_token_shards_set_documents", "sa_hip_token_shards_adopt_documents", "sa_hip_token_shards_doc_bases",
     "sa_hip_token_shards_docs_info", "sa_hip_token_shards_locate_batch_device", "sa_hip_token_shards_locate_batch",
     "sa_hip_token_shards_docs_batch_device", "sa_hip_token_shards_docs_batch", "sa_hip_token_shards_docs_merge_device",
@@ -299,6 +303,19 @@ class TokenShardsMatch(C.Structure):
 class TokenShardsMatchStats(C.Structure):
     """sa_hip_token_shards_match_stats: the last match and match-docs launches of a shard set."""
     _fields_ = [("q", C.c_uint64), ("positions", C.c_uint64), ("match_ms", C.c_double), ("docs_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenShardsScore(C.Structure):
+    _fields_ = [("length", C.c_uint32), ("shards", C.c_uint32), ("context_count", C.c_uint64), ("token_count", C.c_uint64)]
+
+
+class TokenShardsScoreStats(C.Structure):
+    """sa_hip_token_shards_score_stats: the last match, score and score-docs launches of a shard set."""
+    _fields_ = [("q", C.c_uint64), ("positions", C.c_uint64), ("match_ms", C.c_double), ("score_ms", C.c_double),
+                ("docs_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -690,6 +707,14 @@ def lib():
     L.sa_hip_token_shards_match_docs_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.sa_hip_token_shards_match_info.restype = C.c_int
     L.sa_hip_token_shards_match_info.argtypes = [vp, C.POINTER(TokenShardsMatchStats)]
+    L.sa_hip_token_shards_score_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_score_batch_device.argtypes = [vp, vp, vp, u64, u64, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_shards_score_docs_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_score_docs_batch_device.argtypes = [vp, vp, vp, u64, vp]
+    L.sa_hip_token_shards_score_batch.restype = C.c_int
+    L.sa_hip_token_shards_score_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_shards_score_info.restype = C.c_int
+    L.sa_hip_token_shards_score_info.argtypes = [vp, C.POINTER(TokenShardsScoreStats)]
     L.sa_hip_token_shards_set_documents.restype = C.c_int
     L.sa_hip_token_shards_set_documents.argtypes = [vp, vp, vp]
     L.sa_hip_token_shards_adopt_documents.restype = C.c_int
@@ -1823,6 +1848,38 @@ class TokenShards(_TokenHandle):
 
     def match_info(self):
         return self._info(self._lib.sa_hip_token_shards_match_info, TokenShardsMatchStats)
+
+    def score_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, total, max_length, merged_dev_ptr, scores_dev_ptr, per_shard_dev_ptr):
+        """The score over all shards of every one of the `total` = offsets[q] positions of q device documents (max_length 0: no cap)
+        into scores_dev_ptr[total], and every shard's span of the context with the token into per_shard_dev_ptr[S * total].
+        merged_dev_ptr: what match_batch_device wrote for the same batch and max_length, or None (the search over the context
+        length instead).  Asynchronous on the set's stream until sync()."""
+        check(self._lib.sa_hip_token_shards_score_batch_device(self._h, patterns_dev_ptr, offsets_dev_ptr, q, int(total), int(max_length),
+                                                               merged_dev_ptr, scores_dev_ptr, per_shard_dev_ptr))
+
+    def score_docs_batch_device(self, scores_dev_ptr, offsets_dev_ptr, q, heads_dev_ptr):
+        """The heads of q device documents from the scores score_batch_device wrote; asynchronous until sync()."""
+        check(self._lib.sa_hip_token_shards_score_docs_batch_device(self._h, scores_dev_ptr, offsets_dev_ptr, q, heads_dev_ptr))
+
+    def score_batch(self, docs, max_length=0, scores=True, per_shard=True, heads=True):
+        """docs as the patterns of query_batch: query documents.  -> dict: scores (length, shards, context_count, token_count)
+        [offsets[Q]], for every position the longest context before it (at most max_length symbols, 0: no cap) that some shard
+        holds with a token behind it, how often over all shards, how often followed by the token at the position and in how many
+        shards; per_shard (first, count, length, ended)[S, offsets[Q]], every shard's span of that context with the token; heads
+        (scored, seen, certain, longest, length_sum)[Q].  An output that is False is not fetched (None)."""
+        if not scores and not per_shard and not heads:
+            raise ValueError("score_batch: scores, per_shard or heads")
+        buf, off, q = self._contexts(docs)
+        total = int(off[q]) if q else 0
+        sc = _rows(total, SHARDS_SCORE_DTYPE) if scores else None
+        per = self._shard_rows(total, SPAN_DTYPE) if per_shard else None
+        hd = _rows(q, SCORE_HEAD_DTYPE) if heads else None
+        self._call(q, self._lib.sa_hip_token_shards_score_batch, _ptr(buf), _ptr(off), q, int(max_length), _ptr(sc), _ptr(per), _ptr(hd))
+        return {"scores": sc[:total] if scores else None, "per_shard": per[:, :total] if per_shard else None,
+                "heads": hd[:q] if heads else None}
+
+    def score_info(self):
+        return self._info(self._lib.sa_hip_token_shards_score_info, TokenShardsScoreStats)
 
     def set_documents(self, starts):
         """starts: one table per shard as TokenIndex.set_documents takes it (every table is checked before a shard is touched);

@@ -1,7 +1,7 @@
 // capi_token_shards.hpp -- the C ABI of the shard set (include/sa_hip.h section 6c), included by sa_capi.hip behind capi_token.hpp
 // (same translation unit).  The kernels are csrc/token_shards.hpp; the per-shard next symbols are tq::launch_next of every shard.
 // Matching statistics over the set: capi_token_shard_match.hpp; documents over the set: capi_token_shard_docs.hpp; per-document
-// counts and AND groups over the set: capi_token_shard_all.hpp.
+// counts and AND groups over the set: capi_token_shard_all.hpp; infinity-gram scores over the set: capi_token_shard_score.hpp.
 // The stopwatches, the upload of a host batch and token_rows_out are capi_token.hpp's.  What the families of the set share is here:
 // the spans of a host batch (shards_stage_spans) and the walk of a chunked call (shards_chunks: chunk size, per-chunk stopwatch,
 // output pointers of the host and the device form, the way of a chunk's rows to the caller), which the next symbols, the documents
@@ -60,14 +60,19 @@ struct sa_hip_token_shards {
     LaunchTimer tm_tf;                       // the last doc_counts launch
     ChunkTimer<3> tm_al;                     // the last all call: the plan launch, the pair launch, the merge (q: groups)
     u64 al_streamed = 0;
+    // infinity-gram scores (token_shard_score.hpp, capi_token_shard_score.hpp)
+    DevBuf sc_w;                             // u32[3 * total * S]: the scratch planes of the last score launches, position-major
+    DevBuf sc_scores, sc_heads;              // staging of the host form (its per-shard spans go through m_per)
+    LaunchTimer tm_sc, tm_sd;                // the last score launches (q: positions) / score docs launch (q: documents)
+    u64 sc_last = 0;                         // documents of the last launch of either kind
 
     const tq::View* table() const { return tab.as<tq::View>(); }
-    std::array<LaunchTimer*, 6> timers() { return {&tm_r, &tm_sp, &tm_mt, &tm_md, &tm_lc, &tm_tf}; }
+    std::array<LaunchTimer*, 8> timers() { return {&tm_r, &tm_sp, &tm_mt, &tm_md, &tm_lc, &tm_tf, &tm_sc, &tm_sd}; }
     auto buffers() {                         // every DevBuf member above
         return std::array{&tab, &q_pat, &q_off, &r_per, &r_tot, &s_spans, &s_len, &s_tot, &l_sym, &l_cnt, &l_heads, &l_list, &o_sym, &o_cnt,
                           &o_heads, &m_ms, &m_per, &m_merged, &m_pos, &m_out, &m_heads, &dtab, &dbase, &d_docs, &d_offs, &d_heads, &d_sum,
                           &od_docs, &od_offs, &od_heads, &rtab, &a_docs, &a_offs, &a_heads, &a_plan, &a_groups, &a_sum, &oa_heads, &c_docs,
-                          &c_cnt, &c_wr, &a_goff};
+                          &c_cnt, &c_wr, &a_goff, &sc_w, &sc_scores, &sc_heads};
     }
 };
 

@@ -5,9 +5,10 @@
 // This file: the index handle with its build, query, record-retrieval, replica, multi-GPU, CSV and on-disk entry points.
 // capi_dropins.hpp (included below, same translation unit): the libsais- / engine-call-compatible entry points, their device
 // forms and the process-level workspace they share.  capi_token.hpp, capi_token_docs.hpp, capi_token_all.hpp, capi_token_match.hpp and
-// capi_token_shards.hpp with capi_token_shard_match.hpp, capi_token_shard_docs.hpp and capi_token_shard_all.hpp (included at the end):
-// the token index, its documents, per-document counts and AND groups, matching statistics, and sets of token indexes with their
-// matching statistics, documents, per-document counts and AND groups.
+// capi_token_shards.hpp with capi_token_shard_match.hpp, capi_token_shard_score.hpp, capi_token_shard_docs.hpp and
+// capi_token_shard_all.hpp (included at the end): the token index, its documents, per-document counts and AND groups, matching
+// statistics, and sets of token indexes with their matching statistics, infinity-gram scores, documents, per-document counts and
+// AND groups.
 #include <exception>
 #include <mutex>
 #include <new>
@@ -1644,5 +1645,6 @@ int sa_hip_read_suffix_array(sa_hip_SuffixArray_struct* s, const char* sa_filena
 #include "capi_token_score.hpp"
 #include "capi_token_shards.hpp"
 #include "capi_token_shard_match.hpp"
+#include "capi_token_shard_score.hpp"
 #include "capi_token_shard_docs.hpp"
 #include "capi_token_shard_all.hpp"

@@ -40,8 +40,8 @@
 // [0, total) is read.  Match records are read at indices in [0, total) for their length alone.  Records that no match launch
 // wrote, or an in-range array that is not the suffix array, give unspecified answers, never a spin or a read outside the buffers.
 //
-// Not built: the same over a shard set; log-probability sums on the device; carrying LCPs across probes (Manber-Myers); one very
-// long document split over several waves.
+// Not built: log-probability sums on the device; carrying LCPs across probes (Manber-Myers); one very long document split over
+// several waves.  (The same over shard sets is token_shard_score.hpp, which says what is not built there.)
 #pragma once
 #include "token_match.hpp"
 

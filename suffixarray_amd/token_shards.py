@@ -7,6 +7,8 @@
     sti.next_tokens(contexts, cap=64, longest_suffix=True)    # backing off to the longest suffix that ANY shard holds
     sti.matching_statistics([doc])                 # per position: the longest match in any shard, its count, the shards that hold it
     sti.matched_spans([doc], min_length=8)         # the maximal verbatim spans of a text; sti.coverage([doc], 8): how much they cover
+    sti.infgram([doc])                             # per position: the longest context any shard holds, its count, the token's count
+    sti.infgram_probs([doc])                       # token_count / context_count; sti.infgram_summary([doc]): per-document sums
     sti = ShardedTokenIndex([tokens_a, tokens_b], doc_starts=[starts_a, starts_b])     # documents: one table per shard
     sti.locate([464, 2068], limit=10)              # (document uint64, offset int32): ids count through the shards in order
     sti.documents([[464, 2068]], cap=16)           # the distinct documents that hold an n-gram, over all shards
@@ -16,7 +18,7 @@
     sti.count_documents_with_all([[[464, 2068], [11]]])          # (matched uint64[G], exact flags)
 
 The corpus is cut by the caller, at document boundaries: an n-gram never spans two shards, so its count is the sum of the shards'
-counts.  On top of include/sa_hip.h sections 6c, 6g and 6h (suffixarray_amd._capi.TokenShards).  No CPU fallback.
+counts.  On top of include/sa_hip.h sections 6c, 6g, 6h and 6j (suffixarray_amd._capi.TokenShards).  No CPU fallback.
 """
 import numpy as np
 
@@ -118,6 +120,32 @@ class ShardedTokenIndex:
         symbols, longest = its longest match (whatever min_length is), maximal = the number of its maximal spans."""
         h = self._set.match_docs_batch(docs, min_length=min_length, max_length=max_length or 0, cap=0)["heads"]
         return {"covered": h["covered"].copy(), "longest": h["longest"].copy(), "maximal": h["maximal"].copy()}
+
+    def infgram(self, docs, max_length=None):
+        """The infinity-gram score of query texts over all shards.  docs: a list of int sequences.  -> one (length, context_count,
+        token_count) per document, arrays over its positions: length[i] (uint32) = the longest doc[i - L : i] (at most max_length
+        symbols) that some shard holds with a token behind it, context_count[i] (uint64) how often over all shards (length 0: the
+        tokens of the corpus), token_count[i] (uint64) how often followed by doc[i].  A context never spans two shards."""
+        buf, off, q = self._set._contexts(docs)
+        s = self._set.score_batch((buf, off), max_length=max_length or 0, per_shard=False, heads=False)["scores"]
+        cut = [(int(off[d]), int(off[d + 1])) for d in range(q)]
+        return [(s["length"][a:b].copy(), s["context_count"][a:b].copy(), s["token_count"][a:b].copy()) for a, b in cut]
+
+    def infgram_probs(self, docs, max_length=None):
+        """-> one float64 array per document: token_count / context_count of every position (computed on the host; 0 for a token
+        the context was never followed by, and for every token when the corpus is empty)"""
+        out = []
+        for _, cc, tc in self.infgram(docs, max_length=max_length):
+            p = np.zeros(cc.size, np.float64)
+            np.divide(tc, cc, out=p, where=cc > 0)
+            out.append(p)
+        return out
+
+    def infgram_summary(self, docs, max_length=None):
+        """-> dict of per-document arrays as TokenIndex.infgram_summary gives them: scored, seen (token_count > 0), certain
+        (token_count == context_count), longest, length_sum (uint64)."""
+        h = self._set.score_batch(docs, max_length=max_length or 0, scores=False, per_shard=False)["heads"]
+        return {k: h[k].copy() for k in ("scored", "seen", "certain", "longest", "length_sum")}
 
     def set_documents(self, doc_starts):
         """doc_starts: per shard, the first position inside the shard of every document (starts[0] == 0, non-decreasing, <= the
