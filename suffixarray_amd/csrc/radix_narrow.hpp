@@ -445,6 +445,7 @@ struct TextPassArgs {
     DeviceStatus* dstat;
     u32 incl_mask;
     u32* cursor;            // CLAIM form: records of a digit placed so far (zeroed by the host): cursor[digit * TOP_CURSOR_STRIDE]
+    int owned;              // CLAIM form: the owned-run body (text_top_owned_tile; the host has checked k0 <= TOP_OWNED_KMAX)
 };
 constexpr u32 TOP_CURSOR_STRIDE = 64;   // words: every digit's counter in a 256-byte line of its own (packed into 1 KB: 4.1-4.2 against
                                         // 3.5-3.8 ms, profiles/r04_claim_counters_layout.log)
@@ -632,15 +633,140 @@ __device__ __forceinline__ void text_top_tile(const TextPassArgs& a, const u32 t
     }
 }
 
+// ---- the CLAIM form's owned-run body ---------------------------------------------------------------------
+// The claim form owes its successors no order inside a digit, so it needs neither keys assembled byte by byte from staged
+// codes nor a stable rank.  Thread tid owns the 16 CONSECUTIVE positions tile_base + 16 tid + j: it loads the
+// TOP_OWNED_W text bytes that end with the last character of its 16th key straight from global memory, maps each byte
+// once through s_map and rolls the codes through one 64-bit window -- after code W - 16 + j the window's low b k0 bits are
+// the key of position j (older codes sit above them and are masked off or never looked at, which is why the window may start before
+// the first key and every register index is static while b and k0 stay run-time values).  A record's place inside the tile
+// comes from one returning LDS atomic on 256 << TOP_FINE_BITS bins, the top 8 + TOP_FINE_BITS key bits: fine enough that
+// the 64 lanes of an instruction rarely meet in a bin, and nested inside the digits, so a digit's run stays contiguous.
+constexpr int TOP_OWNED_W = 24;                    // 16 + 8 bytes per lane
+constexpr int TOP_OWNED_KMAX = TOP_OWNED_W - 15;   // 16 keys of k0 characters span 15 + k0 bytes
+constexpr int TOP_FINE_BITS = 3;
+constexpr u32 TOP_FINE_BINS = (u32)RADIX << TOP_FINE_BITS;
+inline bool text_owned_applies(int b, int k0) { return k0 >= 1 && k0 <= TOP_OWNED_KMAX && b * k0 >= 8 + TOP_FINE_BITS && b * k0 <= 40; }
+
+// FULL: the tile and the TOP_OWNED_W bytes behind it lie below n (no byte needs a check); otherwise tile_n <= TILE positions
+template <bool FULL, int BLOCK>
+__device__ __forceinline__ void text_top_owned_tile(const TextPassArgs& a, const u32 tile, const u32 chunk, const u32 tile_n, u32* s_keys,
+                                                    u32* s_fine, u32* s_gdelta, u32* s_wsum, u8* s_dig, const u8* s_map) {
+    constexpr int ITEMS = 16, W = TOP_OWNED_W, F = TOP_FINE_BITS;
+    constexpr u32 TILE = BLOCK * ITEMS;
+    static_assert(TEXT_ITEMS == ITEMS, "the tiles of the pass's geometry");
+    static_assert(TOP_FINE_BINS == 4u * BLOCK, "four fine bins per thread");
+    static_assert((TILE & (TILE - 1)) == 0 && TILE <= (1u << 13) && 8 + F + 13 <= 32, "(fine bin, rank) in one register");
+    static_assert(W % 4 == 0 && W > 16 && W <= 32, "a 16-byte load and a shorter one");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u64 tile_base = (u64)tile * TILE;
+    const u32 own = (u32)tid * ITEMS;
+
+    // claims per (chunk, digit) -- the histogram is kept per chunk anyway: a counter takes the atomics of an eighth of the tiles
+    const u32 cd = chunk * RADIX + (u32)(tid >> 1);
+    const u32 dbase = (tid & 1) ? 0u : a.digit_base[cd];   // the start of the chunk's share of the digit: needed with the claim
+
+    // 1. the W text bytes that end with the last character of the 16th key (a load starts below n or is skipped; the one
+    //    lane whose window starts before the text -- tile 0, thread 0, k0 < W - 15 -- takes its bytes one by one)
+    const long long start = (long long)(tile_base + own) + (a.k0 - (W - 15));
+    const long long n = (long long)a.n;
+    u32 x[W / 4];
+#pragma unroll
+    for (int i = 0; i < W / 4; ++i) x[i] = 0;
+    if (start >= 0) {
+        if (FULL || start < n) __builtin_memcpy(&x[0], a.text + start, 16);
+        if (FULL || start + 16 < n) __builtin_memcpy(&x[4], a.text + start + 16, W - 16);
+    } else {
+#pragma unroll
+        for (int i = 0; i < W; ++i) {
+            const long long q = start + i;
+            if (q >= 0 && q < n) x[i >> 2] |= (u32)a.text[q] << ((i & 3) * 8);
+        }
+    }
+    // bytes of the text among the W: the others take code 0 (byte 0 may be a symbol with a code of its own)
+    const u32 live = FULL ? (u32)W : (u32)((start >= n) ? 0 : ((n - start < W) ? (n - start) : W));
+
+    // 2. codes -> rolled window -> narrow key, fine bin, place inside the tile's fine bin (any order will do)
+    //    (branch-free: a position beyond the tile counts into the spare word s_fine[TOP_FINE_BINS], as in split_tile)
+    const u32 up = 32u - (u32)a.b;
+    const u32 fshift = (u32)(a.b * a.k0 - 8 - F);   // 0 .. 29
+    const u32 kmask = (a.b * a.k0 >= 32) ? 0xFFFFFFFFu : ((1u << (a.b * a.k0)) - 1u);   // the key's bits of the low word
+    u32 whi = 0, wlo = 0;
+    u32 key[ITEMS], pk[ITEMS];
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        const u32 byte = (x[i >> 2] >> ((i & 3) * 8)) & 255u;
+        const u32 code = (FULL || (u32)i < live) ? (u32)s_map[byte] : 0u;
+        whi = __builtin_amdgcn_alignbit(whi, wlo, up);   // (whi:wlo << b) | code, b = 1 .. 8
+        wlo = (wlo << a.b) | code;
+        if (i >= W - ITEMS) {
+            const int j = i - (W - ITEMS);
+            key[j] = wlo & kmask;
+            const u32 fine = __builtin_amdgcn_alignbit(whi, wlo, fshift) & (TOP_FINE_BINS - 1u);
+            const u32 slot = (FULL || own + (u32)j < tile_n) ? fine : TOP_FINE_BINS;
+            pk[j] = (fine << 13) | atomicAdd(&s_fine[slot], 1u);
+        }
+    }
+    sync_lds();
+
+    // 3. fine-bin counts, four per thread -> one claim per non-empty digit (thread pair) -> exclusive scan over the bins
+    const uint4 c = *reinterpret_cast<const uint4*>(s_fine + 4 * tid);
+    const u32 tot = c.x + c.y + c.z + c.w;
+    const u32 dcount = tot + __shfl_xor(tot, 1);   // the digit tid >> 1: the bins of threads 2 d and 2 d + 1
+    u32 claim = 0;
+    if (!(tid & 1) && dcount) claim = atomicAdd(&a.cursor[cd * TOP_CURSOR_STRIDE], dcount);   // requested now, needed for the stores
+    const u32 incl = wave_scan_incl(tot, ScanSum{});
+    if (lane == 63) s_wsum[wave] = incl;
+    __syncthreads();   // (every thread has read its four counters)
+    u32 excl = incl - tot;
+    for (int i = 0; i < wave; ++i) excl += s_wsum[i];
+    *reinterpret_cast<uint4*>(s_fine + 4 * tid) = make_uint4(excl, excl + c.x, excl + c.x + c.y, excl + c.x + c.y + c.z);
+    __syncthreads();
+
+    // 4. narrow keys and their top digits -> LDS at the tile-local sorted position (< TILE by the scan, and by the mask)
+    u32 pos[ITEMS];
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j) {
+        const u32 fine = pk[j] >> 13;
+        pos[j] = (s_fine[fine] + (pk[j] & 0x1FFFu)) & (TILE - 1u);
+        if (FULL || own + (u32)j < tile_n) { s_keys[pos[j]] = key[j]; s_dig[pos[j]] = (u8)(fine >> F); }
+    }
+    // 5. where the digit's run goes: its start + what the tile claimed - its tile-local start
+    if (!(tid & 1)) s_gdelta[tid >> 1] = dbase + claim - excl;
+    __syncthreads();
+
+    // 6. coalesced stores per digit run: keys, then the positions through the same LDS
+    u32 gidx[ITEMS];
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const u32 p = k * BLOCK + tid;
+        if (FULL || p < tile_n) {
+            gidx[k] = s_gdelta[s_dig[p]] + p;
+            a.keys_out32[gidx[k]] = s_keys[p];
+        }
+    }
+    __syncthreads();
+    u32* s_vals = s_keys;
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j)
+        if (FULL || own + (u32)j < tile_n) s_vals[pos[j]] = (u32)tile_base + own + (u32)j;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const u32 p = k * BLOCK + tid;
+        if (FULL || p < tile_n) a.vals_out[gidx[k]] = s_vals[p];
+    }
+}
+
 // 79 VGPRs and 50 KB of LDS: three workgroups (24 waves) per CU
 template <int BLOCK, bool EXT = false, bool CLAIM = false>
 __global__ __launch_bounds__(BLOCK, (TEXT_ITEMS > 16 || EXT) ? 4 : 6) void text_top_pass_kernel(TextPassArgs a) {
     constexpr int WAVES = BLOCK / WAVE;
     constexpr u32 TILE = BLOCK * TEXT_ITEMS;
     __shared__ __attribute__((aligned(16))) u32 s_keys[TILE];
-    __shared__ u32 s_whist[WAVES * RADIX];
+    __shared__ __attribute__((aligned(16))) u32 s_whist[WAVES * RADIX + 4];   // owned-run body: the fine bins + a spare word
     __shared__ u32 s_gdelta[RADIX];
-    __shared__ u32 s_wsum[RADIX / WAVE];
+    __shared__ u32 s_wsum[WAVES];
     __shared__ __attribute__((aligned(16))) u8 s_code[TILE + TEXT_HALO];   // codes, later the top digit per sorted slot
     __shared__ u16 s_ext[EXT ? TILE : 2];
     __shared__ u8 s_map[256];
@@ -663,12 +789,22 @@ __global__ __launch_bounds__(BLOCK, (TEXT_ITEMS > 16 || EXT) ? 4 : 6) void text_
         s_chunk = chunk;
     }
     if (tid < 256) s_map[tid] = (u8)a.map[tid];
-    for (int i = tid; i < WAVES * RADIX; i += BLOCK) s_whist[i] = 0;
+    for (int i = tid; i < WAVES * RADIX + 4; i += BLOCK) s_whist[i] = 0;
     __syncthreads();
     const u32 tile = s_tile;
     if (tile == 0xFFFFFFFFu) return;
     const u32 chunk = s_chunk;
     const u64 rest = a.n - (u64)tile * TILE;
+    if constexpr (CLAIM && !EXT && TEXT_ITEMS == 16) {
+        static_assert(TOP_FINE_BINS == (u32)(WAVES * RADIX), "the fine bins live in s_whist");
+        if (a.owned) {   // uniform
+            if (rest >= (u64)TILE + TOP_OWNED_W)
+                text_top_owned_tile<true, BLOCK>(a, tile, chunk, TILE, s_keys, s_whist, s_gdelta, s_wsum, s_code, s_map);
+            else
+                text_top_owned_tile<false, BLOCK>(a, tile, chunk, rest < (u64)TILE ? (u32)rest : TILE, s_keys, s_whist, s_gdelta, s_wsum, s_code, s_map);
+            return;
+        }
+    }
     if (rest >= (u64)TILE)
         text_top_tile<true, BLOCK, EXT, CLAIM>(a, tile, chunk, TILE, s_keys, s_whist, s_gdelta, s_wsum, s_code, s_map, s_ext);
     else
@@ -913,8 +1049,10 @@ struct NarrowWorkspace {
     u32* split_hist = nullptr;     // [RADIX][SPLIT_NB]
     u32* split_base = nullptr;     // [RADIX][SPLIT_NB]
     u32* split_cursor = nullptr;   // [RADIX][SPLIT_NB]: the split pass's claims
-    u32* top_cursor = nullptr;     // [RADIX][TOP_CURSOR_STRIDE]: the claims of the top-digit pass's CLAIM form
+    u32* top_cursor = nullptr;     // [NCHUNK][RADIX][TOP_CURSOR_STRIDE]: the claims of the top-digit pass's CLAIM form (the previous body: chunk 0's)
+    static size_t top_cursor_bytes() { return (size_t)NCHUNK * RADIX * TOP_CURSOR_STRIDE * sizeof(u32); }
     bool top_claims = true;        // SA_HIP_TOP_CLAIMS=0: the top-digit pass always in its stable form (published counts + look-back)
+    bool top_owned = true;         // SA_HIP_TOP_OWNED=0: the claim form with its previous body (keys from staged codes, ballot ranks; A/B, tests)
     u32* split_sub = nullptr;      // [(RADIX << SPLIT_BITS) + 1] sub-bucket starts | [16] largest group per level
     u32* host_word = nullptr;      // pinned, 16 words: the largest group per level comes here
     static size_t split_table_bytes() { return (size_t)RADIX * SPLIT_NB * sizeof(u32); }
@@ -955,11 +1093,12 @@ struct NarrowWorkspace {
         SA_HIP_CHECK(hipMalloc(&split_hist, split_table_bytes()));
         SA_HIP_CHECK(hipMalloc(&split_base, split_table_bytes()));
         SA_HIP_CHECK(hipMalloc(&split_cursor, split_table_bytes()));
-        SA_HIP_CHECK(hipMalloc(&top_cursor, (size_t)RADIX * TOP_CURSOR_STRIDE * sizeof(u32)));
+        SA_HIP_CHECK(hipMalloc(&top_cursor, top_cursor_bytes()));
         SA_HIP_CHECK(hipMalloc(&split_sub, (split_sub_words() + 16) * sizeof(u32)));
         SA_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host_word), 64, hipHostMallocDefault));
         if (const char* e = diag_env("SA_HIP_SPLIT")) split_enabled = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_TOP_CLAIMS")) top_claims = atoi(e) != 0;
+        if (const char* e = diag_env("SA_HIP_TOP_OWNED")) top_owned = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_LOCAL_BIG")) local_big = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_LOCAL_PERSIST")) local_persist = atoi(e) != 0;
         if (const char* e = diag_env("SA_HIP_LOCAL_GRID")) { const int v = atoi(e); local_grid_force = v > 0 ? (u32)v : 0u; }
@@ -1080,8 +1219,9 @@ inline int radix_sort_narrow(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_
         t.keys_out32 = reinterpret_cast<u32*>(keysB); t.ext_out16 = nullptr; t.vals_out = valsB; t.g = g; t.digit_base = ws.base();
         t.status = ws.status; t.ticket = ws.tickets(); t.epoch = ws.epoch; t.dstat = ws.dstat; t.incl_mask = SA_INCL_MASK;
         t.cursor = nw.top_cursor;
+        t.owned = (claim && nw.top_owned && TEXT_ITEMS == 16 && text_owned_applies(src->b, src->k0)) ? 1 : 0;
         int r;
-        if (claim) SA_HIP_CHECK(hipMemsetAsync(nw.top_cursor, 0, (size_t)RADIX * TOP_CURSOR_STRIDE * sizeof(u32), stream));
+        if (claim) SA_HIP_CHECK(hipMemsetAsync(nw.top_cursor, 0, NarrowWorkspace::top_cursor_bytes(), stream));
         if ((r = ws.timer.start(stream, 1))) return r;
         if (claim) hipLaunchKernelGGL((text_top_pass_kernel<512, false, true>), dim3(g.tiles), dim3(512), 0, stream, t);
         else hipLaunchKernelGGL((text_top_pass_kernel<512>), dim3(g.tiles), dim3(512), 0, stream, t);
