@@ -26,6 +26,17 @@
 // so there are up to 256 short chains instead of 8 long ones, and the digit bases are per bucket:
 // base[b][d] = bstart[b] + sum_{d' < d} hist[b][d'].  Since records never leave their bucket, the histogram of
 // the next pass is one LDS histogram per tile added to hist_next[b][.].
+//
+// Host driver (end of the file): radix_sort_narrow is a sequence of phases, each a function with its inputs in its signature:
+//   1. narrow_top_digit     the top-digit pass (from the text: launch_text_top(), all three forms of the kernel, also for
+//                           radix_narrow48.hpp); narrow keys in keysB (u32), values in valsB
+//   2. narrow_plan_look     three-pass plan considered: the largest group per level from the device -- the sort's one
+//                           synchronise -- and choose_split_level(), the host's rule, a pure function of those 16 words
+//   3. narrow_split_pass, narrow_local_pass    the plan taken: B -> A grouped by rb key bits, A -> B ordered in LDS
+//   4. narrow_declined, narrow_lsd_passes      the plan declined: the top-digit pass once more, stable, the plan for the LSD
+//                           tile; then the bucketed LSD passes (the whole sort when the plan is not considered)
+// Every pass goes through RadixWorkspace::next_epoch / timed_pass.  What the sort found -- result buffers, the level taken, the
+// largest group seen, whether the local pass did the flags work -- comes back in NarrowSortResult, not in the workspace.
 #pragma once
 #include "radix_sort.hpp"
 #include <vector>
@@ -1044,8 +1055,6 @@ struct NarrowWorkspace {
     CodeMap map_host;        // source of the asynchronous copy (must outlive the call)
     // the three-pass plan (radix_split.hpp)
     bool split_enabled = true;     // SA_HIP_SPLIT=0: always the LSD passes
-    bool split_used = false;       // of the last sort
-    u32 split_max_seen = 0;        // largest sub-bucket of the last sort that looked (0: the plan was not considered)
     u32* split_hist = nullptr;     // [RADIX][SPLIT_NB]
     u32* split_base = nullptr;     // [RADIX][SPLIT_NB]
     u32* split_cursor = nullptr;   // [RADIX][SPLIT_NB]: the split pass's claims
@@ -1059,29 +1068,25 @@ struct NarrowWorkspace {
     static size_t split_sub_words() { return ((size_t)RADIX << SPLIT_BITS) + 1; }
     u32* split_levels_dev() const { return split_sub + split_sub_words(); }   // [16]: largest group per level
     u32 split_cap = LOCAL_CAP;     // SA_HIP_SPLIT_CAP (tests: a smaller bound makes small texts take more levels)
-    int split_rb = 0;              // level of the last sort that took the plan
     int local_bin_bits = 12;       // SA_HIP_LOCAL_BINS=11: 2048 bins in the local pass
     bool split_flags = true;       // SA_HIP_SPLIT_FLAGS=0: the first flags pass stays a pass of its own
     bool local_big = false;        // SA_HIP_LOCAL_BIG=1: always the large form of the local pass (tests, A/B)
-    bool split_big = false;        // of the last sort: the local pass ran in its large form
     bool local_persist = true;     // SA_HIP_LOCAL_PERSIST=0: the local pass as one workgroup per sub-bucket (A/B)
     u32 local_grid_force = 0;      // SA_HIP_LOCAL_GRID=k: the persistent local pass on k workgroups (tests: one walks thousands of sub-buckets)
-    u32 local_grid[6] = {};        // per instantiation of local_persist_kernel: workgroups resident at once on the device (0: not asked yet)
+    u32 local_grid[6] = {};        // per row of local_kernels(): workgroups of local_persist_kernel resident at once on the device (0: not asked yet)
     // the persistent local pass's grid: as many workgroups as the device holds at once (occupancy x CUs), asked once per workspace
-    template <typename K>
-    int persist_grid(K kernel, int block, int slot, u32 nsub, u32* grid) {
+    int persist_grid(const void* kernel, int block, int slot, u32 nsub, u32* grid) {
         if (!local_grid[slot]) {
             int dev = 0, cus = 0, per_cu = 0;
             SA_HIP_CHECK(hipGetDevice(&dev));
             SA_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-            SA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), block, 0));
+            SA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0));
             local_grid[slot] = (u32)((per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1));
         }
         const u32 g = local_grid_force ? local_grid_force : local_grid[slot];
         *grid = g < nsub ? g : nsub;
         return 0;
     }
-    bool split_flags_done = false; // of the last sort: the local pass has written the directory and staged the active records
     int split_items = 28;          // SA_HIP_SPLIT_ITEMS=24 / 28 / 32: tiles of 12288 / 14336 / 16384 records in the split pass (32 spills 33 registers)
     static size_t hist_bytes() { return (size_t)NARROW_MAX_PASSES * RADIX * RADIX * sizeof(u32); }
     int init() {
@@ -1140,43 +1145,29 @@ struct TextSource {
 };
 inline bool text_pass_applies(int b, int k0) { return b <= 8 && k0 - 1 <= TEXT_HALO; }
 
-// Code map to the device + per-chunk histogram of the top digit of every position's key into ws.hist(0)
-// (radix_prepare() before): what a text-sourced narrow sort needs in place of key generation.
-inline int narrow_text_histogram(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, const u8* text, const CodeMap& map,
-                                 u32 n, int b) {
+// What a text-sourced pass needs in place of key generation (radix_prepare() before): the code map on the device and the
+// per-chunk histogram of one digit of every position's key in ws.hist(0).  tile: that of the pass the histogram's chunks
+// are for -- TEXT_TILE for text_top_pass_kernel (not a power of two: tile_shift unused), ws.tile() for pass 0 of the plain
+// sort.  low_k0 = 0: the TOP digit (narrow sorts); low_k0 = k0: the LOWEST digit of the k0-character key (plain sort).
+inline int text_histogram(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, const u8* text, const CodeMap& map,
+                          u32 n, int b, u32 tile, int low_k0) {
     nw.map_host = map;
     SA_HIP_CHECK(hipMemcpyAsync(nw.map_dev, nw.map_host.code, sizeof(CodeMap), hipMemcpyHostToDevice, stream));
-    const SortGeom g = make_geom(n, TEXT_TILE);   // the chunks of text_top_pass_kernel (its tile is not a power of two: tile_shift unused)
+    const SortGeom g = make_geom(n, tile);
     const u32 spans = div_up(n, 4096);
     const dim3 grid(spans < 2048u ? spans : 2048u), block(256);
-    switch ((8 + b - 1) / b) {
-        case 1: hipLaunchKernelGGL(top_hist_kernel<1>, grid, block, 0, stream, text, nw.map_dev, (u64)n, b, g, ws.hist(0)); break;
-        case 2: hipLaunchKernelGGL(top_hist_kernel<2>, grid, block, 0, stream, text, nw.map_dev, (u64)n, b, g, ws.hist(0)); break;
-        case 3: hipLaunchKernelGGL(top_hist_kernel<3>, grid, block, 0, stream, text, nw.map_dev, (u64)n, b, g, ws.hist(0)); break;
-        case 4: hipLaunchKernelGGL(top_hist_kernel<4>, grid, block, 0, stream, text, nw.map_dev, (u64)n, b, g, ws.hist(0)); break;
-        default: hipLaunchKernelGGL(top_hist_kernel<8>, grid, block, 0, stream, text, nw.map_dev, (u64)n, b, g, ws.hist(0)); break;
+    decltype(&top_hist_kernel<1>) kernel;
+    switch ((8 + b - 1) / b) {   // codes per digit
+        case 1: kernel = top_hist_kernel<1>; break;
+        case 2: kernel = top_hist_kernel<2>; break;
+        case 3: kernel = top_hist_kernel<3>; break;
+        case 4: kernel = top_hist_kernel<4>; break;
+        default: kernel = top_hist_kernel<8>; break;
     }
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, text, nw.map_dev, (u64)n, b, g, ws.hist(0), low_k0);
     return 0;
 }
 
-// What a text-sourced pass 0 of the plain sort needs in place of key generation: the code map on the device and the
-// per-chunk histogram of the LOWEST digit of every position's key in ws.hist(0) (radix_prepare() before).
-inline int wide_text_histogram(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, const u8* text, const CodeMap& map,
-                               u32 n, int b, int k0) {
-    nw.map_host = map;
-    SA_HIP_CHECK(hipMemcpyAsync(nw.map_dev, nw.map_host.code, sizeof(CodeMap), hipMemcpyHostToDevice, stream));
-    const SortGeom g = make_geom(n, ws.tile());
-    const u32 spans = div_up(n, 4096);
-    const dim3 grid(spans < 2048u ? spans : 2048u), block(256);
-    switch ((8 + b - 1) / b) {
-        case 1: hipLaunchKernelGGL(top_hist_kernel<1>, grid, block, 0, stream, text, nw.map_dev, (u64)n, b, g, ws.hist(0), k0); break;
-        case 2: hipLaunchKernelGGL(top_hist_kernel<2>, grid, block, 0, stream, text, nw.map_dev, (u64)n, b, g, ws.hist(0), k0); break;
-        case 3: hipLaunchKernelGGL(top_hist_kernel<3>, grid, block, 0, stream, text, nw.map_dev, (u64)n, b, g, ws.hist(0), k0); break;
-        case 4: hipLaunchKernelGGL(top_hist_kernel<4>, grid, block, 0, stream, text, nw.map_dev, (u64)n, b, g, ws.hist(0), k0); break;
-        default: hipLaunchKernelGGL(top_hist_kernel<8>, grid, block, 0, stream, text, nw.map_dev, (u64)n, b, g, ws.hist(0), k0); break;
-    }
-    return 0;
-}
 struct WideTextCtx {
     const u8* text;
     const u16* map;
@@ -1190,220 +1181,248 @@ inline void launch_text_low_pass(void* ctx, hipStream_t stream, const SortPassAr
     hipLaunchKernelGGL((text_low_pass_kernel<512>), dim3(grid), dim3(512), 0, stream, t);
 }
 
+// The top-digit pass from the text, timed and counted, in one of text_top_pass_kernel's three forms (the caller has taken
+// the pass's epoch and scanned ws.hist(0) into ws.base()).  Keys leave as their low bits in keys_out32, positions in vals_out.
+//   TOP_STABLE  published counts + look-back: what the LSD passes behind it need
+//   TOP_CLAIM   order-free claims on nw.top_cursor (zeroed here); its owned-run body where the key's shape allows
+//   TOP_EXT     stable, and the 16 key bits below keys_out32's leave in ext_out16 (10-byte records)
+enum TopForm { TOP_STABLE, TOP_CLAIM, TOP_EXT };
+inline int launch_text_top(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, const TextSource& src, u32 n, int begin_bit,
+                           TopForm form, u32* keys_out32, u16* ext_out16, u32* vals_out) {
+    const bool claim = form == TOP_CLAIM, ext = form == TOP_EXT;
+    const SortGeom g = make_geom(n, TEXT_TILE);
+    TextPassArgs t;
+    t.text = src.text; t.map = nw.map_dev; t.n = n; t.b = src.b; t.k0 = src.k0; t.begin_bit = begin_bit;
+    t.keys_out32 = keys_out32; t.ext_out16 = ext_out16; t.vals_out = vals_out; t.g = g; t.digit_base = ws.base();
+    t.status = ws.status; t.ticket = ws.tickets(); t.epoch = ws.epoch; t.dstat = ws.dstat; t.incl_mask = SA_INCL_MASK;
+    t.cursor = ext ? nullptr : nw.top_cursor;
+    t.owned = (claim && nw.top_owned && TEXT_ITEMS == 16 && text_owned_applies(src.b, src.k0)) ? 1 : 0;
+    if (claim) SA_HIP_CHECK(hipMemsetAsync(nw.top_cursor, 0, NarrowWorkspace::top_cursor_bytes(), stream));
+    return ws.timed_pass(stream, 1, n, (u64)n * (ext ? 11u : 9u), [&] {
+        if (claim) hipLaunchKernelGGL((text_top_pass_kernel<512, false, true>), dim3(g.tiles), dim3(512), 0, stream, t);
+        else if (!ext) hipLaunchKernelGGL((text_top_pass_kernel<512>), dim3(g.tiles), dim3(512), 0, stream, t);
+        else hipLaunchKernelGGL((text_top_pass_kernel<512, true>), dim3(g.tiles), dim3(512), 0, stream, t);
+    });
+}
+
 // Sort n records (key[i], i) by key bits [begin_bit, 64), stable.
 //   src == nullptr: keysA holds the u64 keys and the per-chunk histogram of their top digit has been accumulated
 //                   into ws.hist(0) by the producer (radix_prepare() before, keygen_kernel);
 //   src != nullptr: keysA holds nothing yet, the keys are the first src->k0 characters of every text position
-//                   (radix_prepare() + narrow_text_histogram() before).
+//                   (radix_prepare() + text_histogram() of the top digit before).
 // keysA / keysB and valsA / valsB are the ping-pong buffers of the plain sort (n * 8 and n * 4 bytes);
-// narrow keys use the first n * 4 bytes of a key buffer.  Result: *keys_res (u64, full keys), *vals_res.
-// keep_narrow: the last pass does not rebuild the u64 keys; *keys_res then points at u32[n] narrow keys, the full key of
+// narrow keys use the first n * 4 bytes of a key buffer.  Result: res->keys (u64, full keys), res->vals.
+// keep_narrow: the last pass does not rebuild the u64 keys; res->keys then points at u32[n] narrow keys, the full key of
 // slot j being (bucket(j) << 56) | (narrow[j] << begin_bit) with the bucket bounds in nw.plan->bstart (8 bytes per
 // record less written here, 4 less read by whoever consumes the keys).
-inline int radix_sort_narrow(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, u64* keysA, u32* valsA, u64* keysB,
-                             u32* valsB, u32 n, int begin_bit, u64** keys_res, u32** vals_res, const TextSource* src = nullptr,
-                             bool keep_narrow = false, int64_t* vals_res64 = nullptr, const LocalFlagsRequest* flags_req = nullptr) {
+// The driver, radix_sort_narrow, stands behind its phases (1 .. 4 below; the head of the file lists them).
+struct NarrowSortResult {
+    u64* keys = nullptr;
+    u32* vals = nullptr;
+    int rb = 0;               // level at which the three-pass plan was taken; 0: the LSD passes ran
+    u32 max_group = 0;        // largest sub-bucket where the plan looked (0: the plan was not considered)
+    bool flags_done = false;  // the local pass has written the directory and staged the active records
+};
+
+// 1. top digit: values generated, keys leave as their low bits -- from the text, or from the u64 key array by the
+// ordinary one-sweep pass
+inline int narrow_top_digit(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, const u64* keys_in, u32* keys_out32, u32* vals_out,
+                            u32 n, int begin_bit, const TextSource* src, bool claim) {
+    int rc;
+    if ((rc = ws.next_epoch(stream))) return rc;
+    hipLaunchKernelGGL(radix_scan_hist_kernel, dim3(1), dim3(256), 0, stream, ws.hist(0), ws.base());
+    if (src) return launch_text_top(ws, nw, stream, *src, n, begin_bit, claim ? TOP_CLAIM : TOP_STABLE, keys_out32, nullptr, vals_out);
+    SortPassArgs a;
+    a.keys_in = keys_in; a.vals_in = nullptr; a.keys_out = nullptr; a.vals_out = vals_out;
+    a.g = make_geom(n, ws.tile()); a.shift = 56; a.mask = 255u; a.next_shift = -1; a.next_mask = 0; a.digit_base = ws.base();
+    a.next_hist = nullptr; a.status = ws.status; a.ticket = ws.tickets(); a.epoch = ws.epoch; a.dstat = ws.dstat;
+    a.home_mode = 0; a.incl_mask = SA_INCL_MASK;
+    a.keys_out32 = keys_out32; a.narrow_shift = begin_bit;
+    return ws.timed_pass(stream, 1, n, (u64)n * 16u, [&] {
+        hipLaunchKernelGGL((radix_onesweep_kernel<512, 0, true>), dim3(a.g.tiles), dim3(512), 0, stream, a);
+    });
+}
+
+// SA_HIP_SPLIT_ITEMS picks the tile of the split pass, and with it the instantiation of its two kernels
+struct SplitKernels {
+    using Hist = decltype(&split_hist_kernel<512, 24>);
+    using Split = decltype(&seg_split_kernel<512, 24>);
+    Hist hist;
+    Split split;
+};
+inline SplitKernels split_kernels(int split_items) {
+    const int i = (split_items == 32) ? 0 : (split_items == 28) ? 1 : 2;
+    static const SplitKernels::Hist hist[3] = {split_hist_kernel<512, 32>, split_hist_kernel<512, 28>, split_hist_kernel<512, 24>};
+    static const SplitKernels::Split split[3] = {seg_split_kernel<512, 32>, seg_split_kernel<512, 28>, seg_split_kernel<512, 24>};
+    return {hist[i], split[i]};
+}
+
+// The host's rule on the largest group per level (host_word[k], k = 0 .. hb: the records of a bucket grouped by their next k
+// key bits): the SMALLEST level whose groups all fit the local pass; its large form (sub-buckets of up to LOCAL_CAP_BIG
+// records: one workgroup per CU) when none fits the small one; rb < 0: declined.
+struct SplitLevel {
+    int rb;
+    bool big;
+};
+inline SplitLevel choose_split_level(const u32* host_word, int hb, int lo_bits, u32 split_cap, bool local_big) {
+    int rb = -1;
+    bool big = local_big;
+    if (!big)
+        for (int k = 1; k <= hb; ++k)
+            if (host_word[k] <= split_cap) { rb = k; break; }
+    if (rb < 0 && split_cap == LOCAL_CAP) {
+        for (int k = 1; k <= hb; ++k)
+            if (host_word[k] <= LOCAL_CAP_BIG && lo_bits - k >= 12) { rb = k; big = true; break; }   // (its 4096 bins: 12 key bits below the sub-bucket's)
+        if (rb < 0) big = false;
+    }
+    return {rb, big};
+}
+
+// 2. plan look: histogram of the next hb key bits per bucket, the largest group per level to the host (the device's own
+// count decides: the sort's one synchronise), the level chosen from it
+inline int narrow_plan_look(NarrowWorkspace& nw, hipStream_t stream, const u32* keys32, int lo_bits, int hb, u32 split_flat_max,
+                            SplitLevel* level) {
+    SA_HIP_CHECK(hipMemsetAsync(nw.split_hist, 0, NarrowWorkspace::split_table_bytes(), stream));
+    SA_HIP_CHECK(hipMemsetAsync(nw.split_levels_dev(), 0, 16 * sizeof(u32), stream));
+    const u32 tpb = 4;
+    hipLaunchKernelGGL(split_kernels(nw.split_items).hist, dim3(div_up(split_flat_max, tpb)), dim3(512), 0, stream, keys32, nw.plan,
+                       lo_bits - hb, (1u << hb) - 1u, nw.split_hist, tpb);
+    hipLaunchKernelGGL(split_levels_kernel, dim3(RADIX), dim3(SPLIT_NB), 0, stream, (const u32*)nw.split_hist, hb, nw.split_levels_dev());
+    SA_HIP_CHECK(hipMemcpyAsync(nw.host_word, nw.split_levels_dev(), 16 * sizeof(u32), hipMemcpyDeviceToHost, stream));
+    SA_HIP_CHECK(hipStreamSynchronize(stream));
+    *level = choose_split_level(nw.host_word, hb, lo_bits, nw.split_cap, nw.local_big);
+    return 0;
+}
+
+// 3a. split pass: the records of a bucket grouped by their next rb key bits, in any order (keys_in -> keys_out)
+inline int narrow_split_pass(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, const u32* keys_in, const u32* vals_in,
+                             u32* keys_out, u32* vals_out, u32 n, int lo_bits, int hb, int rb, u32 split_flat_max) {
+    int rc;
+    hipLaunchKernelGGL(split_scan_kernel, dim3(RADIX), dim3(SPLIT_NB), 0, stream, (const u32*)nw.split_hist, nw.plan, hb, rb,
+                       nw.split_base, nw.split_sub);
+    SA_HIP_CHECK(hipMemsetAsync(nw.split_cursor, 0, NarrowWorkspace::split_table_bytes(), stream));
+    if ((rc = ws.next_epoch(stream))) return rc;   // (the split pass reads no epoch: taken so that the passes after it number theirs as they always have)
+    SplitPassArgs a;
+    a.keys_in = keys_in; a.vals_in = vals_in;
+    a.keys_out = keys_out; a.vals_out = vals_out;
+    a.plan = nw.plan; a.shift = lo_bits - rb; a.mask = (1u << rb) - 1u; a.digit_base = nw.split_base;
+    a.ticket = nw.tickets; a.cursor = nw.split_cursor;
+    return ws.timed_pass(stream, 2, n, (u64)n * 16u, [&] {
+        hipLaunchKernelGGL(split_kernels(nw.split_items).split, dim3(split_flat_max), dim3(512), 0, stream, a);
+    });
+}
+
+// The local pass's kernels, one row per {large form, flags work, bins}; a row's index is also its slot in nw.local_grid[]
+struct LocalKernels {
+    using Persist = decltype(&local_persist_kernel<12, true>);
+    using Finish = decltype(&local_finish_kernel<12, true>);
+    Persist persist;   // as many workgroups as are resident
+    Finish finish;     // one workgroup per sub-bucket (SA_HIP_LOCAL_PERSIST=0)
+    int block, row;
+};
+inline LocalKernels local_kernels(bool big, bool flags, int bb) {
+    const int row = big ? (flags ? 0 : 1) : 2 + (flags ? 0 : 2) + (bb == 12 ? 0 : 1);
+    static const LocalKernels::Persist persist[6] = {
+        local_persist_kernel<12, true, LOCAL_BLOCK_BIG>, local_persist_kernel<12, false, LOCAL_BLOCK_BIG>,
+        local_persist_kernel<12, true>, local_persist_kernel<11, true>, local_persist_kernel<12, false>, local_persist_kernel<11, false>};
+    static const LocalKernels::Finish finish[6] = {
+        local_finish_kernel<12, true, LOCAL_BLOCK_BIG>, local_finish_kernel<12, false, LOCAL_BLOCK_BIG>,
+        local_finish_kernel<12, true>, local_finish_kernel<11, true>, local_finish_kernel<12, false>, local_finish_kernel<11, false>};
+    return {persist[row], finish[row], big ? LOCAL_BLOCK_BIG : LOCAL_BLOCK, row};
+}
+
+// 3b. local pass: every sub-bucket ordered completely in LDS (keys_in -> keys_out; vals_out64: the int64 array as well), with
+// the build's first flags pass inside it when the caller asks for it and provides the buffers (*flags_done)
+inline int narrow_local_pass(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, const u32* keys_in, const u32* vals_in,
+                             u32* keys_out, u32* vals_out, int64_t* vals_out64, u32 n, int begin_bit, int rb, bool big,
+                             const LocalFlagsRequest* flags_req, bool* flags_done) {
+    int rc;
+    const int lo_bits = 56 - begin_bit;
+    const int rest_bits = lo_bits - rb;   // >= LOCAL_BIN_BITS
+    LocalArgs l;
+    l.keys_in = keys_in; l.vals_in = vals_in;
+    l.keys_out = keys_out; l.vals_out = vals_out; l.vals_out64 = vals_out64;
+    l.sub = nw.split_sub;
+    const int bb = (big || (rest_bits >= 12 && nw.local_bin_bits == 12)) ? 12 : 11;
+    l.bin_shift = rest_bits - bb;
+    l.dstat = ws.dstat;
+    l.dir = DirArgs{}; l.counts = nullptr; l.lite = LiteArgs{}; l.lo_shift = begin_bit; l.rb = rb; l.n = n;
+    const u32 nsub = (u32)RADIX << rb;
+    bool with_flags = false;
+    if (nw.split_flags && flags_req && flags_req->prepare) {
+        const int fr = flags_req->prepare(flags_req->ctx, nsub, &l);
+        if (fr < 0) return fr;
+        // (the slice of the directory that belongs to a sub-bucket is read off the local pass's bin starts: the bins must be
+        //  at least as fine as the directory, and the directory's bits must lie inside the narrow key)
+        with_flags = (fr == 0) && l.dir.dir && l.dir.dbits >= 8 + rb && l.dir.dbits - 8 - rb <= bb && l.dir.dbits - 8 <= lo_bits;
+    }
+    const LocalKernels k = local_kernels(big, with_flags, bb);
+    u32 pgrid = 0;
+    if (nw.local_persist && (rc = nw.persist_grid(reinterpret_cast<const void*>(k.persist), k.block, k.row, nsub, &pgrid))) return rc;
+    rc = ws.timed_pass(stream, 3, n, (u64)n * 16u + (vals_out64 ? (u64)n * 8u : 0u), [&] {
+        // persistent: runs of sub-buckets handed out per XCD (their tickets: the second row of nw.tickets, zeroed with the first
+        // at the start of the sort; the LSD passes that would use it do not run when this plan is taken)
+        if (nw.local_persist) hipLaunchKernelGGL(k.persist, dim3(pgrid), dim3(k.block), 0, stream, l, (const u32*)nw.split_sub, nsub, nw.tickets + NCHUNK, LOCAL_RUN);
+        else hipLaunchKernelGGL(k.finish, dim3(nsub), dim3(k.block), 0, stream, l);
+    });
+    if (rc) return rc;
+    *flags_done = with_flags;
+    SA_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// SA_HIP_SPLIT_DEBUG: both passes of the plan checked on the host (keys_split: what the split pass left; keys_out / vals_out:
+// what the local pass left)
+inline int split_debug_check(NarrowWorkspace& nw, hipStream_t stream, const u32* keys_split, const u32* keys_out, const u32* vals_out,
+                             u32 n, int lo_bits, int hb, int rb) {
+    const int dshift = lo_bits - rb;
+    const u32 dmask = (1u << rb) - 1u;
+    const u32 nsub = (u32)RADIX << rb;
+    std::vector<u32> sub(nsub + 1), k1(n), k2(n), v2(n), bst(RADIX + 1);
+    SA_HIP_CHECK(hipStreamSynchronize(stream));
+    SA_HIP_CHECK(hipMemcpy(sub.data(), nw.split_sub, (size_t)(nsub + 1) * 4, hipMemcpyDeviceToHost));
+    SA_HIP_CHECK(hipMemcpy(k1.data(), keys_split, (size_t)n * 4, hipMemcpyDeviceToHost));
+    SA_HIP_CHECK(hipMemcpy(k2.data(), keys_out, (size_t)n * 4, hipMemcpyDeviceToHost));
+    SA_HIP_CHECK(hipMemcpy(v2.data(), vals_out, (size_t)n * 4, hipMemcpyDeviceToHost));
+    SA_HIP_CHECK(hipMemcpy(bst.data(), nw.plan->bstart, (size_t)(RADIX + 1) * 4, hipMemcpyDeviceToHost));
+    u64 bad_sub = 0, bad_split = 0, bad_sorted = 0, bad_mono = 0;
+    u32 first_split = ~0u, first_sorted = ~0u;
+    for (u32 i = 0; i < nsub; ++i) {
+        if (sub[i] > sub[i + 1] || sub[i + 1] > n) { ++bad_mono; continue; }
+        if ((i & (((u32)1 << rb) - 1)) == 0 && sub[i] != bst[i >> rb]) ++bad_sub;
+        for (u32 j = sub[i]; j < sub[i + 1]; ++j) {
+            if (((k1[j] >> dshift) & dmask) != (i & dmask)) { ++bad_split; if (first_split == ~0u) first_split = j; }
+            if (j > sub[i] && (k2[j - 1] > k2[j] || (k2[j - 1] == k2[j] && v2[j - 1] >= v2[j]))) { ++bad_sorted; if (first_sorted == ~0u) first_sorted = j; }
+        }
+    }
+    fprintf(stderr, "[sa_hip] split debug: n=%u rb=%d hb=%d nsub=%u sub[0]=%u sub[last]=%u | table: %llu not monotone, %llu off the bucket starts | split pass: %llu records in the wrong group (first %u) | local pass: %llu out of order (first %u)\n",
+            n, rb, hb, nsub, sub[0], sub[nsub], (unsigned long long)bad_mono, (unsigned long long)bad_sub, (unsigned long long)bad_split, first_split,
+            (unsigned long long)bad_sorted, first_sorted);
+    return 0;
+}
+
+// 4a. declined (skewed text): the LSD passes keep ties in the order they find them, so a top-digit pass that ran in its claim
+// form runs once more, stable; and the plan, made for the split pass's tile, is made again for the tile of the LSD passes
+inline int narrow_declined(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, u32* keys_out32, u32* vals_out, u32 n,
+                           int begin_bit, const TextSource* src, bool top_claimed, u32 split_tile_n, u32 seg_tile_n) {
+    int rc;
+    if (top_claimed) {
+        SA_HIP_CHECK(hipMemsetAsync(ws.tickets(), 0, NCHUNK * sizeof(u32), stream));
+        if ((rc = ws.next_epoch(stream))) return rc;
+        if ((rc = launch_text_top(ws, nw, stream, *src, n, begin_bit, TOP_STABLE, keys_out32, nullptr, vals_out))) return rc;
+    }
+    if (split_tile_n != seg_tile_n)
+        hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(256), 0, stream, ws.hist(0), seg_tile_n, nw.plan);
+    return 0;
+}
+
+// 4b. the bucketed LSD passes over the narrow key, B -> A -> B ...; the last one rebuilds the u64 keys unless keep_narrow
+inline int narrow_lsd_passes(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, u64* keysA, u32* valsA, u64* keysB, u32* valsB,
+                             u32 n, int begin_bit, bool keep_narrow, int64_t* vals_res64, NarrowSortResult* res) {
     int rc;
     const int lo_bits = 56 - begin_bit;                       // 1 .. 32
     const int np = (lo_bits + RADIX_BITS - 1) / RADIX_BITS;   // narrow passes, 1 .. 4
-    const SortGeom g = make_geom(n, src ? TEXT_TILE : ws.tile());
-    SA_HIP_CHECK(hipMemsetAsync(nw.tickets, 0, (size_t)NARROW_MAX_PASSES * NCHUNK * sizeof(u32), stream));
-
-    // the three-pass plan (radix_split.hpp) is considered for this sort; its passes do not need the top-digit pass to be stable,
-    // so that pass runs in its CLAIM form first -- and once more, stable, should the plan be declined (skewed text)
-    const bool try_split = nw.split_enabled && keep_narrow && ws.block == 512 && lo_bits - LOCAL_BIN_BITS >= 1;
-    const bool optimistic = try_split && src && nw.top_claims;
-    auto launch_text_top = [&](bool claim) -> int {
-        TextPassArgs t;
-        t.text = src->text; t.map = nw.map_dev; t.n = n; t.b = src->b; t.k0 = src->k0; t.begin_bit = begin_bit;
-        t.keys_out32 = reinterpret_cast<u32*>(keysB); t.ext_out16 = nullptr; t.vals_out = valsB; t.g = g; t.digit_base = ws.base();
-        t.status = ws.status; t.ticket = ws.tickets(); t.epoch = ws.epoch; t.dstat = ws.dstat; t.incl_mask = SA_INCL_MASK;
-        t.cursor = nw.top_cursor;
-        t.owned = (claim && nw.top_owned && TEXT_ITEMS == 16 && text_owned_applies(src->b, src->k0)) ? 1 : 0;
-        int r;
-        if (claim) SA_HIP_CHECK(hipMemsetAsync(nw.top_cursor, 0, NarrowWorkspace::top_cursor_bytes(), stream));
-        if ((r = ws.timer.start(stream, 1))) return r;
-        if (claim) hipLaunchKernelGGL((text_top_pass_kernel<512, false, true>), dim3(g.tiles), dim3(512), 0, stream, t);
-        else hipLaunchKernelGGL((text_top_pass_kernel<512>), dim3(g.tiles), dim3(512), 0, stream, t);
-        if ((r = ws.timer.stop(stream, (u64)n * 9u))) return r;
-        ws.pass_records += n; ws.pass_bytes += (u64)n * 9u; ws.passes += 1;
-        return 0;
-    };
-    // top digit: values generated, keys leave as their low bits -- from the text, or from the u64 key array by the
-    // ordinary one-sweep pass
-    {
-        if (++ws.epoch >= (1u << 30)) {
-            SA_HIP_CHECK(hipMemsetAsync(ws.status, 0, (size_t)ws.max_tiles * RADIX * sizeof(u64), stream));
-            ws.epoch = 1;
-        }
-        hipLaunchKernelGGL(radix_scan_hist_kernel, dim3(1), dim3(256), 0, stream, ws.hist(0), ws.base());
-        if (src) {
-            if ((rc = launch_text_top(optimistic))) return rc;
-        } else {
-            SortPassArgs a;
-            a.keys_in = keysA; a.vals_in = nullptr; a.keys_out = nullptr; a.vals_out = valsB;
-            a.g = g; a.shift = 56; a.mask = 255u; a.next_shift = -1; a.next_mask = 0; a.digit_base = ws.base();
-            a.next_hist = nullptr; a.status = ws.status; a.ticket = ws.tickets(); a.epoch = ws.epoch; a.dstat = ws.dstat;
-            a.home_mode = 0; a.incl_mask = SA_INCL_MASK;
-            a.keys_out32 = reinterpret_cast<u32*>(keysB); a.narrow_shift = begin_bit;
-            if ((rc = ws.timer.start(stream, 1))) return rc;
-            hipLaunchKernelGGL((radix_onesweep_kernel<512, 0, true>), dim3(g.tiles), dim3(512), 0, stream, a);
-            if ((rc = ws.timer.stop(stream, (u64)n * 16u))) return rc;
-            ws.pass_records += n; ws.pass_bytes += (u64)n * 16u; ws.passes += 1;
-        }
-    }
-    const u32 seg_tile_n = 512u * SEG_ITEMS;
-    const u32 flat_max = n / seg_tile_n + 1 + RADIX;   // >= sum over buckets of ceil(size / tile)
-    const u32 split_tile_n = 512u * (u32)nw.split_items;   // the split pass has its own tile size: the plan is made for it first
-    const u32 split_flat_max = n / split_tile_n + 1 + RADIX;
-    hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(256), 0, stream, ws.hist(0), try_split ? split_tile_n : seg_tile_n, nw.plan);
-    // narrow keys now in keysB (u32), values in valsB.
-    // Three-pass plan (radix_split.hpp): the records of a bucket are grouped by their next rb key bits, then every group is
-    // ordered completely in LDS -- when the largest group fits (near-random text; the device's own count decides)
-    nw.split_used = false;
-    nw.split_flags_done = false;
-    nw.split_max_seen = 0;
-    if (try_split) {
-        const int hb = (lo_bits - LOCAL_BIN_BITS < SPLIT_BITS) ? lo_bits - LOCAL_BIN_BITS : SPLIT_BITS;   // key bits the histogram looks at
-        SA_HIP_CHECK(hipMemsetAsync(nw.split_hist, 0, NarrowWorkspace::split_table_bytes(), stream));
-        SA_HIP_CHECK(hipMemsetAsync(nw.split_levels_dev(), 0, 16 * sizeof(u32), stream));
-        const u32 tpb = 4;
-        if (nw.split_items == 32)
-            hipLaunchKernelGGL((split_hist_kernel<512, 32>), dim3(div_up(split_flat_max, tpb)), dim3(512), 0, stream,
-                               reinterpret_cast<const u32*>(keysB), nw.plan, lo_bits - hb, (1u << hb) - 1u, nw.split_hist, tpb);
-        else if (nw.split_items == 28)
-            hipLaunchKernelGGL((split_hist_kernel<512, 28>), dim3(div_up(split_flat_max, tpb)), dim3(512), 0, stream,
-                               reinterpret_cast<const u32*>(keysB), nw.plan, lo_bits - hb, (1u << hb) - 1u, nw.split_hist, tpb);
-        else
-            hipLaunchKernelGGL((split_hist_kernel<512, 24>), dim3(div_up(split_flat_max, tpb)), dim3(512), 0, stream,
-                               reinterpret_cast<const u32*>(keysB), nw.plan, lo_bits - hb, (1u << hb) - 1u, nw.split_hist, tpb);
-        hipLaunchKernelGGL(split_levels_kernel, dim3(RADIX), dim3(SPLIT_NB), 0, stream, (const u32*)nw.split_hist, hb, nw.split_levels_dev());
-        SA_HIP_CHECK(hipMemcpyAsync(nw.host_word, nw.split_levels_dev(), 16 * sizeof(u32), hipMemcpyDeviceToHost, stream));
-        SA_HIP_CHECK(hipStreamSynchronize(stream));
-        int rb = -1;
-        bool big = nw.local_big;   // sub-buckets of up to LOCAL_CAP_BIG records: one workgroup per CU in the local pass
-        if (!big)
-            for (int k = 1; k <= hb; ++k)
-                if (nw.host_word[k] <= nw.split_cap) { rb = k; break; }
-        if (rb < 0 && nw.split_cap == LOCAL_CAP) {
-            for (int k = 1; k <= hb; ++k)
-                if (nw.host_word[k] <= LOCAL_CAP_BIG && lo_bits - k >= 12) { rb = k; big = true; break; }   // (its 4096 bins: 12 key bits below the sub-bucket's)
-            if (rb < 0) big = false;
-        }
-        nw.split_max_seen = nw.host_word[rb > 0 ? rb : hb];
-        if (rb > 0) {
-            const int rest_bits = lo_bits - rb;   // >= LOCAL_BIN_BITS
-            const int dshift = lo_bits - rb;
-            const u32 dmask = (1u << rb) - 1u;
-            hipLaunchKernelGGL(split_scan_kernel, dim3(RADIX), dim3(SPLIT_NB), 0, stream, (const u32*)nw.split_hist, nw.plan, hb, rb,
-                               nw.split_base, nw.split_sub);
-            SA_HIP_CHECK(hipMemsetAsync(nw.split_cursor, 0, NarrowWorkspace::split_table_bytes(), stream));
-            if (++ws.epoch >= (1u << 30)) {   // (the split pass reads no epoch: taken so that the passes after it number theirs as they always have)
-                SA_HIP_CHECK(hipMemsetAsync(ws.status, 0, (size_t)ws.max_tiles * RADIX * sizeof(u64), stream));
-                ws.epoch = 1;
-            }
-            SplitPassArgs a;
-            a.keys_in = reinterpret_cast<const u32*>(keysB); a.vals_in = valsB;
-            a.keys_out = reinterpret_cast<u32*>(keysA); a.vals_out = valsA;
-            a.plan = nw.plan; a.shift = dshift; a.mask = dmask; a.digit_base = nw.split_base;
-            a.ticket = nw.tickets; a.cursor = nw.split_cursor;
-            if ((rc = ws.timer.start(stream, 2))) return rc;
-            if (nw.split_items == 32) hipLaunchKernelGGL((seg_split_kernel<512, 32>), dim3(split_flat_max), dim3(512), 0, stream, a);
-            else if (nw.split_items == 28) hipLaunchKernelGGL((seg_split_kernel<512, 28>), dim3(split_flat_max), dim3(512), 0, stream, a);
-            else hipLaunchKernelGGL((seg_split_kernel<512, 24>), dim3(split_flat_max), dim3(512), 0, stream, a);
-            if ((rc = ws.timer.stop(stream, (u64)n * 16u))) return rc;
-            ws.pass_records += n; ws.pass_bytes += (u64)n * 16u; ws.passes += 1;
-            LocalArgs l;
-            l.keys_in = reinterpret_cast<const u32*>(keysA); l.vals_in = valsA;
-            l.keys_out = reinterpret_cast<u32*>(keysB); l.vals_out = valsB; l.vals_out64 = vals_res64;
-            l.sub = nw.split_sub;
-            const int bb = (big || (rest_bits >= 12 && nw.local_bin_bits == 12)) ? 12 : 11;
-            l.bin_shift = rest_bits - bb;
-            l.dstat = ws.dstat;
-            const u64 local_bytes = (u64)n * 16u + (vals_res64 ? (u64)n * 8u : 0u);
-            // the build's first flags pass inside the local pass, when the caller asks for it and provides the buffers
-            nw.split_flags_done = false;
-            l.dir = DirArgs{}; l.counts = nullptr; l.lite = LiteArgs{}; l.lo_shift = begin_bit; l.rb = rb; l.n = n;
-            bool with_flags = false;
-            if (nw.split_flags && flags_req && flags_req->prepare) {
-                const int fr = flags_req->prepare(flags_req->ctx, (u32)RADIX << rb, &l);
-                if (fr < 0) return fr;
-                // (the slice of the directory that belongs to a sub-bucket is read off the local pass's bin starts: the bins must be
-                //  at least as fine as the directory, and the directory's bits must lie inside the narrow key)
-                with_flags = (fr == 0) && l.dir.dir && l.dir.dbits >= 8 + rb && l.dir.dbits - 8 - rb <= bb && l.dir.dbits - 8 <= lo_bits;
-            }
-            if ((rc = ws.timer.start(stream, 3))) return rc;
-            const u32 nsub = (u32)RADIX << rb;
-            const dim3 lgrid(nsub), lblock(big ? LOCAL_BLOCK_BIG : LOCAL_BLOCK);
-            if (nw.local_persist) {   // as many workgroups as are resident, walking runs of sub-buckets handed out per XCD
-                // (their tickets: the second row of nw.tickets, zeroed with the first at the start of the sort; the LSD passes that
-                //  would use it do not run when this plan is taken)
-                const int slot = big ? (with_flags ? 0 : 1) : 2 + (with_flags ? 0 : 1) + (bb == 12 ? 0 : 2);   // (local_grid[])
-                u32 pg = 0;
-                auto go = [&](auto kernel) -> int {
-                    if ((rc = nw.persist_grid(kernel, (int)lblock.x, slot, nsub, &pg))) return rc;
-                    hipLaunchKernelGGL(kernel, dim3(pg), lblock, 0, stream, l, (const u32*)nw.split_sub, nsub, nw.tickets + NCHUNK, LOCAL_RUN);
-                    return 0;
-                };
-                if (big) rc = with_flags ? go(local_persist_kernel<12, true, LOCAL_BLOCK_BIG>) : go(local_persist_kernel<12, false, LOCAL_BLOCK_BIG>);
-                else if (with_flags) rc = (bb == 12) ? go(local_persist_kernel<12, true>) : go(local_persist_kernel<11, true>);
-                else rc = (bb == 12) ? go(local_persist_kernel<12, false>) : go(local_persist_kernel<11, false>);
-                if (rc) return rc;
-            } else if (big) {
-                if (with_flags) hipLaunchKernelGGL((local_finish_kernel<12, true, LOCAL_BLOCK_BIG>), lgrid, lblock, 0, stream, l);
-                else hipLaunchKernelGGL((local_finish_kernel<12, false, LOCAL_BLOCK_BIG>), lgrid, lblock, 0, stream, l);
-            } else if (with_flags) {
-                if (bb == 12) hipLaunchKernelGGL((local_finish_kernel<12, true>), lgrid, lblock, 0, stream, l);
-                else hipLaunchKernelGGL((local_finish_kernel<11, true>), lgrid, lblock, 0, stream, l);
-            } else {
-                if (bb == 12) hipLaunchKernelGGL((local_finish_kernel<12, false>), lgrid, lblock, 0, stream, l);
-                else hipLaunchKernelGGL((local_finish_kernel<11, false>), lgrid, lblock, 0, stream, l);
-            }
-            nw.split_flags_done = with_flags;
-            nw.split_big = big;
-            if ((rc = ws.timer.stop(stream, local_bytes))) return rc;
-            ws.pass_records += n; ws.pass_bytes += local_bytes; ws.passes += 1;
-            SA_HIP_CHECK(hipGetLastError());
-            if (diag_env("SA_HIP_SPLIT_DEBUG")) {   // diagnostic: both passes checked on the host
-                const u32 nsub = (u32)RADIX << rb;
-                std::vector<u32> sub(nsub + 1), k1(n), k2(n), v2(n), bst(RADIX + 1);
-                SA_HIP_CHECK(hipStreamSynchronize(stream));
-                SA_HIP_CHECK(hipMemcpy(sub.data(), nw.split_sub, (size_t)(nsub + 1) * 4, hipMemcpyDeviceToHost));
-                SA_HIP_CHECK(hipMemcpy(k1.data(), keysA, (size_t)n * 4, hipMemcpyDeviceToHost));
-                SA_HIP_CHECK(hipMemcpy(k2.data(), keysB, (size_t)n * 4, hipMemcpyDeviceToHost));
-                SA_HIP_CHECK(hipMemcpy(v2.data(), valsB, (size_t)n * 4, hipMemcpyDeviceToHost));
-                SA_HIP_CHECK(hipMemcpy(bst.data(), nw.plan->bstart, (size_t)(RADIX + 1) * 4, hipMemcpyDeviceToHost));
-                u64 bad_sub = 0, bad_split = 0, bad_sorted = 0, bad_mono = 0;
-                u32 first_split = ~0u, first_sorted = ~0u;
-                for (u32 i = 0; i < nsub; ++i) {
-                    if (sub[i] > sub[i + 1] || sub[i + 1] > n) { ++bad_mono; continue; }
-                    if ((i & (((u32)1 << rb) - 1)) == 0 && sub[i] != bst[i >> rb]) ++bad_sub;
-                    for (u32 j = sub[i]; j < sub[i + 1]; ++j) {
-                        if (((k1[j] >> dshift) & dmask) != (i & dmask)) { ++bad_split; if (first_split == ~0u) first_split = j; }
-                        if (j > sub[i] && (k2[j - 1] > k2[j] || (k2[j - 1] == k2[j] && v2[j - 1] >= v2[j]))) { ++bad_sorted; if (first_sorted == ~0u) first_sorted = j; }
-                    }
-                }
-                fprintf(stderr, "[sa_hip] split debug: n=%u rb=%d hb=%d nsub=%u sub[0]=%u sub[last]=%u | table: %llu not monotone, %llu off the bucket starts | split pass: %llu records in the wrong group (first %u) | local pass: %llu out of order (first %u)\n",
-                        n, rb, hb, nsub, sub[0], sub[nsub], (unsigned long long)bad_mono, (unsigned long long)bad_sub, (unsigned long long)bad_split, first_split,
-                        (unsigned long long)bad_sorted, first_sorted);
-            }
-            nw.split_used = true;
-            nw.split_rb = rb;
-            *keys_res = reinterpret_cast<u64*>(keysB);
-            *vals_res = valsB;
-            return 0;
-        }
-    }
-    if (optimistic) {   // declined: the LSD passes keep ties in the order they find them, so the top-digit pass once more, stable
-        SA_HIP_CHECK(hipMemsetAsync(ws.tickets(), 0, NCHUNK * sizeof(u32), stream));
-        if (++ws.epoch >= (1u << 30)) {
-            SA_HIP_CHECK(hipMemsetAsync(ws.status, 0, (size_t)ws.max_tiles * RADIX * sizeof(u64), stream));
-            ws.epoch = 1;
-        }
-        if ((rc = launch_text_top(false))) return rc;
-    }
-    if (try_split && split_tile_n != seg_tile_n)   // declined: the plan again, for the tiles of the LSD passes
-        hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(256), 0, stream, ws.hist(0), seg_tile_n, nw.plan);
+    const u32 flat_max = n / (512u * SEG_ITEMS) + 1 + RADIX;   // >= sum over buckets of ceil(size / tile)
     // histogram of the first narrow digit per bucket (the LSD passes' histograms are zeroed here: the three-pass plan has no use for them)
     SA_HIP_CHECK(hipMemsetAsync(nw.hist, 0, NarrowWorkspace::hist_bytes(), stream));
     {
@@ -1415,10 +1434,7 @@ inline int radix_sort_narrow(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_
     u32* kin = reinterpret_cast<u32*>(keysB); u32* vin = valsB;
     u32* kout = reinterpret_cast<u32*>(keysA); u32* vout = valsA;
     for (int p = 0; p < np; ++p) {
-        if (++ws.epoch >= (1u << 30)) {
-            SA_HIP_CHECK(hipMemsetAsync(ws.status, 0, (size_t)ws.max_tiles * RADIX * sizeof(u64), stream));
-            ws.epoch = 1;
-        }
+        if ((rc = ws.next_epoch(stream))) return rc;
         const bool last = (p == np - 1);
         const int bits_p = last ? (lo_bits - RADIX_BITS * (np - 1)) : RADIX_BITS;
         hipLaunchKernelGGL(seg_scan_kernel, dim3(RADIX), dim3(256), 0, stream, nw.hist + (size_t)p * RADIX * RADIX, nw.plan, nw.base);
@@ -1436,19 +1452,57 @@ inline int radix_sort_narrow(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_
         a.next_hist = last ? nullptr : nw.hist + (size_t)(p + 1) * RADIX * RADIX;
         a.status = ws.status; a.ticket = nw.tickets + p * NCHUNK; a.epoch = ws.epoch; a.dstat = ws.dstat;
         a.lo_shift = begin_bit; a.incl_mask = SA_INCL_MASK;   // every 4th tile: 1 / 3 / 7 / 15 measured 3.84 / 3.74 / 3.80 / 3.98 ms per pass
-        if ((rc = ws.timer.start(stream, last ? 3 : 2))) return rc;
-        if (last) hipLaunchKernelGGL((seg_onesweep_kernel<512, SEG_ITEMS, true>), dim3(flat_max), dim3(512), 0, stream, a);
-        else hipLaunchKernelGGL((seg_onesweep_kernel<512, SEG_ITEMS, false>), dim3(flat_max), dim3(512), 0, stream, a);
         const u64 pass_bytes = (u64)n * ((last && !keep_narrow) ? 20u : 16u) + ((last && vals_res64) ? (u64)n * 8u : 0u);
-        if ((rc = ws.timer.stop(stream, pass_bytes))) return rc;
-        ws.pass_records += n; ws.pass_bytes += pass_bytes; ws.passes += 1;
-        u32* tk = kin; kin = kout; kout = tk;
-        u32* tv = vin; vin = vout; vout = tv;
+        rc = ws.timed_pass(stream, last ? 3 : 2, n, pass_bytes, [&] {
+            if (last) hipLaunchKernelGGL((seg_onesweep_kernel<512, SEG_ITEMS, true>), dim3(flat_max), dim3(512), 0, stream, a);
+            else hipLaunchKernelGGL((seg_onesweep_kernel<512, SEG_ITEMS, false>), dim3(flat_max), dim3(512), 0, stream, a);
+        });
+        if (rc) return rc;
+        std::swap(kin, kout);
+        std::swap(vin, vout);
     }
     SA_HIP_CHECK(hipGetLastError());
-    *keys_res = reinterpret_cast<u64*>(kin);
-    *vals_res = vin;
+    res->keys = reinterpret_cast<u64*>(kin);
+    res->vals = vin;
     return 0;
+}
+
+inline int radix_sort_narrow(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, u64* keysA, u32* valsA, u64* keysB,
+                             u32* valsB, u32 n, int begin_bit, NarrowSortResult* res, const TextSource* src = nullptr,
+                             bool keep_narrow = false, int64_t* vals_res64 = nullptr, const LocalFlagsRequest* flags_req = nullptr) {
+    int rc;
+    *res = NarrowSortResult{};
+    const int lo_bits = 56 - begin_bit;   // 1 .. 32
+    u32* const k32A = reinterpret_cast<u32*>(keysA);
+    u32* const k32B = reinterpret_cast<u32*>(keysB);
+    SA_HIP_CHECK(hipMemsetAsync(nw.tickets, 0, (size_t)NARROW_MAX_PASSES * NCHUNK * sizeof(u32), stream));
+    // the three-pass plan (radix_split.hpp) is considered for this sort; its passes do not need the top-digit pass to be stable,
+    // so that pass runs in its CLAIM form first -- and once more, stable, should the plan be declined
+    const bool try_split = nw.split_enabled && keep_narrow && ws.block == 512 && lo_bits - LOCAL_BIN_BITS >= 1;
+    const bool optimistic = try_split && src && nw.top_claims;
+    if ((rc = narrow_top_digit(ws, nw, stream, keysA, k32B, valsB, n, begin_bit, src, optimistic))) return rc;
+    const u32 seg_tile_n = 512u * SEG_ITEMS;
+    const u32 split_tile_n = 512u * (u32)nw.split_items;   // the split pass has its own tile size: the plan is made for it first
+    hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(256), 0, stream, ws.hist(0), try_split ? split_tile_n : seg_tile_n, nw.plan);
+    if (try_split) {
+        const int hb = (lo_bits - LOCAL_BIN_BITS < SPLIT_BITS) ? lo_bits - LOCAL_BIN_BITS : SPLIT_BITS;   // key bits the histogram looks at
+        const u32 split_flat_max = n / split_tile_n + 1 + RADIX;
+        SplitLevel lv;
+        if ((rc = narrow_plan_look(nw, stream, k32B, lo_bits, hb, split_flat_max, &lv))) return rc;
+        res->max_group = nw.host_word[lv.rb > 0 ? lv.rb : hb];
+        if (lv.rb > 0) {
+            if ((rc = narrow_split_pass(ws, nw, stream, k32B, valsB, k32A, valsA, n, lo_bits, hb, lv.rb, split_flat_max))) return rc;
+            if ((rc = narrow_local_pass(ws, nw, stream, k32A, valsA, k32B, valsB, vals_res64, n, begin_bit, lv.rb, lv.big, flags_req,
+                                        &res->flags_done))) return rc;
+            if (diag_env("SA_HIP_SPLIT_DEBUG") && (rc = split_debug_check(nw, stream, k32A, k32B, valsB, n, lo_bits, hb, lv.rb))) return rc;
+            res->rb = lv.rb;
+            res->keys = keysB;
+            res->vals = valsB;
+            return 0;
+        }
+        if ((rc = narrow_declined(ws, nw, stream, k32B, valsB, n, begin_bit, src, optimistic, split_tile_n, seg_tile_n))) return rc;
+    }
+    return narrow_lsd_passes(ws, nw, stream, keysA, valsA, keysB, valsB, n, begin_bit, keep_narrow, vals_res64, res);
 }
 
 }  // namespace sa

@@ -19,6 +19,9 @@
 // computed on whichever array holds the pass's digit, both key arrays are staged in LDS side by side at the record's
 // tile-local sorted position (one round for the 6 key bytes), the values follow through the same buffer.  The last pass
 // rebuilds full u64 keys -- the flags pass, the bucket directory and the query kernel see what the 12-byte plan left them.
+//
+// Host driver: radix_sort_narrow48 runs on the pieces of the other drivers -- the top-digit pass through launch_text_top()
+// in its EXT form (radix_narrow.hpp), every pass through RadixWorkspace::next_epoch / timed_pass (radix_sort.hpp).
 #pragma once
 #include "radix_narrow.hpp"
 
@@ -242,7 +245,7 @@ inline bool narrow48_applies(const RadixWorkspace& ws, u64 n, int begin_bit, int
 }
 
 // Sort n records (key of every text position, position) by key bits [begin_bit, 64), stable; keys = the first src->k0
-// characters (radix_prepare() + narrow_text_histogram() before).  keysA / keysB: 8 n + 64 bytes each (k32 in the first
+// characters (radix_prepare() + text_histogram() of the top digit before).  keysA / keysB: 8 n + 64 bytes each (k32 in the first
 // 4 n bytes of a buffer, k16 behind it); result: *keys_res = u64 full keys, *vals_res.
 inline int radix_sort_narrow48(RadixWorkspace& ws, NarrowWorkspace& nw, hipStream_t stream, u64* keysA, u32* valsA,
                                u64* keysB, u32* valsB, u32 n, int begin_bit, u64** keys_res, u32** vals_res, const TextSource& src,
@@ -252,7 +255,6 @@ inline int radix_sort_narrow48(RadixWorkspace& ws, NarrowWorkspace& nw, hipStrea
     const int hi_bits = rem - 16;                                // in k32: 17 .. 32
     const int np_hi = (hi_bits + RADIX_BITS - 1) / RADIX_BITS;   // 3 or 4
     const int np = 2 + np_hi;
-    const SortGeom g = make_geom(n, TEXT_TILE);
     SA_HIP_CHECK(hipMemsetAsync(nw.hist, 0, NarrowWorkspace::hist_bytes(), stream));
     SA_HIP_CHECK(hipMemsetAsync(nw.tickets, 0, (size_t)NARROW_MAX_PASSES * NCHUNK * sizeof(u32), stream));
     const size_t off16 = ((size_t)n * 4 + 63) & ~(size_t)63;    // k16 of a buffer starts here
@@ -260,24 +262,12 @@ inline int radix_sort_narrow48(RadixWorkspace& ws, NarrowWorkspace& nw, hipStrea
     auto k16_of = [&](u64* buf) { return reinterpret_cast<u16*>(reinterpret_cast<u8*>(buf) + off16); };
 
     // top digit straight from the text: k32, k16 and the positions leave in top-digit order
-    {
-        if (++ws.epoch >= (1u << 30)) {
-            SA_HIP_CHECK(hipMemsetAsync(ws.status, 0, (size_t)ws.max_tiles * RADIX * sizeof(u64), stream));
-            ws.epoch = 1;
-        }
-        hipLaunchKernelGGL(radix_scan_hist_kernel, dim3(1), dim3(256), 0, stream, ws.hist(0), ws.base());
-        TextPassArgs t;
-        t.text = src.text; t.map = nw.map_dev; t.n = n; t.b = src.b; t.k0 = src.k0; t.begin_bit = begin_bit;
-        t.keys_out32 = k32_of(keysB); t.ext_out16 = k16_of(keysB); t.vals_out = valsB; t.g = g; t.digit_base = ws.base();
-        t.status = ws.status; t.ticket = ws.tickets(); t.epoch = ws.epoch; t.dstat = ws.dstat; t.incl_mask = SA_INCL_MASK; t.cursor = nullptr; t.owned = 0;
-        if ((rc = ws.timer.start(stream, 1))) return rc;
-        hipLaunchKernelGGL((text_top_pass_kernel<512, true>), dim3(g.tiles), dim3(512), 0, stream, t);
-        if ((rc = ws.timer.stop(stream, (u64)n * 11u))) return rc;
-        ws.pass_records += n; ws.pass_bytes += (u64)n * 11u; ws.passes += 1;
-    }
-    const u32 tile_mid = 512u * SEG48_ITEMS;
+    if ((rc = ws.next_epoch(stream))) return rc;
+    hipLaunchKernelGGL(radix_scan_hist_kernel, dim3(1), dim3(256), 0, stream, ws.hist(0), ws.base());
+    if ((rc = launch_text_top(ws, nw, stream, src, n, begin_bit, TOP_EXT, k32_of(keysB), k16_of(keysB), valsB))) return rc;
+    const u32 tile_mid = 512u * SEG48_ITEMS;   // (SEG48_LAST_ITEMS == SEG48_ITEMS: the last pass runs on the same flat tiles)
     hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(256), 0, stream, ws.hist(0), tile_mid, nw.plan);
-    const u32 flat_mid = n / tile_mid + 1 + RADIX, flat_last = flat_mid;
+    const u32 flat_mid = n / tile_mid + 1 + RADIX;
     {   // histogram of the first narrow digit (low 8 bits of k16) per bucket
         const u32 tpb = 4;
         hipLaunchKernelGGL((seg_hist_kernel<512, SEG48_ITEMS, u16>), dim3(div_up(flat_mid, tpb)), dim3(512), 0, stream,
@@ -286,10 +276,7 @@ inline int radix_sort_narrow48(RadixWorkspace& ws, NarrowWorkspace& nw, hipStrea
     u64* bin = keysB; u32* vin = valsB;
     u64* bout = keysA; u32* vout = valsA;
     for (int p = 0; p < np; ++p) {
-        if (++ws.epoch >= (1u << 30)) {
-            SA_HIP_CHECK(hipMemsetAsync(ws.status, 0, (size_t)ws.max_tiles * RADIX * sizeof(u64), stream));
-            ws.epoch = 1;
-        }
+        if ((rc = ws.next_epoch(stream))) return rc;
         const bool last = (p == np - 1);
         const bool on16 = p < 2;
         auto bits_of = [&](int q) { return q < 2 ? RADIX_BITS : ((q == np - 1) ? hi_bits - RADIX_BITS * (np_hi - 1) : RADIX_BITS); };
@@ -309,15 +296,15 @@ inline int radix_sort_narrow48(RadixWorkspace& ws, NarrowWorkspace& nw, hipStrea
         a.next_hist = last ? nullptr : nw.hist + (size_t)(p + 1) * RADIX * RADIX;
         a.status = ws.status; a.ticket = nw.tickets + p * NCHUNK; a.epoch = ws.epoch; a.dstat = ws.dstat;
         a.begin_bit = begin_bit; a.incl_mask = SA_INCL_MASK;
-        if ((rc = ws.timer.start(stream, last ? 3 : 2))) return rc;
-        if (last) hipLaunchKernelGGL((seg48_onesweep_kernel<512, SEG48_LAST_ITEMS, false, true>), dim3(flat_last), dim3(512), 0, stream, a);
-        else if (on16) hipLaunchKernelGGL((seg48_onesweep_kernel<512, SEG48_ITEMS, true, false>), dim3(flat_mid), dim3(512), 0, stream, a);
-        else hipLaunchKernelGGL((seg48_onesweep_kernel<512, SEG48_ITEMS, false, false>), dim3(flat_mid), dim3(512), 0, stream, a);
         const u64 pass_bytes = (u64)n * (last ? 22u : 20u) + ((last && vals_res64) ? (u64)n * 8u : 0u);
-        if ((rc = ws.timer.stop(stream, pass_bytes))) return rc;
-        ws.pass_records += n; ws.pass_bytes += pass_bytes; ws.passes += 1;
-        u64* tb = bin; bin = bout; bout = tb;
-        u32* tv = vin; vin = vout; vout = tv;
+        rc = ws.timed_pass(stream, last ? 3 : 2, n, pass_bytes, [&] {
+            if (last) hipLaunchKernelGGL((seg48_onesweep_kernel<512, SEG48_LAST_ITEMS, false, true>), dim3(flat_mid), dim3(512), 0, stream, a);
+            else if (on16) hipLaunchKernelGGL((seg48_onesweep_kernel<512, SEG48_ITEMS, true, false>), dim3(flat_mid), dim3(512), 0, stream, a);
+            else hipLaunchKernelGGL((seg48_onesweep_kernel<512, SEG48_ITEMS, false, false>), dim3(flat_mid), dim3(512), 0, stream, a);
+        });
+        if (rc) return rc;
+        std::swap(bin, bout);
+        std::swap(vin, vout);
     }
     SA_HIP_CHECK(hipGetLastError());
     *keys_res = bin;

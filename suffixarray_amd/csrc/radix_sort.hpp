@@ -35,6 +35,10 @@
 //      global stores, counting the next pass's (chunk, digit) histogram on the way.
 // Algorithmic bytes per pass over M records: 2*M*(8+4).
 //
+// Host side: every driver (radix_sort_pairs here, radix_sort_narrow, radix_sort_narrow48) puts the same step around a pass
+// kernel, and RadixWorkspace holds it: next_epoch() numbers the pass, timed_pass() takes the launch as a callable between
+// the stopwatch's events and counts the pass's records and algorithmic bytes (given once) into BuildStats' figures.
+//
 // This replaces, by function only, the bucket placement / induced-sorting scans of the
 // reference's libsais (libsais.c:1542-1614, 2110-2141, 2942-2975): same output order, no
 // shared code or structure.
@@ -42,6 +46,7 @@
 #include "common.hpp"
 #include "scan.hpp"
 #include <type_traits>
+#include <utility>
 
 namespace sa {
 
@@ -583,6 +588,28 @@ struct RadixWorkspace {
         timer.destroy();
     }
     void reset_stats() { timer.reset(); pass_records = 0; pass_bytes = 0; passes = 0; }
+
+    // ---- the pass step: what every sort driver does around a pass kernel ----
+    // A new epoch for the next pass that publishes to `status` (a granule is told from an earlier pass's by it); once per
+    // 2^30 passes the granules are re-zeroed and the count starts over.
+    int next_epoch(hipStream_t stream) {
+        if (++epoch >= (1u << 30)) {
+            SA_HIP_CHECK(hipMemsetAsync(status, 0, (size_t)max_tiles * RADIX * sizeof(u64), stream));
+            epoch = 1;
+        }
+        return 0;
+    }
+    // One timed, counted pass over n records: launch() enqueues the pass kernel between the stopwatch's two events.
+    // kind: EventTimer's; bytes: the algorithmic bytes of the launch (records x bytes read + written per record).
+    template <typename Launch>
+    int timed_pass(hipStream_t stream, int kind, u32 n, u64 bytes, Launch&& launch) {
+        int rc;
+        if ((rc = timer.start(stream, kind))) return rc;
+        launch();
+        if ((rc = timer.stop(stream, bytes))) return rc;
+        pass_records += n; pass_bytes += bytes; passes += 1;
+        return 0;
+    }
 };
 
 struct SortPlan {
@@ -642,10 +669,7 @@ inline int radix_sort_pairs(RadixWorkspace& ws, hipStream_t stream, u64* keysA, 
 
     u64* kin = keysA; u32* vin = valsA; u64* kout = keysB; u32* vout = valsB;
     for (int p = 0; p < pl.npasses; ++p) {
-        if (++ws.epoch >= (1u << 30)) {  // epoch wrap: re-zero the granules once per 2^30 passes
-            SA_HIP_CHECK(hipMemsetAsync(ws.status, 0, (size_t)ws.max_tiles * RADIX * sizeof(u64), stream));
-            ws.epoch = 1;
-        }
+        if ((rc = ws.next_epoch(stream))) return rc;
         hipLaunchKernelGGL(radix_scan_hist_kernel, dim3(1), dim3(256), 0, stream, ws.hist(p), ws.base());
         SortPassArgs a;
         a.keys_in = kin;
@@ -668,23 +692,21 @@ inline int radix_sort_pairs(RadixWorkspace& ws, hipStream_t stream, u64* keysA, 
         a.incl_mask = SA_INCL_MASK;
         a.keys_out32 = nullptr;
         a.narrow_shift = 0;
-        if ((rc = ws.timer.start(stream, 0))) return rc;
         const u32 grid = pl.g.tiles;   // one tile per workgroup
         const bool by_producer = (p == 0 && pass0 && pass0->launch);
-        if (by_producer)
-            pass0->launch(pass0->ctx, stream, a, grid);
-        else if (ws.block == 512)
-            hipLaunchKernelGGL((radix_onesweep_kernel<512, 0>), dim3(grid), dim3(512), 0, stream, a);
-        else
-            hipLaunchKernelGGL((radix_onesweep_kernel<256, 0>), dim3(grid), dim3(256), 0, stream, a);
         const u64 pass_b = (u64)n * (by_producer ? pass0->bytes_per_record : (a.vals_in ? 24u : 20u));   // pass 0 of a build generates its values
-        if ((rc = ws.timer.stop(stream, pass_b))) return rc;
-        ws.pass_records += n;
-        ws.pass_bytes += pass_b;
-        ws.passes += 1;
+        rc = ws.timed_pass(stream, 0, n, pass_b, [&] {
+            if (by_producer)
+                pass0->launch(pass0->ctx, stream, a, grid);
+            else if (ws.block == 512)
+                hipLaunchKernelGGL((radix_onesweep_kernel<512, 0>), dim3(grid), dim3(512), 0, stream, a);
+            else
+                hipLaunchKernelGGL((radix_onesweep_kernel<256, 0>), dim3(grid), dim3(256), 0, stream, a);
+        });
+        if (rc) return rc;
         if (ws.debug_hook) ws.debug_hook(ws.debug_ctx, p, pl.npasses, a.shift, a.mask, kin, a.vals_in, kout, vout, n);
-        u64* tk = kin; kin = kout; kout = tk;
-        u32* tv = vin; vin = vout; vout = tv;
+        std::swap(kin, kout);
+        std::swap(vin, vout);
     }
     SA_HIP_CHECK(hipGetLastError());
     *keys_res = kin;

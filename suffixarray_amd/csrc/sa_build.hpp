@@ -1912,15 +1912,16 @@ struct Builder {
                                pl.npasses > 1 && n >= (1u << 16);
         stats.text_top_pass = (text_pass || wide_text || narrow48_path) ? 1u : 0u;
         if (text_pass || narrow48_path) {
-            if ((rc = narrow_text_histogram(radix, narrow, stream, text.as<u8>(), map, n32, b))) return rc;
+            if ((rc = text_histogram(radix, narrow, stream, text.as<u8>(), map, n32, b, TEXT_TILE, 0))) return rc;
         } else if (wide_text) {
-            if ((rc = wide_text_histogram(radix, narrow, stream, text.as<u8>(), map, n32, b, k0))) return rc;
+            if ((rc = text_histogram(radix, narrow, stream, text.as<u8>(), map, n32, b, radix.tile(), k0))) return rc;
         } else {
             hipLaunchKernelGGL(keygen_kernel, dim3(stream_grid(n, BLD_TILE)), dim3(BLD_BLOCK), 0, stream, text.as<u8>(), n, map, b,
                                k0, keys0.as<u64>(), pl.g, narrow_path ? 56 : pl.shift(0), narrow_path ? 255u : pl.mask(0),
                                fuse_hist ? radix.hist(0) : (u32*)nullptr);
         }
         u64* kres; u32* vres;
+        bool flags_by_local_pass = false;   // the three-pass plan's local pass has written the directory and staged the active records
         // the narrow keys can stay narrow when the query directory comes out of the flags pass below (the directory
         // by binary search reads u64 keys)
         const bool keep_narrow = narrow_path && narrow_k && fuse_directory;
@@ -1930,11 +1931,14 @@ struct Builder {
             src.text = text.as<u8>(); src.b = b; src.k0 = k0;
             LocalFlagsRequest freq;   // the first flags pass inside the sort's last pass, when the three-pass plan is taken
             if (keep_narrow && lite_flags) { freq.prepare = &Builder::split_flags_prepare; freq.ctx = this; }
+            NarrowSortResult res;
             if ((rc = radix_sort_narrow(radix, narrow, stream, keys0.as<u64>(), vals0.as<u32>(), keys1.as<u64>(), vals1.as<u32>(),
-                                        n32, begin_bit, &kres, &vres, text_pass ? &src : nullptr, keep_narrow, sa64_out, &freq))) return rc;
+                                        n32, begin_bit, &res, text_pass ? &src : nullptr, keep_narrow, sa64_out, &freq))) return rc;
+            kres = res.keys; vres = res.vals;
             if (sa64_out) stats.widen_fused = 1;
-            stats.split_plan = narrow.split_used ? (u32)narrow.split_rb : 0u;
-            stats.split_max = narrow.split_max_seen;
+            stats.split_plan = (u32)res.rb;
+            stats.split_max = res.max_group;
+            flags_by_local_pass = res.flags_done;
         } else if (narrow48_path) {
             // The 56 key bits hold k0 whole characters and, when the next one does not fit, its TOP bits: the key is the first
             // 56 bits of the (k0 + 1)-character key.  Groups are still classes of the first k0 characters (h = k0) cut a little
@@ -1976,12 +1980,12 @@ struct Builder {
             // has left free), the full form only when a tile overflows its staging row
             void* stage = (static_cast<void*>(kres) == keys0.p) ? keys1.p : keys0.p;
             bool overflow = false;
-            if (narrow_path && narrow.split_flags_done) { if ((rc = flags_after_split(nk, tot, &overflow))) return rc; }
+            if (flags_by_local_pass) { if ((rc = flags_after_split(nk, tot, &overflow))) return rc; }
             else
             if ((rc = flags_lite_pass(nk, n32, stage, tot, &overflow))) return rc;
             if (overflow) { if ((rc = flags_and_counts(kres, n32, flags.as<u8>(), nullptr, nullptr, tot, false, &nk))) return rc; }
             else { flags_valid = false; staged = true; }
-            stats.lite_flags = staged ? ((narrow_path && narrow.split_flags_done) ? 2u : 1u) : 0u;
+            stats.lite_flags = staged ? (flags_by_local_pass ? 2u : 1u) : 0u;
         } else
         if ((rc = flags_and_counts(kres, n32, flags.as<u8>(), nullptr, nullptr, tot, fuse_directory, keep_narrow ? &nk : nullptr))) return rc;
         if ((rc = check_device_status())) return rc;

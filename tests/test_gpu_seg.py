@@ -19,7 +19,8 @@ init):
 
 BuildStats must show that the path under test ran: narrow48, narrow_k, text_top_pass, split_plan == 0, one launch of the
 top-digit pass (two on the declined path: claim form, then stable form), and as many launches of the LSD pass kernels as
-seg_cases.passes() lists.  One run per plan also asks for the int64 array (build_device64) and expects it from the sort's last
+seg_cases.passes() lists; for the L = k0 build, where the sort is all that counts, also the passes, records and algorithmic
+bytes, total and per kind, that the host drivers add up (_accounting).  One run per plan also asks for the int64 array (build_device64) and expects it from the sort's last
 store (widen_fused).  All comparisons are exact; a mismatch names the first bad slot, its bucket, its flat tile and whether
 that tile is full or partial.  Text, oracle arrays and models are shared by the runs of one case."""
 import time
@@ -55,6 +56,31 @@ def _read(ptr, nbytes, dtype):
     return device_view(ptr, nbytes, torch.uint8, torch.device("cuda", 0)).cpu().numpy().view(dtype)
 
 
+def _accounting(st, T, form, k0, spec, err):
+    """The L = k0 build runs one sort and nothing else that counts: passes, records and algorithmic bytes per pass kind
+    (EventTimer's kinds: 0 12-byte passes, 1 top digit, 2 LSD passes but the last, 3 the last) as the host drivers count them,
+    in units of n.  Every counted pass moves n records."""
+    plan_, _, expect = sg.FORMS[form]
+    n = int(T.t.size)
+    if plan_ == 12:      # pass 0 reads the text (13 bytes per record), every other pass 8 + 4 bytes in and out
+        np12 = -(-T.b * k0 // 8)
+        per_kind = [13 + 24 * (np12 - 1), 0, 0, 0]
+        count = np12
+    else:
+        mid = len(spec["passes"]) - 1
+        if plan_ == 10:  # the top-digit pass writes k16 too; the last pass rebuilds the u64 keys
+            per_kind = [0, 11, 20 * mid, 22]
+        else:            # from the text 9 bytes per record (twice on the declined path), from a u64 key array 16
+            top = 9 * expect["top"] if expect["text_top_pass"] else 16
+            per_kind = [0, top, 16 * mid, 16 if expect["narrow_k"] else 20]
+        count = expect["top"] + mid + 1
+    want = dict(radix_passes=count, radix_records=count * n, radix_bytes=sum(per_kind) * n, pass_bytes=[x * n for x in per_kind])
+    for x, v in want.items():
+        got = list(st[x]) if isinstance(v, list) else st[x]
+        if got != v:
+            err("L=%d: %s = %s, the drivers' model counts %s (n = %d)", k0, x, st[x], v, n)
+
+
 def _stats(st, T, form, k0, spec, err, L):
     plan_, env, expect = sg.FORMS[form]
     want = dict(initial_chars=k0, bits_per_symbol=T.b, sigma=T.sigma, narrow48=expect["narrow48"], narrow_k=expect["narrow_k"],
@@ -63,6 +89,8 @@ def _stats(st, T, form, k0, spec, err, L):
         if st[x] != v:
             err("L=%d: %s = %s, expected %s", L, x, st[x], v)
     launches = st["pass_launches"]
+    if L == k0:
+        _accounting(st, T, form, k0, spec, err)
     if plan_ == 12:
         if launches[0] == 0 or launches[1:] != [0, 0, 0]:
             err("L=%d: the 12-byte control launched %s", L, launches)

@@ -3,7 +3,7 @@ tests/split_cases.py).  Every fallback of this plan repairs the array -- a stagi
 as its own pass, a sub-bucket over the cap moves the sort to the large form or to the LSD passes, a tied pair that is never
 staged stays in (key, suffix) order -- so every build is compared four ways: the array with the oracle (and verify()), the
 queries with the oracle (they go through the directory the local pass writes, the entries of empty sub-buckets and the end
-marker included), BuildStats' plan fields with the model (split_plan, split_max, lite_flags, radix_passes), and its
+marker included), BuildStats' plan fields with the model (split_plan, split_max, lite_flags, radix_passes and the records and bytes they count), and its
 refinement counts with refine_cases.simulate on the tied groups read off the oracle's array, exactly: a tied slot that is
 not staged, or staged with the wrong head bit, changes tiny_resolved / finisher_* / rounds / active_total.
 
@@ -123,7 +123,9 @@ def run_case(gpu, oracle, monkeypatch, name, errors):
         expect = dict(split_plan=c["plan"], split_max=c["split_max"], lite_flags=lite, narrow_k=c.get("narrow_k", 1), initial_chars=T.k,
                       bits_per_symbol=5)
         if taken:
-            expect["radix_passes"] = 3
+            # top digit from the text 9 bytes per record, split pass 16, local pass 16 (24 when it stores the int64 array too:
+            # the wide form's stats are those of the 64-bit build)
+            expect.update(radix_passes=3, radix_records=3 * t.size, radix_bytes=(49 if wide else 41) * t.size)
         if (m["plan"], m["split_max"], m["lite"]) != (c["plan"], c["split_max"], c["lite"]):
             err("model and claim disagree: %s", (m["plan"], m["split_max"], m["lite"]))
         for x, v in expect.items():
