@@ -49,6 +49,12 @@ __device__ __forceinline__ T wave_scan_incl(T v, Op op) {
     return v;
 }
 
+// the wave's aggregate op(v[0], ..., v[63]) in every lane: the scan read at lane 63 (a minimum: ~wave_reduce(~key, ScanMax{}))
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+    return __shfl(wave_scan_incl(v, op), WAVE - 1);
+}
+
 // exclusive scan over a workgroup of WAVES full waves (thread order): wave scan, lane 63 publishes its wave's total to
 // s_w[WAVES], barrier, prefix over the earlier waves, trailing barrier (s_w may be reused at once, e.g. by the next trip of
 // a carry loop).  *total, when asked for, is the workgroup's aggregate in every thread.  Every thread must call it.

@@ -164,7 +164,7 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_all_kernel(View x, RankV
         Walk mine{0u, 0u, 0u};
         if (lane < m) mine = tq_walk_of(x, sp[lane]);
         const u64 key = lane < m ? ((u64)(mine.end - mine.a) << 32) | lane : ~0ull;
-        const u64 best = ~__shfl(wave_scan_incl(~key, ScanMax{}), WAVE - 1);
+        const u64 best = ~wave_reduce(~key, ScanMax{});
         const u32 driver = m ? (u32)best : 0u, count = m ? (u32)(best >> 32) : 0u;   // (m == 0: the host refused such a table)
         const u32 first_u = __shfl(mine.a, (int)driver);
         const u32 examined = (g.budget && g.budget < count) ? g.budget : count;
@@ -276,9 +276,7 @@ inline int launch_tf(const Index& x, const Docs& d, const DocRanks& r, hipStream
 
 // G >= 1 groups, G * cap < 2^31 (cap may be 0)
 inline int launch_all(const Index& x, const Docs& d, const DocRanks& r, hipStream_t stream, const AllArgs& g) {
-    const u64 wave_grid = (g.G + NEXT_WAVES - 1) / NEXT_WAVES;
-    const u32 grid = (u32)(wave_grid < 256u * 16u ? wave_grid : 256u * 16u);
-    hipLaunchKernelGGL(tq_all_kernel, dim3(grid), dim3(NEXT_WAVES * WAVE), 0, stream, x.view(), r.view(d), g);
+    hipLaunchKernelGGL(tq_all_kernel, dim3(wave_row_grid(g.G)), dim3(NEXT_WAVES * WAVE), 0, stream, x.view(), r.view(d), g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }

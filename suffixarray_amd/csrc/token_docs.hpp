@@ -310,10 +310,8 @@ inline int launch_locate(const Index& x, const Docs& d, hipStream_t stream, cons
 
 // Q >= 1 spans, Q * cap < 2^31 (cap may be 0); g.examined is zeroed on the stream first
 inline int launch_docs(const Index& x, const Docs& d, hipStream_t stream, const DocsArgs& g) {
-    const u64 wave_grid = (g.Q + NEXT_WAVES - 1) / NEXT_WAVES;
-    const u32 grid = (u32)(wave_grid < 256u * 16u ? wave_grid : 256u * 16u);
     SA_HIP_CHECK(hipMemsetAsync(g.examined, 0, sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(tq_docs_kernel, dim3(grid), dim3(NEXT_WAVES * WAVE), 0, stream, x.view(), d.view(), g);
+    hipLaunchKernelGGL(tq_docs_kernel, dim3(wave_row_grid(g.Q)), dim3(NEXT_WAVES * WAVE), 0, stream, x.view(), d.view(), g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }

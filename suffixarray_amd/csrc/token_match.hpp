@@ -25,8 +25,8 @@
 //                         then fact 1: a range search, two neighbour LCPs (tq_lcp), and a second range search when 1 <= ms < |P|.
 //   tq_match_docs_kernel  a template over the position's 16-byte record (here sa_hip_token_span; over a shard set the merged
 //                         record of token_shard_match.hpp), of which it reads .length and which it copies out whole.
-//                         One wave per document, NEXT_WAVES per workgroup, no LDS.  The document's positions in windows of 64,
-//                         spans[j] read coalesced (16 bytes per lane, the next window's load in flight); the predecessor's end by
+//                         One wave per document, NEXT_WAVES per workgroup, no LDS.  The document's positions by tq_doc_windows,
+//                         spans[j] read coalesced (16 bytes per lane); the predecessor's end by
 //                         lane_shift_up with prev_end carried across windows (fact 2), E by wave_scan_incl with max and a carried
 //                         value (fact 3); a ballot and a popcount prefix give the output slots of the maximal matches of at least
 //                         min_length.  Lanes with a slot < cap write positions[d * cap + slot] (the offset inside the document)
@@ -118,6 +118,25 @@ __device__ __forceinline__ MatchRecWords tq_match_rec_load(const Rec* p) {
     return w;
 }
 
+// One wave's walk over document [o0, o1) (o1 clamped to >= o0), here and in token_score.hpp: windows of 64, lane l at j = a + l.
+// load(j) is called for j < o1 only, one trip before body(j, j < o1, record) uses it; a lane beyond o1 gets a zero record.
+struct DocSpan { u64 o0, o1; };
+__device__ __forceinline__ DocSpan tq_doc_span(const u64* off, u64 d) {
+    const u64 o0 = off[d], o1 = off[d + 1];
+    return DocSpan{o0, o1 > o0 ? o1 : o0};
+}
+template <class Load, class Body>
+__device__ __forceinline__ void tq_doc_windows(const DocSpan& doc, u32 lane, Load load, Body body) {
+    decltype(load(u64{})) nxt{};
+    if (doc.o0 + lane < doc.o1) nxt = load(doc.o0 + lane);
+    for (u64 a = doc.o0; a < doc.o1; a += (u64)WAVE) {
+        const u64 j = a + lane;
+        const auto rec = nxt;
+        if (j + WAVE < doc.o1) nxt = load(j + WAVE);
+        body(j, j < doc.o1, rec);
+    }
+}
+
 template <class Rec>
 struct MatchDocsArgs {
     const Rec* spans;                  // [offsets[Q]], by position
@@ -136,8 +155,8 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_match_docs_kernel(MatchD
     const u32 lane = threadIdx.x & (WAVE - 1);
     const u64 waves = (u64)gridDim.x * NEXT_WAVES;
     for (u64 d = (u64)blockIdx.x * NEXT_WAVES + (threadIdx.x >> 6); d < g.Q; d += waves) {
-        const u64 o0 = g.off[d], o1r = g.off[d + 1];
-        const u64 o1 = o1r > o0 ? o1r : o0;
+        const DocSpan doc = tq_doc_span(g.off, d);
+        const u64 o0 = doc.o0, o1 = doc.o1;
         u32* const pos = g.positions + d * g.cap;
         Rec* const outs = g.out_spans + d * g.cap;
         u64 prev_end = o0;         // end(j - 1) of the window's first position: no match before the document reaches into it
@@ -145,13 +164,7 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_match_docs_kernel(MatchD
         u64 covered = 0;           // this lane's share
         u32 longest = 0;           // this lane's share
         u32 maximal = 0;
-        MatchRecWords nxt = {0u, 0u, 0u, 0u};
-        if (o0 + lane < o1) nxt = tq_match_rec_load(g.spans + o0 + lane);
-        for (u64 a = o0; a < o1; a += (u64)WAVE) {
-            const u64 j = a + lane;
-            const bool act = j < o1;
-            const MatchRecWords sp = nxt;
-            if (j + WAVE < o1) nxt = tq_match_rec_load(g.spans + j + WAVE);
+        tq_doc_windows(doc, lane, [&](u64 j) { return tq_match_rec_load(g.spans + j); }, [&](u64 j, bool act, const MatchRecWords& sp) {
             const u32 sp_length = sp[offsetof(Rec, length) / 4];
             const u64 left = act ? o1 - j : 0;
             const u32 len = act ? (sp_length < left ? sp_length : (u32)left) : 0u;   // a match never passes its document's end
@@ -177,9 +190,9 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_match_docs_kernel(MatchD
             const u64 top = __shfl(incl, WAVE - 1);
             if (top > E) E = top;
             prev_end = __shfl(end, WAVE - 1);                                        // (inactive lanes hold o1: >= every end)
-        }
-        covered = __shfl(wave_scan_incl(covered, ScanSum{}), WAVE - 1);
-        longest = __shfl(wave_scan_incl(longest, ScanMax{}), WAVE - 1);
+        });
+        covered = wave_reduce(covered, ScanSum{});
+        longest = wave_reduce(longest, ScanMax{});
         if (lane == 0) {
             sa_hip_token_match_head h;
             h.written = maximal < g.cap ? maximal : g.cap;
@@ -204,9 +217,7 @@ inline int launch_match(const Index& x, hipStream_t stream, const MatchArgs& g) 
 // Q >= 1 documents, Q * cap < 2^31 (cap may be 0); every pointer on the device; asynchronous on `stream`
 template <class Rec>
 inline int launch_match_docs(hipStream_t stream, const MatchDocsArgs<Rec>& g) {
-    const u64 wave_grid = (g.Q + NEXT_WAVES - 1) / NEXT_WAVES;
-    const u32 grid = (u32)(wave_grid < 256u * 16u ? wave_grid : 256u * 16u);
-    hipLaunchKernelGGL(tq_match_docs_kernel<Rec>, dim3(grid), dim3(NEXT_WAVES * WAVE), 0, stream, g);
+    hipLaunchKernelGGL(tq_match_docs_kernel<Rec>, dim3(wave_row_grid(g.Q)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }

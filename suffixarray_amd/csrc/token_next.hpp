@@ -5,7 +5,7 @@
 // non-decreasing in r and the one suffix that ends stands first: the next symbols of a span with their multiplicities are the
 // run-length encoding of the step function s over [first + ended, first + count).
 //
-//   tq_span_kernel       one lane per context.  mode 0: one tq_range (token_query.hpp).  mode 1: the largest L such that the
+//   tq_span_kernel       one lane per context.  mode 0: one tq_range (tq_span_exact).  mode 1: the largest L such that the
 //                        last L symbols of the context occur (need_next: occur with a next symbol) -- that property is
 //                        monotone in L, so a binary search over L, <= 64 probes of tq_range.
 //   tq_next_kernel       one wave per span, 4 waves per workgroup.  Window step: 64 consecutive ranks, a lane is a run head
@@ -35,6 +35,11 @@ constexpr int NEXT_WAVES = 4;          // waves (spans in flight) per workgroup 
 constexpr u32 NEXT_JUMP_MIN = 256;     // ranks left behind an all-equal window before a jump is taken (4 windows)
 constexpr int NEXT_JUMP_STEPS = 6;     // 64^6 > 2^31
 constexpr int SPAN_PROBES = 64;        // bound of the binary search over L (m < 2^64)
+constexpr u32 WAVE_GRID_MAX = 256u * 16u;   // cap of a wave-per-row launch: twice what 256 CUs hold at 8 waves per SIMD
+inline u32 wave_row_grid(u64 rows) {   // workgroups for `rows` rows, NEXT_WAVES each; the kernels stride over the rows beyond the cap
+    const u64 grid = (rows + NEXT_WAVES - 1) / NEXT_WAVES;
+    return (u32)(grid < WAVE_GRID_MAX ? grid : WAVE_GRID_MAX);
+}
 
 // s(r) of a span of matched length `length`; false: suffix r has no next symbol (or, in a foreign array, lies outside the text)
 __device__ __forceinline__ bool tq_next_symbol(const View& x, u32 r, u32 length, int32_t* s) {
@@ -54,6 +59,20 @@ __device__ __forceinline__ u32 tq_span_ended(const View& x, u32 first, u32 count
     return (count > 0 && first < x.n && (u64)x.sa[first] + length == x.n) ? 1u : 0u;
 }
 
+// the span of the m symbols whose range is r: length saturates at 2^32 - 1 (no text holds a longer pattern: its count is 0)
+__device__ __forceinline__ sa_hip_token_span tq_span_of(const View& x, const sa_hip_pair_u32& r, u64 m) {
+    sa_hip_token_span s;
+    s.first = r.first; s.count = r.second;
+    s.length = m > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)m;
+    s.ended = tq_span_ended(x, r.first, r.second, m);
+    return s;
+}
+// the exact (mode-0) span of P[0 .. m): one tq_range
+__device__ __forceinline__ sa_hip_token_span tq_span_exact(const View& x, const int32_t* __restrict__ P, u64 m) {
+    if (x.n == 0) return sa_hip_token_span{0u, 0u, 0u, 0u};   // an empty index: its arrays are not touched
+    return tq_span_of(x, tq_range(x, P, m), m);
+}
+
 __global__ __launch_bounds__(BLOCK) void tq_span_kernel(View x, const int32_t* __restrict__ pat, const u64* __restrict__ off, u64 Q,
                                                         int mode, u32 max_length, int need_next, sa_hip_token_span* __restrict__ out) {
     const u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x;
@@ -63,14 +82,7 @@ __global__ __launch_bounds__(BLOCK) void tq_span_kernel(View x, const int32_t* _
     const int32_t* P = pat + o0;
     sa_hip_token_span s{0u, 0u, 0u, 0u};
     if (x.n == 0) { out[i] = s; return; }
-    if (mode == 0) {
-        const sa_hip_pair_u32 r = tq_range(x, P, m);
-        s.first = r.first; s.count = r.second;
-        s.length = m > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)m;
-        s.ended = tq_span_ended(x, r.first, r.second, m);
-        out[i] = s;
-        return;
-    }
+    if (mode == 0) { out[i] = tq_span_exact(x, P, m); return; }
     u64 hi = m < x.n ? m : x.n;                         // no more than n symbols match
     if (max_length && hi > max_length) hi = max_length;
     u64 lo = 0;                                         // L = 0 always qualifies: {0, n}
@@ -261,8 +273,7 @@ inline int launch_spans(const Index& x, hipStream_t stream, const int32_t* pat, 
 
 // Q >= 1 spans (Q * cap < 2^31); list: Q u32 and n_list: one u32 of the handle, used by the lane form only
 inline int launch_next(const Index& x, hipStream_t stream, const NextKnobs& knobs, const NextArgs& g, u32* list, u32* n_list) {
-    const u64 wave_grid = (g.Q + NEXT_WAVES - 1) / NEXT_WAVES;
-    const u32 grid = (u32)(wave_grid < 256u * 16u ? wave_grid : 256u * 16u);
+    const u32 grid = wave_row_grid(g.Q);
     if (knobs.lanes) {
         SA_HIP_CHECK(hipMemsetAsync(n_list, 0, sizeof(u32), stream));
         hipLaunchKernelGGL(tq_next_lane_kernel, dim3((u32)((g.Q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x.view(), g, list, n_list);

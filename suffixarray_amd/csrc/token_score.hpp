@@ -26,8 +26,8 @@
 //                         context's range s(r) = T[SA[r] + L] is non-decreasing with the ended suffix first (token_next.hpp), so
 //                         two bounds over the ranks, comparing one symbol each (from K[r] when L <= 1), give {first, token_count}.
 //   tq_score_docs_kernel  one wave per document, NEXT_WAVES per workgroup, no LDS.  The document's records in windows of 64, read
-//                         coalesced (16 bytes per lane, the next window's load in flight), summed per lane and reduced once with
-//                         wave_scan_incl; lane 0 writes the head {scored, seen, certain, longest, length_sum}.
+//                         coalesced (16 bytes per lane, the next window's load in flight: tq_doc_windows), summed per lane and
+//                         reduced once with wave_reduce; lane 0 writes the head {scored, seen, certain, longest, length_sum}.
 //
 // Cost: a probe whose suffix shares k symbols with the context reads k + 1 of them, so a text copied verbatim from the corpus
 // costs about m * min(m, M) * log2 n symbol reads for its m positions in way 1 (one range search per position) and log2 min(m, M)
@@ -149,23 +149,16 @@ struct ScoreDocsArgs {
     sa_hip_token_score_head* heads;    // [Q]
 };
 
-// One wave per document.  Every trip of the walk advances by one window of 64 positions.
+// One wave per document.  The walk is tq_doc_windows (token_match.hpp).
 __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_score_docs_kernel(ScoreDocsArgs g) {
-    static_assert(sizeof(sa_hip_token_score) == sizeof(MatchRecWords), "a record is four words");
     const u32 lane = threadIdx.x & (WAVE - 1);
     const u64 waves = (u64)gridDim.x * NEXT_WAVES;
     for (u64 d = (u64)blockIdx.x * NEXT_WAVES + (threadIdx.x >> 6); d < g.Q; d += waves) {
-        const u64 o0 = g.off[d], o1r = g.off[d + 1];
-        const u64 o1 = o1r > o0 ? o1r : o0;
+        const DocSpan doc = tq_doc_span(g.off, d);
         u64 length_sum = 0;            // this lane's share, as the three below
         u32 seen = 0, certain = 0, longest = 0;
-        MatchRecWords nxt = {0u, 0u, 0u, 0u};
-        if (o0 + lane < o1) nxt = tq_match_rec_load(g.scores + o0 + lane);
-        for (u64 a = o0; a < o1; a += (u64)WAVE) {
-            const u64 j = a + lane;
-            const MatchRecWords w = nxt;
-            if (j + WAVE < o1) nxt = tq_match_rec_load(g.scores + j + WAVE);
-            if (j < o1) {
+        tq_doc_windows(doc, lane, [&](u64 j) { return tq_match_rec_load(g.scores + j); }, [&](u64, bool act, const MatchRecWords& w) {
+            if (act) {
                 const u32 length = w[offsetof(sa_hip_token_score, length) / 4];
                 const u32 cc = w[offsetof(sa_hip_token_score, context_count) / 4];
                 const u32 tc = w[offsetof(sa_hip_token_score, token_count) / 4];
@@ -174,14 +167,14 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_score_docs_kernel(ScoreD
                 certain += tc == cc ? 1u : 0u;
                 if (length > longest) longest = length;
             }
-        }
-        length_sum = __shfl(wave_scan_incl(length_sum, ScanSum{}), WAVE - 1);
-        seen = __shfl(wave_scan_incl(seen, ScanSum{}), WAVE - 1);
-        certain = __shfl(wave_scan_incl(certain, ScanSum{}), WAVE - 1);
-        longest = __shfl(wave_scan_incl(longest, ScanMax{}), WAVE - 1);
+        });
+        length_sum = wave_reduce(length_sum, ScanSum{});
+        seen = wave_reduce(seen, ScanSum{});
+        certain = wave_reduce(certain, ScanSum{});
+        longest = wave_reduce(longest, ScanMax{});
         if (lane == 0) {
             sa_hip_token_score_head h;
-            const u64 scored = o1 - o0;
+            const u64 scored = doc.o1 - doc.o0;
             h.scored = scored > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)scored;
             h.seen = seen;
             h.certain = certain;
@@ -204,9 +197,7 @@ inline int launch_score(const Index& x, hipStream_t stream, const ScoreArgs& g) 
 
 // Q >= 1 documents; every pointer on the device; asynchronous on `stream`
 inline int launch_score_docs(hipStream_t stream, const ScoreDocsArgs& g) {
-    const u64 wave_grid = (g.Q + NEXT_WAVES - 1) / NEXT_WAVES;
-    const u32 grid = (u32)(wave_grid < 256u * 16u ? wave_grid : 256u * 16u);
-    hipLaunchKernelGGL(tq_score_docs_kernel, dim3(grid), dim3(NEXT_WAVES * WAVE), 0, stream, g);
+    hipLaunchKernelGGL(tq_score_docs_kernel, dim3(wave_row_grid(g.Q)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }

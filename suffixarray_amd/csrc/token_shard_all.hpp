@@ -16,8 +16,9 @@
 //                              found by a search of base[0 .. S], at most SHARD_STEPS halvings; then tq_seg_lower twice in RK_s.
 //                              An id >= base[S] gives 0 without touching any RK.
 //   tq_shard_all_plan_kernel   one wave per group.  Lane s loads shard s's clamped count of the group's m <= ALL_MAX spans, one span
-//                              per trip; a wave sum (u64) gives C_j, kept by lane j.  One wave_scan_incl(ScanMax) over the inverted
-//                              key (C_j << 4) | j gives the driver; an exclusive u64 scan of c_{s,driver} gives e_s.  It writes
+//                              per trip; a wave sum (u64) gives C_j, kept by lane j.  One wave_reduce(ScanMax) over the inverted
+//                              key (C_j << 4) | j gives the driver; an exclusive u64 scan of c_{s,driver} gives e_s by
+//                              tq_budget_share (token_shards.hpp), as tq_shard_docs_kernel has it.  It writes
 //                              {driver, e_s} per (group, shard) pair and {driver, C_driver} per group.  A launch of its own: inside
 //                              every pair wave the same S * m span loads would be repeated S times per group.
 //   tq_shard_all_kernel        one wave per (group, shard) pair, pair = g * S + s, NEXT_WAVES per workgroup: the walk of
@@ -25,7 +26,7 @@
 //                              matched, candidates} and the list, local ids, go to scratch of the set, shard-major [s * G + g].
 //                              One atomic add per wave into a u64 counter: the ranks streamed.
 //   tq_shard_all_merge_kernel  one wave per group, lane s holds pair (s, g)'s head: an exclusive u64 scan of `matched` gives every
-//                              shard's first slot, inclusive scans read at lane 63 the three sums.  Shard by shard, while the first
+//                              shard's first slot, wave_reduce the three sums.  Shard by shard, while the first
 //                              slot is below cap, the wave copies the written entries, 64 per step, and adds base[s].  Lane 0 writes
 //                              the head from the plan's {driver, C_driver}.
 //
@@ -123,12 +124,12 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_shard_all_plan_kernel(Sh
                 const Walk k = tq_walk_of(x, g.spans[(u64)lane * g.P + p0 + j]);
                 c = k.end - k.a;
             }
-            const u64 C = __shfl(wave_scan_incl((u64)c, ScanSum{}), WAVE - 1);
+            const u64 C = wave_reduce((u64)c, ScanSum{});
             if (lane == j) mine = C;
         }
         // the driver: the smallest {C_j, j}; lanes beyond the group hold the largest key there is
         const u64 key = lane < m ? (mine << 4) | lane : ~0ull;
-        const u64 best = ~__shfl(wave_scan_incl(~key, ScanMax{}), WAVE - 1);
+        const u64 best = ~wave_reduce(~key, ScanMax{});
         const u32 driver = m ? (u32)(best & 15u) : 0u;     // (m == 0: the host refused such a table)
         const u64 count = m ? best >> 4 : 0ull;
         u32 c = 0;
@@ -137,12 +138,7 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_shard_all_plan_kernel(Sh
             c = k.end - k.a;
         }
         const u64 before = wave_scan_incl((u64)c, ScanSum{}) - c;   // the driver's ranks in the shards in front
-        u32 e = c;
-        if (g.budget) {
-            const u64 left = g.budget > before ? g.budget - before : 0;
-            if (left < c) e = (u32)left;
-        }
-        if (lane < g.S) g.pairs[w * g.S + lane] = ShardAllPlan{driver, e};
+        if (lane < g.S) g.pairs[w * g.S + lane] = ShardAllPlan{driver, tq_budget_share(g.budget, before, c)};
         if (lane == 0) g.groups[w] = ShardAllGroup{driver, 0u, count};
     }
 }
@@ -222,8 +218,8 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_shard_all_merge_kernel(S
         const u64 ma_incl = wave_scan_incl(ma, ScanSum{});
         const u64 slot0 = ma_incl - ma;                    // this shard's first slot
         const u64 matched = __shfl(ma_incl, WAVE - 1);
-        const u64 examined = __shfl(wave_scan_incl(ex, ScanSum{}), WAVE - 1);
-        const u64 candidates = __shfl(wave_scan_incl(ca, ScanSum{}), WAVE - 1);
+        const u64 examined = wave_reduce(ex, ScanSum{});
+        const u64 candidates = wave_reduce(ca, ScanSum{});
         for (u32 s = 0; s < g.S; ++s) {
             const u64 at = __shfl(slot0, (int)s);
             if (at >= g.cap) break;                        // (wave-uniform; the first slots are non-decreasing in s)
@@ -262,27 +258,22 @@ inline int launch_shard_tf(hipStream_t stream, const ShardTfArgs& g) {
     return 0;
 }
 
-inline u32 shard_all_grid(u64 waves) {
-    const u64 wave_grid = (waves + NEXT_WAVES - 1) / NEXT_WAVES;
-    return (u32)(wave_grid < 256u * 16u ? wave_grid : 256u * 16u);
-}
-
 // G >= 1 groups of a chunk
 inline int launch_shard_all_plan(hipStream_t stream, const ShardAllPlanArgs& g) {
-    hipLaunchKernelGGL(tq_shard_all_plan_kernel, dim3(shard_all_grid(g.G)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
+    hipLaunchKernelGGL(tq_shard_all_plan_kernel, dim3(wave_row_grid(g.G)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 // the caller has zeroed g.streamed on the stream
 inline int launch_shard_all(hipStream_t stream, const ShardAllArgs& g) {
-    hipLaunchKernelGGL(tq_shard_all_kernel, dim3(shard_all_grid(g.G * g.S)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
+    hipLaunchKernelGGL(tq_shard_all_kernel, dim3(wave_row_grid(g.G * g.S)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 inline int launch_shard_all_merge(hipStream_t stream, const ShardAllMergeArgs& g) {
-    hipLaunchKernelGGL(tq_shard_all_merge_kernel, dim3(shard_all_grid(g.G)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
+    hipLaunchKernelGGL(tq_shard_all_merge_kernel, dim3(wave_row_grid(g.G)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }

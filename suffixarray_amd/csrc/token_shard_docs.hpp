@@ -17,11 +17,11 @@
 //   tq_shard_docs_kernel        one wave per (context, shard) pair, NEXT_WAVES per workgroup, pair = i * S + s: the shards of a
 //                               context are neighbouring waves, so the S pieces of one long span are walked side by side.  Lane t
 //                               loads shard t's clamped count, one wave_scan_incl over u64 gives the ranks in front of shard s,
-//                               hence e_s = clamp(budget - that sum, 0, c_s) (c_s without a budget).  The walk is tq_docs_walk
+//                               hence e_s = clamp(budget - that sum, 0, c_s) (tq_budget_share).  The walk is tq_docs_walk
 //                               (token_docs.hpp).  The pair's head (sa_hip_token_docs) and its list, local ids, go to scratch of
 //                               the set, shard-major [s * qc + i].  One atomic add per wave into a u64 counter: the ranks streamed.
 //   tq_shard_docs_merge_kernel  one wave per context, lane s holds pair (s, i)'s head.  An exclusive u64 scan of `distinct` gives
-//                               every shard's first slot, the inclusive scans read at lane 63 give the sums of the head.  Shard by
+//                               every shard's first slot, wave_reduce gives the sums of the head.  Shard by
 //                               shard, while the first slot is below cap, the wave copies that shard's written entries, 64 per
 //                               step, adds base[s] and drops slots at or beyond cap.  Lane 0 writes the head.
 //
@@ -108,11 +108,7 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_shard_docs_kernel(ShardD
         const u64 before = __shfl(incl - c, (int)s);       // ranks of the shards in front of s
         const u32 first = __shfl(a, (int)s);
         const u32 count = __shfl(c, (int)s);
-        u32 examined = count;
-        if (g.budget) {
-            const u64 left = g.budget > before ? g.budget - before : 0;
-            if (left < count) examined = (u32)left;
-        }
+        const u32 examined = tq_budget_share(g.budget, before, count);
         const u64 row = (u64)s * g.Q + i;
         const u32 distinct = tq_docs_walk(g.tab[s], g.dtab[s], first, examined, g.cap, g.docs + row * g.cap, g.offsets + row * g.cap, lane);
         if (lane == 0) {
@@ -154,8 +150,8 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_shard_docs_merge_kernel(
         const u64 di_incl = wave_scan_incl(di, ScanSum{});
         const u64 slot0 = di_incl - di;                    // this shard's first slot
         const u64 distinct = __shfl(di_incl, WAVE - 1);
-        const u64 examined = __shfl(wave_scan_incl(ex, ScanSum{}), WAVE - 1);
-        const u64 count = __shfl(wave_scan_incl(ct, ScanSum{}), WAVE - 1);
+        const u64 examined = wave_reduce(ex, ScanSum{});
+        const u64 count = wave_reduce(ct, ScanSum{});
         for (u32 s = 0; s < g.S; ++s) {
             const u64 at = __shfl(slot0, (int)s);
             if (at >= g.cap) break;                        // (wave-uniform; the first slots are non-decreasing in s)
@@ -194,17 +190,13 @@ inline int launch_shard_locate(hipStream_t stream, const ShardLocateArgs& g) {
 
 // Q >= 1 contexts of a chunk; the caller has zeroed g.streamed on the stream
 inline int launch_shard_docs(hipStream_t stream, const ShardDocsArgs& g) {
-    const u64 wave_grid = (g.Q * g.S + NEXT_WAVES - 1) / NEXT_WAVES;
-    const u32 grid = (u32)(wave_grid < 256u * 16u ? wave_grid : 256u * 16u);
-    hipLaunchKernelGGL(tq_shard_docs_kernel, dim3(grid), dim3(NEXT_WAVES * WAVE), 0, stream, g);
+    hipLaunchKernelGGL(tq_shard_docs_kernel, dim3(wave_row_grid(g.Q * g.S)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 inline int launch_shard_docs_merge(hipStream_t stream, const ShardDocsMergeArgs& g) {
-    const u64 wave_grid = (g.Q + NEXT_WAVES - 1) / NEXT_WAVES;
-    const u32 grid = (u32)(wave_grid < 256u * 16u ? wave_grid : 256u * 16u);
-    hipLaunchKernelGGL(tq_shard_docs_merge_kernel, dim3(grid), dim3(NEXT_WAVES * WAVE), 0, stream, g);
+    hipLaunchKernelGGL(tq_shard_docs_merge_kernel, dim3(wave_row_grid(g.Q)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -58,8 +58,9 @@ struct ShardMatchArgs {
 
 __global__ __launch_bounds__(BLOCK) void tq_shard_match_kernel(ShardMatchArgs g) {
     const u64 t = (u64)blockIdx.x * BLOCK + threadIdx.x;
-    const u64 j = t / g.S;
-    const u32 s = (u32)(t - j * g.S);
+    const Pair p = tq_pair_of(t, g.S);
+    const u64 j = p.row;
+    const u32 s = p.s;
     if (j >= g.total) return;
     const u64 cell = (u64)s * g.total + j;
     sa_hip_token_span sp{0u, 0u, 0u, 0u};
@@ -93,9 +94,9 @@ __global__ __launch_bounds__(BLOCK) void tq_shard_match_kernel(ShardMatchArgs g)
 }
 
 __global__ __launch_bounds__(BLOCK) void tq_shard_match_span_kernel(ShardMatchArgs g) {
-    const u64 t = (u64)blockIdx.x * BLOCK + threadIdx.x;
-    const u64 j = t / g.S;
-    const u32 s = (u32)(t - j * g.S);
+    const Pair p = tq_pair_of((u64)blockIdx.x * BLOCK + threadIdx.x, g.S);
+    const u64 j = p.row;
+    const u32 s = p.s;
     if (j >= g.total) return;
     const u32* const w = g.ms + j * g.S;
     u64 L = 0;
@@ -109,16 +110,10 @@ __global__ __launch_bounds__(BLOCK) void tq_shard_match_span_kernel(ShardMatchAr
     const View x = g.tab[s];
     if (!outside && x.n != 0) {
         if (L > g.total - j) L = g.total - j;                             // (ms never passes its document: a bound for the loads)
-        const int32_t* P = g.pat + j;
         const sa_hip_token_span mine = g.per[cell];
-        if (L > 0 && w[s] == L && mine.count > 0) {                       // this shard's own search hit at L: its range stands
-            sp.first = mine.first; sp.count = mine.count;
-        } else {
-            const sa_hip_pair_u32 r = tq_range(x, P, L);                  // (L == 0: {0, n_s} without a search)
-            sp.first = r.first; sp.count = r.second;
-        }
-        sp.length = (u32)L;
-        sp.ended = tq_span_ended(x, sp.first, sp.count, L);
+        const bool own = L > 0 && w[s] == L && mine.count > 0;            // this shard's own search hit at L: its range stands
+        const sa_hip_pair_u32 r = own ? sa_hip_pair_u32{mine.first, mine.count} : tq_range(x, g.pat + j, L);
+        sp = tq_span_of(x, r, L);                                         // (L == 0: {0, n_s} without a search)
     }
     g.per[cell] = sp;
 }
@@ -140,10 +135,10 @@ __global__ __launch_bounds__(BLOCK) void tq_shard_match_total_kernel(ShardMatchA
 
 // total >= 1 positions (< 2^31), every pointer on the device, g.ms[total * S]; asynchronous on `stream`
 inline int launch_shard_match(hipStream_t stream, const ShardMatchArgs& g) {
-    const u64 grid = (g.total * g.S + BLOCK - 1) / BLOCK;
-    if (grid > 0x7FFFFFFFull) return fail(SA_HIP_EINVAL, "sa_hip_token_shards_match_batch", "too many positions for one launch");
-    hipLaunchKernelGGL(tq_shard_match_kernel, dim3((u32)grid), dim3(BLOCK), 0, stream, g);
-    hipLaunchKernelGGL(tq_shard_match_span_kernel, dim3((u32)grid), dim3(BLOCK), 0, stream, g);
+    const u32 grid = shard_pair_grid(g.total, g.S, "sa_hip_token_shards_match_batch", "too many positions for one launch");
+    if (!grid) return SA_HIP_EINVAL;
+    hipLaunchKernelGGL(tq_shard_match_kernel, dim3(grid), dim3(BLOCK), 0, stream, g);
+    hipLaunchKernelGGL(tq_shard_match_span_kernel, dim3(grid), dim3(BLOCK), 0, stream, g);
     hipLaunchKernelGGL(tq_shard_match_total_kernel, dim3((u32)((g.total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;

@@ -43,7 +43,7 @@
 //                                 deterministic), the shards with a token_count counted, scores[j] written.
 //   tq_shard_score_docs_kernel    tq_score_docs_kernel's shape over the 24-byte record: one wave per document, NEXT_WAVES per
 //                                 workgroup, windows of 64 records held as three pairs of words per lane, the next window's load in
-//                                 flight, one wave_scan_incl per field, lane 0 writes the head.
+//                                 flight, one wave_reduce per field, lane 0 writes the head.
 //
 // merged == nullptr ("way 2") is the same three launches with every position that the capped context misses taking the search over
 // L: an independent path to the same bytes.
@@ -87,8 +87,9 @@ struct ShardScoreArgs {
 
 __global__ __launch_bounds__(BLOCK) void tq_shard_score_probe_kernel(ShardScoreArgs g) {
     const u64 t = (u64)blockIdx.x * BLOCK + threadIdx.x;
-    const u64 j = t / g.S;
-    const u32 s = (u32)(t - j * g.S);
+    const Pair p = tq_pair_of(t, g.S);
+    const u64 j = p.row;
+    const u32 s = p.s;
     if (j >= g.total) return;
     const u64 pairs = g.total * g.S;
     u32* const w0 = g.w;
@@ -128,8 +129,9 @@ __global__ __launch_bounds__(BLOCK) void tq_shard_score_probe_kernel(ShardScoreA
 
 __global__ __launch_bounds__(BLOCK) void tq_shard_score_narrow_kernel(ShardScoreArgs g) {
     const u64 t = (u64)blockIdx.x * BLOCK + threadIdx.x;
-    const u64 j = t / g.S;
-    const u32 s = (u32)(t - j * g.S);
+    const Pair p = tq_pair_of(t, g.S);
+    const u64 j = p.row;
+    const u32 s = p.s;
     if (j >= g.total) return;
     const u64 pairs = g.total * g.S;
     const u32* const w0 = g.w + j * g.S;
@@ -250,10 +252,10 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_shard_score_docs_kernel(
                 if (length > longest) longest = length;
             }
         }
-        length_sum = __shfl(wave_scan_incl(length_sum, ScanSum{}), WAVE - 1);
-        seen = __shfl(wave_scan_incl(seen, ScanSum{}), WAVE - 1);
-        certain = __shfl(wave_scan_incl(certain, ScanSum{}), WAVE - 1);
-        longest = __shfl(wave_scan_incl(longest, ScanMax{}), WAVE - 1);
+        length_sum = wave_reduce(length_sum, ScanSum{});
+        seen = wave_reduce(seen, ScanSum{});
+        certain = wave_reduce(certain, ScanSum{});
+        longest = wave_reduce(longest, ScanMax{});
         if (lane == 0) {
             sa_hip_token_score_head h;
             const u64 scored = o1 - o0;
@@ -271,10 +273,10 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_shard_score_docs_kernel(
 
 // total >= 1 positions (< 2^31), every pointer on the device, g.w[3 * total * S]; asynchronous on `stream`
 inline int launch_shard_score(hipStream_t stream, const ShardScoreArgs& g) {
-    const u64 grid = (g.total * g.S + BLOCK - 1) / BLOCK;
-    if (grid > 0x7FFFFFFFull) return fail(SA_HIP_EINVAL, "sa_hip_token_shards_score_batch", "too many positions for one launch");
-    hipLaunchKernelGGL(tq_shard_score_probe_kernel, dim3((u32)grid), dim3(BLOCK), 0, stream, g);
-    hipLaunchKernelGGL(tq_shard_score_narrow_kernel, dim3((u32)grid), dim3(BLOCK), 0, stream, g);
+    const u32 grid = shard_pair_grid(g.total, g.S, "sa_hip_token_shards_score_batch", "too many positions for one launch");
+    if (!grid) return SA_HIP_EINVAL;
+    hipLaunchKernelGGL(tq_shard_score_probe_kernel, dim3(grid), dim3(BLOCK), 0, stream, g);
+    hipLaunchKernelGGL(tq_shard_score_narrow_kernel, dim3(grid), dim3(BLOCK), 0, stream, g);
     hipLaunchKernelGGL(tq_shard_score_total_kernel, dim3((u32)((g.total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
@@ -282,9 +284,7 @@ inline int launch_shard_score(hipStream_t stream, const ShardScoreArgs& g) {
 
 // Q >= 1 documents; every pointer on the device; asynchronous on `stream`
 inline int launch_shard_score_docs(hipStream_t stream, const ShardScoreDocsArgs& g) {
-    const u64 wave_grid = (g.Q + NEXT_WAVES - 1) / NEXT_WAVES;
-    const u32 grid = (u32)(wave_grid < 256u * 16u ? wave_grid : 256u * 16u);
-    hipLaunchKernelGGL(tq_shard_score_docs_kernel, dim3(grid), dim3(NEXT_WAVES * WAVE), 0, stream, g);
+    hipLaunchKernelGGL(tq_shard_score_docs_kernel, dim3(wave_row_grid(g.Q)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -13,8 +13,8 @@
 //                           searches at the L found (mode 0: at the context's length).  <= SPAN_PROBES * S + S range searches.
 //   tq_next_merge_kernel    one wave per context, lane s holds the cursor into shard s's list (hence S <= 64).  A step: wave-wide
 //                           minimum of the head symbols, wave-wide u64 sum of the counts of the lanes that hold it, those lanes
-//                           advance, lane 0 writes the entry.  <= cap steps, no LDS.  Both reductions are wave_scan_incl of
-//                           scan.hpp read at lane 63.  An idle lane (s >= S, or its list exhausted) carries the key 2^64 - 1; a
+//                           advance, lane 0 writes the entry.  <= cap steps, no LDS.  Both reductions are wave_reduce of
+//                           scan.hpp.  An idle lane (s >= S, or its list exhausted) carries the key 2^64 - 1; a
 //                           symbol's key is its value with the sign bit flipped, < 2^32: symbol 2^31 - 1 cannot collide.
 //
 // The per-shard next symbols are tq_next_kernel as it is: launch_next of every shard on its slice of the spans.
@@ -30,15 +30,28 @@ namespace tq {
 
 constexpr u32 SHARDS_MAX = 64;         // one lane of the merge's wave per shard
 
+// a pair index t = row * S + s: the S shards of a row are neighbours; the caller tests the row against its count
+struct Pair { u64 row; u32 s; };
+__device__ __forceinline__ Pair tq_pair_of(u64 t, u32 S) {
+    const u64 row = t / S;
+    return Pair{row, (u32)(t - row * S)};
+}
+
+// a shard's share (<= count) of a budget of ranks, `before` of them in the shards in front; budget == 0: no budget
+__device__ __forceinline__ u32 tq_budget_share(u64 budget, u64 before, u32 count) {
+    if (!budget) return count;
+    const u64 left = budget > before ? budget - before : 0;
+    return left < count ? (u32)left : count;
+}
+
 __global__ __launch_bounds__(BLOCK) void tq_shard_range_kernel(const View* __restrict__ tab, u32 S, const int32_t* __restrict__ pat,
                                                                const u64* __restrict__ off, u64 Q, sa_hip_pair_u32* __restrict__ out) {
-    const u64 t = (u64)blockIdx.x * BLOCK + threadIdx.x;
-    const u64 i = t / S;
-    const u32 s = (u32)(t - i * S);
+    const Pair p = tq_pair_of((u64)blockIdx.x * BLOCK + threadIdx.x, S);
+    const u64 i = p.row;
     if (i >= Q) return;
-    const View x = tab[s];
+    const View x = tab[p.s];
     const u64 o0 = off[i], o1 = off[i + 1];
-    out[(u64)s * Q + i] = tq_range(x, pat + o0, o1 > o0 ? o1 - o0 : 0);
+    out[(u64)p.s * Q + i] = tq_range(x, pat + o0, o1 > o0 ? o1 - o0 : 0);
 }
 
 __global__ __launch_bounds__(BLOCK) void tq_shard_total_kernel(const sa_hip_pair_u32* __restrict__ per, u32 S, u64 Q, u64* __restrict__ totals) {
@@ -47,17 +60,6 @@ __global__ __launch_bounds__(BLOCK) void tq_shard_total_kernel(const sa_hip_pair
     u64 sum = 0;
     for (u32 s = 0; s < S; ++s) sum += per[(u64)s * Q + i].second;
     totals[i] = sum;
-}
-
-// the mode-0 span of P[0 .. m) in one shard, as tq_span_kernel writes it (an empty shard answers {0, 0, 0, 0})
-__device__ __forceinline__ sa_hip_token_span tq_span_exact(const View& x, const int32_t* __restrict__ P, u64 m) {
-    sa_hip_token_span s{0u, 0u, 0u, 0u};
-    if (x.n == 0) return s;
-    const sa_hip_pair_u32 r = tq_range(x, P, m);
-    s.first = r.first; s.count = r.second;
-    s.length = m > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)m;
-    s.ended = tq_span_ended(x, r.first, r.second, m);
-    return s;
 }
 
 // max_n: the longest shard (no more symbols than that match anywhere)
@@ -133,17 +135,17 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_next_merge_kernel(MergeA
             ct += row * g.cap;
             if (g.spans) len = g.spans[(u64)lane * g.span_stride + i].length;
         }
-        const u64 total = __shfl(wave_scan_incl(tot, ScanSum{}), WAVE - 1);
-        const u32 length = __shfl(wave_scan_incl(len, ScanMax{}), WAVE - 1);
+        const u64 total = wave_reduce(tot, ScanSum{});
+        const u32 length = wave_reduce(len, ScanMax{});
         u32 pos = 0, written = 0;
         u64 covered = 0;
         for (u32 step = 0; step < g.cap; ++step) {
             const bool has = pos < end;
             const u64 key = has ? (u64)((u32)sy[pos] ^ 0x80000000u) : MERGE_IDLE;
-            const u64 mn = ~__shfl(wave_scan_incl(~key, ScanMax{}), WAVE - 1);      // the smallest key of the wave
+            const u64 mn = ~wave_reduce(~key, ScanMax{});                           // the smallest key of the wave
             if (mn == MERGE_IDLE) break;                                            // (wave-uniform) every list is exhausted
             const bool hit = key == mn;
-            const u64 sum = __shfl(wave_scan_incl(hit ? (u64)ct[pos] : 0ull, ScanSum{}), WAVE - 1);
+            const u64 sum = wave_reduce(hit ? (u64)ct[pos] : 0ull, ScanSum{});
             if (lane == 0) {
                 g.out_sym[i * g.cap + step] = (int32_t)((u32)mn ^ 0x80000000u);
                 g.out_cnt[i * g.cap + step] = sum;
@@ -175,12 +177,18 @@ inline u64 shard_chunk(u64 knob, u32 S, u32 cap, u64 Q) {
     return c < Q ? c : Q;
 }
 
+// the workgroups of one lane per (row, shard) pair, rows >= 1; beyond 2^31 - 1: 0, and the error is set under the caller's name
+inline u32 shard_pair_grid(u64 rows, u32 S, const char* who, const char* too_many) {
+    const u64 g = (rows * S + BLOCK - 1) / BLOCK;
+    return g > 0x7FFFFFFFull ? (u32)(fail(SA_HIP_EINVAL, who, too_many), 0) : (u32)g;
+}
+
 // Q >= 1 patterns, every pointer on the device, per[S * Q]; asynchronous on `stream`
 inline int launch_shard_ranges(const View* tab, u32 S, hipStream_t stream, const int32_t* pat, const u64* off, u64 Q, u64* totals,
                                sa_hip_pair_u32* per) {
-    const u64 grid = (Q * S + BLOCK - 1) / BLOCK;
-    if (grid > 0x7FFFFFFFull) return fail(SA_HIP_EINVAL, "sa_hip_token_shards_query_batch", "too many patterns for one launch");
-    hipLaunchKernelGGL(tq_shard_range_kernel, dim3((u32)grid), dim3(BLOCK), 0, stream, tab, S, pat, off, Q, per);
+    const u32 grid = shard_pair_grid(Q, S, "sa_hip_token_shards_query_batch", "too many patterns for one launch");
+    if (!grid) return SA_HIP_EINVAL;
+    hipLaunchKernelGGL(tq_shard_range_kernel, dim3(grid), dim3(BLOCK), 0, stream, tab, S, pat, off, Q, per);
     hipLaunchKernelGGL(tq_shard_total_kernel, dim3((u32)((Q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, (const sa_hip_pair_u32*)per, S, Q, totals);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
@@ -197,9 +205,7 @@ inline int launch_shard_spans(const View* tab, u32 S, u32 max_n, hipStream_t str
 }
 
 inline int launch_merge(hipStream_t stream, const MergeArgs& g) {
-    const u64 wave_grid = (g.Q + NEXT_WAVES - 1) / NEXT_WAVES;
-    const u32 grid = (u32)(wave_grid < 256u * 16u ? wave_grid : 256u * 16u);
-    hipLaunchKernelGGL(tq_next_merge_kernel, dim3(grid), dim3(NEXT_WAVES * WAVE), 0, stream, g);
+    hipLaunchKernelGGL(tq_next_merge_kernel, dim3(wave_row_grid(g.Q)), dim3(NEXT_WAVES * WAVE), 0, stream, g);
     SA_HIP_CHECK(hipGetLastError());
     return 0;
 }
