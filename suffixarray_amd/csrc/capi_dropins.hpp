@@ -57,15 +57,6 @@ struct OneShot {
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
-// A build over the text in idx's own buffer (the caller holds idx->mu): the handle has no index while it runs or after it failed.
-int rebuild(sa_hip_index* idx, u64 n, u32 L) {
-    idx->has_index = false;
-    idx->widen_ms = 0.0;
-    const int rc = idx->b.build(n, L);
-    idx->has_index = (rc == 0);
-    return rc;
-}
-
 // One host drop-in call.  Holds g_oneshot.mu from construction to return.  The breakdown's phases (workspace, upload, build,
 // download) are closed one after the other with phase(); commit() ends the call on its success path and is the only place that
 // writes g_oneshot.last -- a call that fails, or that is served by the opt-in host path, leaves the last breakdown alone.

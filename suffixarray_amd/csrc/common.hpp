@@ -43,6 +43,11 @@ inline int fail(int code, const char* what, const char* detail = nullptr) {
 
 __host__ __device__ inline u32 div_up(u64 a, u64 b) { return (u32)((a + b - 1) / b); }
 
+// how many hits an SA range holds; a miss is second = first - 1, or both UINT32_MAX
+__host__ __device__ __forceinline__ u32 hits_of_range(const sa_hip_pair_u32 rg) {
+    return (rg.first != 0xFFFFFFFFu && (u32)(rg.second - rg.first + 1u) != 0u) ? rg.second - rg.first + 1u : 0u;
+}
+
 // smallest b with 2^b >= count
 inline int bits_for(u64 count) {
     int b = 0;

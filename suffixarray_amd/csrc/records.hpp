@@ -27,7 +27,7 @@ template <class Fetch>
 inline int distinct_rows(const HostU64Array& row_starts, sa_hip_pair_u32 range, u32 k, const u32* first_hits, u32 n_first,
                          Fetch&& fetch, std::vector<u64>& rows) {
     rows.clear();
-    if (k == 0 || row_starts.empty() || range.first == 0xFFFFFFFFu || (u32)(range.second - range.first + 1u) == 0u) return 0;
+    if (k == 0 || row_starts.empty() || hits_of_range(range) == 0) return 0;
     const u64 end = (u64)range.second + 1;
     u64 pos = range.first;
     std::unordered_set<u64> seen;

@@ -76,10 +76,6 @@ __device__ __forceinline__ u32 row_of_pos(const RowsArgs& a, const u64 pos) {
     return (u32)(lo - 1);
 }
 
-__device__ __forceinline__ u32 hits_of_range(const sa_hip_pair_u32 rg) {   // miss: second = first - 1, or both UINT32_MAX
-    return (rg.first != 0xFFFFFFFFu && (u32)(rg.second - rg.first + 1u) != 0u) ? rg.second - rg.first + 1u : 0u;
-}
-
 // One lane per query: ranges of <= ROWS_LANE_MAX hits are answered completely (distinct rows in first-hit order, at most k),
 // the others are appended to pending[] (their out_counts entry is written by rows_kernel).
 // pending[0 .. q) collects the ranges for the wave form (use_wave: k <= ROWS_WAVE_K_MAX), pending[q .. 2q) those for the workgroup form

@@ -9,6 +9,7 @@
 // capi_token_shard_all.hpp (included at the end): the token index, its documents, per-document counts and AND groups, matching
 // statistics, and sets of token indexes with their matching statistics, infinity-gram scores, documents, per-document counts and
 // AND groups.
+#include <array>
 #include <exception>
 #include <mutex>
 #include <new>
@@ -33,6 +34,27 @@
 
 using namespace sa;
 
+// The mapped pinned block of the per-call paths (sa_hip_index_query_hits, _query_rows, a small sa_hip_query_batch) as one side sees
+// it, host or device.  One query: [0,8) range, [8,12) hit count, [64, 64 + 4*MAX_HITS) hits or rows, 16 bytes of offsets {0, len},
+// the pattern up to BYTES - 64 (zero padded).  A small batch lays its ranges, offsets and patterns over the same bytes.
+struct QueryBlock {
+    static constexpr u32 MAX_HITS = 4096;
+    static constexpr size_t BYTES = 64 * 1024, OFF_HITS = 64, OFF_OFFSETS = OFF_HITS + 4 * MAX_HITS, OFF_PATTERN = OFF_OFFSETS + 64;
+    static constexpr u64 MAX_PATTERN = BYTES - 64 - OFF_PATTERN;
+    static constexpr u64 SMALL_Q = 448, SMALL_BYTES = 16384;
+    static constexpr size_t SB_OUT = 0, SB_OFF = 4096, SB_PAT = 8192;
+    static_assert(SMALL_Q * 8 <= SB_OFF && (SMALL_Q + 1) * 8 <= SB_PAT - SB_OFF && SB_PAT + SMALL_BYTES + 64 <= BYTES, "small-batch layout");
+    u8* base = nullptr;
+    sa_hip_pair_u32* range() const { return reinterpret_cast<sa_hip_pair_u32*>(base); }
+    u32* nhits() const { return reinterpret_cast<u32*>(base + 8); }
+    u32* hits() const { return reinterpret_cast<u32*>(base + OFF_HITS); }
+    u64* offsets() const { return reinterpret_cast<u64*>(base + OFF_OFFSETS); }
+    u8* pattern() const { return base + OFF_PATTERN; }
+    sa_hip_pair_u32* sb_out() const { return reinterpret_cast<sa_hip_pair_u32*>(base + SB_OUT); }
+    u64* sb_off() const { return reinterpret_cast<u64*>(base + SB_OFF); }
+    u8* sb_pat() const { return base + SB_PAT; }
+};
+
 struct sa_hip_index {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -42,8 +64,7 @@ struct sa_hip_index {
     // query staging (host-pointer API)
     DevBuf q_pat, q_off, q_out;
     DevBuf widen;
-    u8* qh_host = nullptr;   // pinned, device-mapped block of sa_hip_index_query_hits (QH_BYTES)
-    u8* qh_dev = nullptr;    // the same block as the device sees it
+    QueryBlock qh_host, qh_dev;   // the pinned, device-mapped block (made on first use: query_block) and the same block as the device sees it
     // HIP events of the last QRING search launches: a pipelined caller (distributed.py: search chunk k+1 while chunk k is
     // gathered) asks for the statistics once per step, and every launch since the previous call is resolved then
     static constexpr int QRING = 32;
@@ -68,6 +89,14 @@ struct sa_hip_index {
     sa_hip_replica_layout pending{};
     lcp::Workspace lcp_ws;         // sa_hip_index_[p]lcp_device (lcp.hpp)
     bwt::Workspace bwt_ws;         // sa_hip_index_bwt_device (bwt.hpp)
+    auto buffers() {               // every DevBuf member above (b and the two workspaces release their own)
+        return std::array{&q_pat, &q_off, &q_out, &widen, &rows_dev, &rows_coarse, &r_rows, &r_counts, &r_pending, &qc_hist, &qc_off, &qc_part, &qc_tmp};
+    }
+    auto events() {                // every event above
+        std::array<hipEvent_t*, 2 * QRING + 2> e{&w_begin, &w_end};
+        for (int i = 0; i < 2 * QRING; ++i) e[2 + i] = &q_ev[i / 2][i % 2];
+        return e;
+    }
 };
 
 // multi-GPU lifecycle (comm_rccl.hpp): one communicator per process / GPU
@@ -93,6 +122,56 @@ namespace {
 
 int set_device(int device) {
     SA_HIP_CHECK(hipSetDevice(device));
+    return 0;
+}
+
+// One call on an index handle: what nearly every entry point below opens with, as steps.  An entry point takes the steps it needs
+// in ITS order -- which refusal wins when two apply is part of the interface and differs between entry points -- and keeps its
+// own checks (NULL outputs, ranges, an empty batch) between them.  The helpers that run under a lock already held (*_locked) take
+// the steps without lock().
+// Every step returns 0 or the error code, which stays in `rc`: if (c.lock() || c.device_form() || c.has_index()) return c.rc;
+struct IndexCall {   // (not copyable: the lock)
+    sa_hip_index* const idx;
+    const char* const who;
+    std::unique_lock<std::mutex> held;
+    int rc = 0;
+
+    IndexCall(sa_hip_index* idx, const char* who) : idx(idx), who(who) {}
+    // refuses a NULL handle -- together with the NULL arguments of an entry point that names them in one text -- then locks
+    int lock(const char* null_text = "NULL index", bool args = true) {
+        if (!idx || !args) return rc = fail(SA_HIP_EINVAL, who, null_text);
+        held = std::unique_lock<std::mutex>(idx->mu);
+        return 0;
+    }
+    int device_form() { return rc = idx->host ? fail(SA_HIP_EHIP, who, "the host path (no HIP device) has no device buffers") : 0; }
+    int has_index() { return rc = idx->has_index ? 0 : fail(SA_HIP_EINVAL, who, "no index"); }
+    int current() { return rc = set_device(idx->device); }
+};
+
+// A build over the text in idx's own buffer (the caller holds idx->mu): the handle has no index while it runs or after it failed.
+int rebuild(sa_hip_index* idx, u64 n, u32 L, int64_t* sa64_dev = nullptr) {
+    idx->has_index = false;
+    idx->widen_ms = 0.0;
+    const int rc = idx->b.build(n, L, sa64_dev);
+    idx->has_index = (rc == 0);
+    return rc;
+}
+
+// idx->b.sa[first .. first + count) or the text, to the host (the caller holds idx->mu and has checked the index and `out`)
+int copy_to_host(IndexCall& c, void* out, const void* src_dev, size_t bytes) {
+    if (c.current()) return c.rc;
+    if (bytes) SA_HIP_CHECK(hipMemcpyAsync(out, src_dev, bytes, hipMemcpyDeviceToHost, c.idx->stream));
+    SA_HIP_CHECK(hipStreamSynchronize(c.idx->stream));
+    return 0;
+}
+
+// an SA entry >= n would send the query kernel's text reads out of bounds: counts them into *bad_host, which is valid after the
+// stream's next synchronisation
+int check_sa_entries(sa_hip_index* idx, const u32* sa, u64 n, u64* bad_host) {
+    u64* bad = reinterpret_cast<u64*>(idx->b.small.as<u8>() + 3072);
+    SA_HIP_CHECK(hipMemsetAsync(bad, 0, 8, idx->stream));
+    hipLaunchKernelGGL(sa_range_check_kernel, dim3(stream_grid(n, 1024)), dim3(256), 0, idx->stream, sa, n, bad);
+    SA_HIP_CHECK(hipMemcpyAsync(bad_host, bad, 8, hipMemcpyDeviceToHost, idx->stream));
     return 0;
 }
 
@@ -155,80 +234,157 @@ QueryArgs query_args(sa_hip_index* idx, const u8* pat_dev, const u64* off_dev, u
     return a;
 }
 
-int launch_query(sa_hip_index* idx, const u8* pat_dev, const u64* off_dev, u64 Q, sa_hip_pair_u32* out_dev, u64 fixed_len = 0) {
-    if (idx->q_pending == sa_hip_index::QRING) { int rc = resolve_query_events(idx, 1); if (rc) return rc; }
-    hipEvent_t* ev = idx->q_ev[idx->q_head];
-    if (Q >= K2_AUTO_BATCH && idx->k2_auto) { int rc = ensure_k2(idx); if (rc) return rc; }
-    QueryArgs a = query_args(idx, pat_dev, off_dev, Q, out_dev, fixed_len);
-    // a large batch over a wide-key index is answered in the order of its patterns' first characters (qcluster_*): the buffers
-    // first (no memory: the plain order), the three small passes inside the timed region
-    // (from 2^20 patterns on: its ten small launches cost ~0.11 ms -- 1e6 names 0.324 vs 0.331 ms, 8e6 names 1.75 vs 2.40 ms;
-    //  SA_HIP_QCLUSTER_MIN lowers the threshold for the tests, SA_HIP_QCLUSTER=0 switches it off; both under SA_HIP_DIAG=1 only)
+// The search's switches (under SA_HIP_DIAG=1 only), read once at the top of every launch: the tests flip them on a live handle.
+// SA_HIP_QCLUSTER_MIN lowers the clustering threshold for the tests, SA_HIP_QCLUSTER=0 switches the clustering off.
+struct QuerySwitches {
     u64 cluster_min = 1ull << 20;
-    if (const char* e = diag_env("SA_HIP_QCLUSTER_MIN")) cluster_min = strtoull(e, nullptr, 10);
-    if (const char* e = diag_env("SA_HIP_QCLUSTER")) { if (atoi(e) == 0) cluster_min = ~0ull; }
-    bool cluster = Q >= cluster_min && Q >= QC_TILE && Q < 0xFFFFFFFFull && a.keys && idx->k2_auto;
-    const u32 qtiles = (u32)((Q + QC_TILE - 1) / QC_TILE);
-    const u64 hlen = (u64)QC_BINS * qtiles, nparts = (hlen + big::SC_TILE - 1) / big::SC_TILE;
-    if (cluster && (idx->qc_hist.ensure(hlen * 4 + 64) || idx->qc_off.ensure(hlen * 8 + 64) || idx->qc_part.ensure((nparts + 1) * 8 + 64) ||
-                    idx->qc_tmp.ensure((size_t)Q * 16 + 64))) cluster = false;
-    SA_HIP_CHECK(hipEventRecord(ev[0], idx->stream));
-    if (cluster) {
-        u32* qkey = idx->qc_tmp.as<u32>();
-        u32* tmp = qkey + Q;
-        u32* perm0 = tmp + Q;
-        u32* perm1 = perm0 + Q;
-        const u32 g = stream_grid(Q, 256);
-        for (int pass = 0; pass < 2; ++pass) {
-            const u32* order = pass ? perm0 : nullptr;
-            hipLaunchKernelGGL(qcluster_rank_kernel, dim3(qtiles), dim3(256), 0, idx->stream, a, idx->b.qmap, pass, order, qkey, tmp, idx->qc_hist.as<u32>(), qtiles);
-            hipLaunchKernelGGL(big::bg_scan_reduce_kernel, dim3((u32)nparts), dim3(big::SC_BLOCK), 0, idx->stream, (const u32*)idx->qc_hist.as<u32>(), hlen,
-                               idx->qc_part.as<u64>());
-            hipLaunchKernelGGL(big::bg_scan_parts_kernel, dim3(1), dim3(big::SC_BLOCK), 0, idx->stream, idx->qc_part.as<u64>(), nparts);
-            hipLaunchKernelGGL(big::bg_scan_apply_kernel, dim3((u32)nparts), dim3(big::SC_BLOCK), 0, idx->stream, (const u32*)idx->qc_hist.as<u32>(), hlen,
-                               (const u64*)idx->qc_part.as<u64>(), idx->qc_off.as<u64>());
-            hipLaunchKernelGGL(qcluster_place_kernel, dim3(g), dim3(256), 0, idx->stream, Q, (const u64*)idx->qc_off.as<u64>(), (const u32*)tmp, order, qtiles,
-                               pass ? perm1 : perm0);
-        }
-        a.perm = perm1;
+    QuerySwitches() {
+        if (const char* e = diag_env("SA_HIP_QCLUSTER_MIN")) cluster_min = strtoull(e, nullptr, 10);
+        if (const char* e = diag_env("SA_HIP_QCLUSTER")) { if (atoi(e) == 0) cluster_min = ~0ull; }
     }
-    if (Q) {
-        u64 g = (Q + 255) / 256;
-        if (g > 256u * 16u) g = 256u * 16u;
-        const dim3 grid((u32)g), block(256);
-        if (a.keys32) {
-            if (a.sector_search == 2) hipLaunchKernelGGL((query_kernel<true, 2>), grid, block, 0, idx->stream, a, idx->b.qmap);
-            else if (a.sector_search == 1) hipLaunchKernelGGL((query_kernel<true, 1>), grid, block, 0, idx->stream, a, idx->b.qmap);
-            else hipLaunchKernelGGL((query_kernel<true, 0>), grid, block, 0, idx->stream, a, idx->b.qmap);
-        } else {
-            if (a.sector_search == 2) hipLaunchKernelGGL((query_kernel<false, 2>), grid, block, 0, idx->stream, a, idx->b.qmap);
-            else if (a.sector_search == 1) hipLaunchKernelGGL((query_kernel<false, 1>), grid, block, 0, idx->stream, a, idx->b.qmap);
-            else hipLaunchKernelGGL((query_kernel<false, 0>), grid, block, 0, idx->stream, a, idx->b.qmap);
-        }
+};
+
+// A large batch over a wide-key index is answered in the order of its patterns' first characters (qcluster_*).
+// (from 2^20 patterns on: its ten small launches cost ~0.11 ms -- 1e6 names 0.324 vs 0.331 ms, 8e6 names 1.75 vs 2.40 ms)
+struct ClusterShape {
+    u32 qtiles;
+    u64 hlen, nparts;
+    explicit ClusterShape(u64 Q) : qtiles((u32)((Q + QC_TILE - 1) / QC_TILE)), hlen((u64)QC_BINS * qtiles), nparts((hlen + big::SC_TILE - 1) / big::SC_TILE) {}
+};
+
+// whether this batch is clustered, with the buffers for it (no memory: the plain order); before the launch's timed region
+bool cluster_buffers(sa_hip_index* idx, const QuerySwitches& sw, const QueryArgs& a) {
+    const u64 Q = a.q, cluster_min = sw.cluster_min;
+    const bool cluster = Q >= cluster_min && Q >= QC_TILE && Q < 0xFFFFFFFFull && a.keys && idx->k2_auto;
+    const ClusterShape s(Q);
+    return cluster && !(idx->qc_hist.ensure(s.hlen * 4 + 64) || idx->qc_off.ensure(s.hlen * 8 + 64) || idx->qc_part.ensure((s.nparts + 1) * 8 + 64) ||
+             idx->qc_tmp.ensure((size_t)Q * 16 + 64));
+}
+
+// the two passes of five small launches each, inside the timed region; returns the permutation
+const u32* cluster_batch(sa_hip_index* idx, const QueryArgs& a) {
+    const u64 Q = a.q;
+    const ClusterShape s(Q);
+    u32* qkey = idx->qc_tmp.as<u32>();
+    u32* tmp = qkey + Q;
+    u32* perm0 = tmp + Q;
+    u32* perm1 = perm0 + Q;
+    const u32 g = stream_grid(Q, 256);
+    for (int pass = 0; pass < 2; ++pass) {
+        const u32* order = pass ? perm0 : nullptr;
+        hipLaunchKernelGGL(qcluster_rank_kernel, dim3(s.qtiles), dim3(256), 0, idx->stream, a, idx->b.qmap, pass, order, qkey, tmp, idx->qc_hist.as<u32>(), s.qtiles);
+        hipLaunchKernelGGL(big::bg_scan_reduce_kernel, dim3((u32)s.nparts), dim3(big::SC_BLOCK), 0, idx->stream, (const u32*)idx->qc_hist.as<u32>(), s.hlen,
+                           idx->qc_part.as<u64>());
+        hipLaunchKernelGGL(big::bg_scan_parts_kernel, dim3(1), dim3(big::SC_BLOCK), 0, idx->stream, idx->qc_part.as<u64>(), s.nparts);
+        hipLaunchKernelGGL(big::bg_scan_apply_kernel, dim3((u32)s.nparts), dim3(big::SC_BLOCK), 0, idx->stream, (const u32*)idx->qc_hist.as<u32>(), s.hlen,
+                           (const u64*)idx->qc_part.as<u64>(), idx->qc_off.as<u64>());
+        hipLaunchKernelGGL(qcluster_place_kernel, dim3(g), dim3(256), 0, idx->stream, Q, (const u64*)idx->qc_off.as<u64>(), (const u32*)tmp, order, s.qtiles,
+                           pass ? perm1 : perm0);
     }
-    SA_HIP_CHECK(hipEventRecord(ev[1], idx->stream));
-    SA_HIP_CHECK(hipGetLastError());
+    return perm1;
+}
+
+// query_kernel<NARROW, SECTOR>: wide keys or narrow ones, the index's sector form (anything but 1 and 2: the plain bisection)
+void launch_query_kernel(sa_hip_index* idx, const QueryArgs& a) {
+    using Kernel = void (*)(QueryArgs, CodeMap);
+    static constexpr Kernel form[2][3] = {{query_kernel<false, 0>, query_kernel<false, 1>, query_kernel<false, 2>},
+                                          {query_kernel<true, 0>, query_kernel<true, 1>, query_kernel<true, 2>}};
+    if (!a.q) return;
+    u64 g = (a.q + 255) / 256;
+    if (g > 256u * 16u) g = 256u * 16u;
+    const int sector = (a.sector_search == 1 || a.sector_search == 2) ? a.sector_search : 0;
+    hipLaunchKernelGGL(form[a.keys32 ? 1 : 0][sector], dim3((u32)g), dim3(256), 0, idx->stream, a, idx->b.qmap);
+}
+
+// the event ring: the slot of the next launch (the oldest pending launch is resolved first when all are taken) ...
+int claim_query_slot(sa_hip_index* idx, hipEvent_t** ev) {
+    if (idx->q_pending == sa_hip_index::QRING) { int rc = resolve_query_events(idx, 1); if (rc) return rc; }
+    *ev = idx->q_ev[idx->q_head];
+    return 0;
+}
+// ... and the launch entered into it
+void advance_query_slot(sa_hip_index* idx, u64 Q) {
     idx->q_head = (idx->q_head + 1) % sa_hip_index::QRING;
     ++idx->q_pending;
     ++idx->q_launches;
     idx->qstats.q = Q;   // the times are resolved lazily by sa_hip_index_query_stats
+}
+
+int launch_query(sa_hip_index* idx, const u8* pat_dev, const u64* off_dev, u64 Q, sa_hip_pair_u32* out_dev, u64 fixed_len = 0) {
+    const QuerySwitches sw;
+    hipEvent_t* ev;
+    if (int rc = claim_query_slot(idx, &ev)) return rc;
+    if (Q >= K2_AUTO_BATCH && idx->k2_auto) { int rc = ensure_k2(idx); if (rc) return rc; }
+    QueryArgs a = query_args(idx, pat_dev, off_dev, Q, out_dev, fixed_len);
+    const bool cluster = cluster_buffers(idx, sw, a);
+    SA_HIP_CHECK(hipEventRecord(ev[0], idx->stream));
+    if (cluster) a.perm = cluster_batch(idx, a);
+    launch_query_kernel(idx, a);
+    SA_HIP_CHECK(hipEventRecord(ev[1], idx->stream));
+    SA_HIP_CHECK(hipGetLastError());
+    advance_query_slot(idx, Q);
     return 0;
 }
 
-// pinned block of sa_hip_index_query_hits: [0,8) range, [8,12) nhits, [64, 64 + 4*QH_MAX_HITS) hits,
-// [QH_OFF_OFFSETS, +16) offsets {0, len}, [QH_OFF_PATTERN, QH_BYTES - 64) pattern (zero padded)
-constexpr u32 QH_MAX_HITS = 4096;
-constexpr size_t QH_OFF_HITS = 64, QH_OFF_OFFSETS = QH_OFF_HITS + 4 * QH_MAX_HITS, QH_OFF_PATTERN = QH_OFF_OFFSETS + 64;
-constexpr size_t QH_BYTES = 64 * 1024;
+// the pinned block, made on first use (the caller holds idx->mu and has set the device)
+int query_block(sa_hip_index* idx) {
+    if (idx->qh_host.base) return 0;
+    SA_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&idx->qh_host.base), QueryBlock::BYTES, hipHostMallocMapped));
+    SA_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&idx->qh_dev.base), idx->qh_host.base, 0));
+    return 0;
+}
+
+// ONE pattern for the per-call paths: the bound the block sets on it, checked where the entry point checks its arguments ...
+int one_pattern_fits(const char* who, u64 len) {
+    return len > QueryBlock::MAX_PATTERN ? fail(SA_HIP_EINVAL, who, "pattern longer than 47 KB") : 0;
+}
+// ... and the pattern staged in the block: offsets {0, len}, the pattern, 64 zero bytes
+int stage_one_pattern(sa_hip_index* idx, const u8* pattern, u64 len) {
+    int rc = query_block(idx);
+    if (rc) return rc;
+    const QueryBlock& h = idx->qh_host;
+    h.offsets()[0] = 0; h.offsets()[1] = len;
+    if (len) memcpy(h.pattern(), pattern, len);
+    memset(h.pattern() + len, 0, 64);
+    return 0;
+}
+// QueryArgs of that one pattern, its range into the block
+QueryArgs one_pattern_args(sa_hip_index* idx) {
+    const QueryBlock& d = idx->qh_dev;
+    return query_args(idx, d.pattern(), d.offsets(), 1, d.range(), 0);
+}
+
+// A host batch in q_pat / q_off (q_out sized for its ranges): patterns, offsets, the 64-byte pad, through the ring of pinned slabs
+// when given one (host_io.hpp), by plain copies otherwise
+int stage_batch(sa_hip_index* idx, PinnedRing* ring, const u8* patterns, const u64* offsets, u64 Q) {
+    const u64 total = offsets[Q];
+    int rc;
+    if ((rc = idx->q_pat.ensure((size_t)total + 64))) return rc;
+    if ((rc = idx->q_off.ensure((size_t)(Q + 1) * 8))) return rc;
+    if ((rc = idx->q_out.ensure((size_t)Q * sizeof(sa_hip_pair_u32)))) return rc;
+    if (ring) {
+        if ((rc = ring_upload(*ring, idx->stream, idx->device, idx->q_pat.p, patterns, (size_t)total))) return rc;
+        if ((rc = ring_upload(*ring, idx->stream, idx->device, idx->q_off.p, reinterpret_cast<const u8*>(offsets), (size_t)(Q + 1) * 8))) return rc;
+    } else {
+        if (total) SA_HIP_CHECK(hipMemcpyAsync(idx->q_pat.p, patterns, total, hipMemcpyHostToDevice, idx->stream));
+        SA_HIP_CHECK(hipMemcpyAsync(idx->q_off.p, offsets, (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, idx->stream));
+    }
+    SA_HIP_CHECK(hipMemsetAsync(idx->q_pat.as<u8>() + total, 0, 64, idx->stream));
+    return 0;
+}
+
+// the first hits of a range into hits[], their number into *nhits (one workgroup)
+__device__ __forceinline__ void copy_hits(const u32* __restrict__ sa, const sa_hip_pair_u32 rg, const u32 max_hits, u32* __restrict__ hits,
+                                          u32* __restrict__ nhits) {
+    u32 count = hits_of_range(rg);
+    if (count > max_hits) count = max_hits;
+    for (u32 i = threadIdx.x; i < count; i += blockDim.x) hits[i] = sa[(u64)rg.first + i];
+    if (threadIdx.x == 0) *nhits = count;
+}
 
 __global__ __launch_bounds__(256) void hits_copy_kernel(const u32* __restrict__ sa, const sa_hip_pair_u32* __restrict__ range,
                                                         u32 max_hits, u32* __restrict__ hits, u32* __restrict__ nhits) {
-    const u32 first = range->first, second = range->second;
-    u32 count = 0;
-    if (first != 0xFFFFFFFFu && ((second - first + 1u) != 0u)) count = second - first + 1u;   // miss: second = first - 1
-    if (count > max_hits) count = max_hits;
-    for (u32 i = threadIdx.x; i < count; i += blockDim.x) hits[i] = sa[(u64)first + i];
-    if (threadIdx.x == 0) *nhits = count;
+    copy_hits(sa, *range, max_hits, hits, nhits);
 }
 
 // ONE query + its first hits in one launch (sa_hip_index_query_hits, sa_hip_get_substring_positions[_file]): thread 0 searches,
@@ -246,12 +402,7 @@ __global__ __launch_bounds__(256) void query_hits_one_kernel(QueryArgs qa, CodeM
         s_rg = rg;
     }
     __syncthreads();
-    const u32 first = s_rg.first, second = s_rg.second;
-    u32 count = 0;
-    if (first != 0xFFFFFFFFu && ((second - first + 1u) != 0u)) count = second - first + 1u;   // miss: second = first - 1
-    if (count > max_hits) count = max_hits;
-    for (u32 i = threadIdx.x; i < count; i += blockDim.x) hits[i] = sa[(u64)first + i];
-    if (threadIdx.x == 0) *nhits = count;
+    copy_hits(sa, s_rg, max_hits, hits, nhits);
 }
 
 }  // namespace
@@ -298,12 +449,8 @@ int sa_hip_index_create(sa_hip_index** out, uint64_t n_max, int device) {
     hipError_t e = hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete idx; return fail(SA_HIP_EHIP, "hipStreamCreate", hipGetErrorString(e)); }
     rc = idx->b.init(n_max, idx->stream);
-    if (!rc) {
-        bool ok = hipEventCreate(&idx->w_begin) == hipSuccess && hipEventCreate(&idx->w_end) == hipSuccess;
-        for (int i = 0; ok && i < sa_hip_index::QRING; ++i)
-            ok = hipEventCreate(&idx->q_ev[i][0]) == hipSuccess && hipEventCreate(&idx->q_ev[i][1]) == hipSuccess;
-        if (!ok) rc = fail(SA_HIP_EHIP, "hipEventCreate");
-    }
+    for (hipEvent_t* ev : idx->events())
+        if (!rc && hipEventCreate(ev) != hipSuccess) rc = fail(SA_HIP_EHIP, "hipEventCreate");
     if (rc) { sa_hip_index_destroy(idx); return rc; }
     *out = idx;
     return 0;
@@ -315,78 +462,55 @@ void sa_hip_index_destroy(sa_hip_index* idx) {
     (void)hipSetDevice(idx->device);
     if (idx->stream) (void)hipStreamSynchronize(idx->stream);
     idx->b.destroy();
-    idx->q_pat.release(); idx->q_off.release(); idx->q_out.release(); idx->widen.release();
-    idx->rows_dev.release(); idx->rows_coarse.release(); idx->r_rows.release(); idx->r_counts.release(); idx->r_pending.release();
-    idx->qc_hist.release(); idx->qc_off.release(); idx->qc_part.release(); idx->qc_tmp.release();
+    for (DevBuf* b : idx->buffers()) b->release();
     idx->lcp_ws.release();
     idx->bwt_ws.release();
-    if (idx->qh_host) (void)hipHostFree(idx->qh_host);
-    for (int i = 0; i < sa_hip_index::QRING; ++i)
-        for (int k = 0; k < 2; ++k) if (idx->q_ev[i][k]) (void)hipEventDestroy(idx->q_ev[i][k]);
-    if (idx->w_begin) (void)hipEventDestroy(idx->w_begin);
-    if (idx->w_end) (void)hipEventDestroy(idx->w_end);
+    if (idx->qh_host.base) (void)hipHostFree(idx->qh_host.base);
+    for (hipEvent_t* ev : idx->events()) if (*ev) (void)hipEventDestroy(*ev);
     if (idx->stream) (void)hipStreamDestroy(idx->stream);
     delete idx;
 }
 
+// the device leg of the three builds: the text into the handle's own buffer (unless it is that buffer), then the build
+static int build_from(IndexCall& c, const void* T, uint64_t n, uint32_t L, hipMemcpyKind kind, void* sa64_dev = nullptr) {
+    sa_hip_index* idx = c.idx;
+    if (c.current()) return c.rc;
+    if (n > idx->b.n_max) return fail(SA_HIP_EINVAL, c.who, "n exceeds the index capacity");
+    if (n && T != idx->b.text.p) SA_HIP_CHECK(hipMemcpyAsync(idx->b.text.p, T, n, kind, idx->stream));
+    return rebuild(idx, n, L, static_cast<int64_t*>(sa64_dev));
+}
+
 int sa_hip_index_build(sa_hip_index* idx, const uint8_t* T_host, uint64_t n, uint32_t max_suffix_length) {
-    if (!idx || (!T_host && n)) return fail(SA_HIP_EINVAL, "sa_hip_index_build: NULL argument");
-    std::lock_guard<std::mutex> g(idx->mu);
+    IndexCall c(idx, "sa_hip_index_build");
+    if (c.lock("NULL argument", T_host || !n)) return c.rc;
     if (idx->host) {
         HostIndex& h = *idx->host;
-        if (n > h.n_max) return fail(SA_HIP_EINVAL, "sa_hip_index_build: n exceeds the index capacity");
+        if (n > h.n_max) return fail(SA_HIP_EINVAL, c.who, "n exceeds the index capacity");
         try { h.set_text(T_host, n); h.build(max_suffix_length); }
-        catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, "sa_hip_index_build: out of host memory"); }
+        catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, c.who, "out of host memory"); }
         idx->has_index = true;
         return 0;
     }
-    int rc = set_device(idx->device);
-    if (rc) return rc;
-    if (n > idx->b.n_max) return fail(SA_HIP_EINVAL, "sa_hip_index_build: n exceeds the index capacity");
-    if (n) SA_HIP_CHECK(hipMemcpyAsync(idx->b.text.p, T_host, n, hipMemcpyHostToDevice, idx->stream));
-    idx->has_index = false;
-    idx->widen_ms = 0.0;
-    rc = idx->b.build(n, max_suffix_length);
-    idx->has_index = (rc == 0);
-    return rc;
+    return build_from(c, T_host, n, max_suffix_length, hipMemcpyHostToDevice);
 }
 
 int sa_hip_index_build_device(sa_hip_index* idx, const void* T_dev, uint64_t n, uint32_t max_suffix_length) {
-    if (!idx || (!T_dev && n)) return fail(SA_HIP_EINVAL, "sa_hip_index_build_device: NULL argument");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (idx->host) return fail(SA_HIP_EHIP, "sa_hip_index_build_device: the host path (no HIP device) has no device buffers");
-    int rc = set_device(idx->device);
-    if (rc) return rc;
-    if (n > idx->b.n_max) return fail(SA_HIP_EINVAL, "sa_hip_index_build_device: n exceeds the index capacity");
-    if (n && T_dev != idx->b.text.p)
-        SA_HIP_CHECK(hipMemcpyAsync(idx->b.text.p, T_dev, n, hipMemcpyDeviceToDevice, idx->stream));
-    idx->has_index = false;
-    idx->widen_ms = 0.0;
-    rc = idx->b.build(n, max_suffix_length);
-    idx->has_index = (rc == 0);
-    return rc;
+    IndexCall c(idx, "sa_hip_index_build_device");
+    if (c.lock("NULL argument", T_dev || !n) || c.device_form()) return c.rc;
+    return build_from(c, T_dev, n, max_suffix_length, hipMemcpyDeviceToDevice);
 }
 
 int sa_hip_index_build_device64(sa_hip_index* idx, const void* T_dev, uint64_t n, uint32_t max_suffix_length, void* sa64_dev) {
-    if (!idx || (!T_dev && n) || (!sa64_dev && n)) return fail(SA_HIP_EINVAL, "sa_hip_index_build_device64: NULL argument");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (idx->host) return fail(SA_HIP_EHIP, "sa_hip_index_build_device64: the host path (no HIP device) has no device buffers");
-    int rc = set_device(idx->device);
-    if (rc) return rc;
-    if (n > idx->b.n_max) return fail(SA_HIP_EINVAL, "sa_hip_index_build_device64: n exceeds the index capacity");
-    if (n && T_dev != idx->b.text.p)
-        SA_HIP_CHECK(hipMemcpyAsync(idx->b.text.p, T_dev, n, hipMemcpyDeviceToDevice, idx->stream));
-    idx->has_index = false;
-    idx->widen_ms = 0.0;
-    rc = idx->b.build(n, max_suffix_length, static_cast<int64_t*>(sa64_dev));
-    idx->has_index = (rc == 0);
-    return rc;
+    IndexCall c(idx, "sa_hip_index_build_device64");
+    if (c.lock("NULL argument", (T_dev && sa64_dev) || !n) || c.device_form()) return c.rc;
+    return build_from(c, T_dev, n, max_suffix_length, hipMemcpyDeviceToDevice, sa64_dev);
 }
 
 static int load_common(sa_hip_index* idx, const void* T, const void* SA, uint64_t n, uint32_t L, hipMemcpyKind kind) {
-    std::lock_guard<std::mutex> g(idx->mu);
+    IndexCall c(idx, "sa_hip_index_load_device");
+    c.lock();
     if (idx->host) {
-        if (kind != hipMemcpyHostToDevice) return fail(SA_HIP_EHIP, "sa_hip_index_load_device: the host path (no HIP device) has no device buffers");
+        if (kind != hipMemcpyHostToDevice) return c.device_form();
         HostIndex& h = *idx->host;
         if (n > h.n_max) return fail(SA_HIP_EINVAL, "sa_hip_index_load: n exceeds the index capacity");
         const u32* s32 = static_cast<const u32*>(SA);
@@ -397,7 +521,7 @@ static int load_common(sa_hip_index* idx, const void* T, const void* SA, uint64_
         idx->has_index = true;
         return 0;
     }
-    int rc = set_device(idx->device);
+    int rc = c.current();
     if (rc) return rc;
     if (n > idx->b.n_max) return fail(SA_HIP_EINVAL, "sa_hip_index_load: n exceeds the index capacity");
     Builder& b = idx->b;
@@ -407,13 +531,8 @@ static int load_common(sa_hip_index* idx, const void* T, const void* SA, uint64_
     if (n) {
         SA_HIP_CHECK(hipMemcpyAsync(b.text.p, T, n, kind, idx->stream));
         SA_HIP_CHECK(hipMemcpyAsync(b.sa_own.p, SA, (size_t)n * 4, kind, idx->stream));
-        // an entry >= n would send the query kernel's text reads out of bounds: refuse the array (the copy of the
-        // count rides on the synchronisation prepare_text() does anyway)
-        u64* bad = reinterpret_cast<u64*>(b.small.as<u8>() + 3072);
-        SA_HIP_CHECK(hipMemsetAsync(bad, 0, 8, idx->stream));
-        hipLaunchKernelGGL(sa_range_check_kernel, dim3(stream_grid(n, 1024)), dim3(256), 0, idx->stream,
-                           (const u32*)b.sa_own.p, n, bad);
-        SA_HIP_CHECK(hipMemcpyAsync(&bad_host, bad, 8, hipMemcpyDeviceToHost, idx->stream));
+        // refuse an array with entries >= n (the copy of the count rides on the synchronisation prepare_text() does anyway)
+        if ((rc = check_sa_entries(idx, b.sa_own.as<u32>(), n, &bad_host))) return rc;
     }
     CodeMap map; u32 sigma; int bits;
     if ((rc = b.prepare_text(n, map, sigma, bits))) return rc;
@@ -460,50 +579,43 @@ static void fill_layout(const sa_hip_index* idx, sa_hip_replica_layout* out) {
 }
 
 int sa_hip_index_replica_layout(sa_hip_index* idx, sa_hip_replica_layout* out) {
-    if (!idx || !out) return fail(SA_HIP_EINVAL, "sa_hip_index_replica_layout: NULL argument");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (idx->host) return fail(SA_HIP_EHIP, "sa_hip_index_replica_layout: the host path (no HIP device) has no device buffers");
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_replica_layout: no index");
+    IndexCall c(idx, "sa_hip_index_replica_layout");
+    if (c.lock("NULL argument", out) || c.device_form() || c.has_index()) return c.rc;
     fill_layout(idx, out);
     return 0;
 }
 
-static void fill_buffers(const sa_hip_index* idx, const sa_hip_replica_layout& l, sa_hip_replica_buffers* out) {
+// (keys: the key array of the layout's width -- the index's own, or the one a replica receives into)
+static void fill_buffers(const sa_hip_index* idx, const sa_hip_replica_layout& l, void* keys, sa_hip_replica_buffers* out) {
     const Builder& b = idx->b;
     memset(out, 0, sizeof *out);
     out->text = b.text.p;                       out->text_bytes = l.n;
     out->sa = b.sa;                             out->sa_bytes = l.n * 4;
-    out->keys = l.key_bytes == 4 ? (void*)b.qkeys32 : (void*)b.qkeys;
-    out->keys_bytes = l.n * l.key_bytes;
+    out->keys = keys;                           out->keys_bytes = l.n * l.key_bytes;
     out->dir = l.key_bytes ? b.qdir.p : nullptr; out->dir_bytes = l.dir_entries * 4;
 }
 
 int sa_hip_index_replica_buffers(sa_hip_index* idx, sa_hip_replica_buffers* out) {
-    if (!idx || !out) return fail(SA_HIP_EINVAL, "sa_hip_index_replica_buffers: NULL argument");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (idx->host) return fail(SA_HIP_EHIP, "sa_hip_index_replica_buffers: the host path (no HIP device) has no device buffers");
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_replica_buffers: no index");
-    int rc = set_device(idx->device);
-    if (rc) return rc;
+    IndexCall c(idx, "sa_hip_index_replica_buffers");
+    if (c.lock("NULL argument", out) || c.device_form() || c.has_index() || c.current()) return c.rc;
     SA_HIP_CHECK(hipStreamSynchronize(idx->stream));   // whoever reads the buffers next runs on another stream
     sa_hip_replica_layout l;
     fill_layout(idx, &l);
-    fill_buffers(idx, l, out);
+    fill_buffers(idx, l, l.key_bytes == 4 ? (void*)idx->b.qkeys32 : (void*)idx->b.qkeys, out);
     return 0;
 }
 
 int sa_hip_index_replica_reserve(sa_hip_index* idx, const sa_hip_replica_layout* l, sa_hip_replica_buffers* out) {
-    if (!idx || !l || !out) return fail(SA_HIP_EINVAL, "sa_hip_index_replica_reserve: NULL argument");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (idx->host) return fail(SA_HIP_EHIP, "sa_hip_index_replica_reserve: the host path (no HIP device) has no device buffers");
-    if (l->n > idx->b.n_max) return fail(SA_HIP_EINVAL, "sa_hip_index_replica_reserve: n exceeds the index capacity");
-    if (l->key_bytes != 0 && l->key_bytes != 4 && l->key_bytes != 8) return fail(SA_HIP_EINVAL, "sa_hip_index_replica_reserve: bad key width");
+    IndexCall c(idx, "sa_hip_index_replica_reserve");
+    if (c.lock("NULL argument", l && out) || c.device_form()) return c.rc;
+    if (l->n > idx->b.n_max) return fail(SA_HIP_EINVAL, c.who, "n exceeds the index capacity");
+    if (l->key_bytes != 0 && l->key_bytes != 4 && l->key_bytes != 8) return fail(SA_HIP_EINVAL, c.who, "bad key width");
     if (l->key_bytes && (l->dir_bits < 8 || l->dir_bits > 28 || l->dir_entries != (1ull << l->dir_bits) + 1 || l->bits_per_symbol < 1 ||
                          l->bits_per_symbol > 16 || l->initial_chars < 1 || l->initial_chars * l->bits_per_symbol > 64 ||
                          l->lo_shift < 0 || l->lo_shift > 63))
-        return fail(SA_HIP_EINVAL, "sa_hip_index_replica_reserve: inconsistent layout");
-    int rc = set_device(idx->device);
-    if (rc) return rc;
+        return fail(SA_HIP_EINVAL, c.who, "inconsistent layout");
+    int rc;
+    if (c.current()) return c.rc;
     Builder& b = idx->b;
     idx->has_index = false;
     if ((rc = b.sa_own.ensure((size_t)(l->n ? l->n : 1) * 4))) return rc;
@@ -518,21 +630,16 @@ int sa_hip_index_replica_reserve(sa_hip_index* idx, const sa_hip_replica_layout*
     b.qkeys = nullptr; b.qkeys32 = nullptr; b.dir_ready = false; b.k2_ready = false;
     idx->pending = *l;
     idx->receiving = true;
-    memset(out, 0, sizeof *out);
-    out->text = b.text.p;     out->text_bytes = l->n;
-    out->sa = b.sa_own.p;     out->sa_bytes = l->n * 4;
-    out->keys = l->key_bytes ? b.keys0.p : nullptr; out->keys_bytes = l->n * l->key_bytes;
-    out->dir = l->key_bytes ? b.qdir.p : nullptr;   out->dir_bytes = l->dir_entries * 4;
+    fill_buffers(idx, *l, l->key_bytes ? b.keys0.p : nullptr, out);
     return 0;
 }
 
 int sa_hip_index_replica_commit(sa_hip_index* idx) {
-    if (!idx) return fail(SA_HIP_EINVAL, "sa_hip_index_replica_commit: NULL index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (idx->host) return fail(SA_HIP_EHIP, "sa_hip_index_replica_commit: the host path (no HIP device) has no device buffers");
-    if (!idx->receiving) return fail(SA_HIP_EINVAL, "sa_hip_index_replica_commit: nothing reserved");
-    int rc = set_device(idx->device);
-    if (rc) return rc;
+    IndexCall c(idx, "sa_hip_index_replica_commit");
+    if (c.lock() || c.device_form()) return c.rc;
+    if (!idx->receiving) return fail(SA_HIP_EINVAL, c.who, "nothing reserved");
+    int rc;
+    if (c.current()) return c.rc;
     Builder& b = idx->b;
     const sa_hip_replica_layout& l = idx->pending;
     idx->receiving = false;
@@ -540,10 +647,7 @@ int sa_hip_index_replica_commit(sa_hip_index* idx) {
     u64 bad_host = 0;
     u32 dir_ends[2] = {0, (u32)l.n};
     if (l.n) {
-        u64* bad = reinterpret_cast<u64*>(b.small.as<u8>() + 3072);
-        SA_HIP_CHECK(hipMemsetAsync(bad, 0, 8, idx->stream));
-        hipLaunchKernelGGL(sa_range_check_kernel, dim3(stream_grid(l.n, 1024)), dim3(256), 0, idx->stream, (const u32*)b.sa_own.p, l.n, bad);
-        SA_HIP_CHECK(hipMemcpyAsync(&bad_host, bad, 8, hipMemcpyDeviceToHost, idx->stream));
+        if ((rc = check_sa_entries(idx, b.sa_own.as<u32>(), l.n, &bad_host))) return rc;
         if (l.key_bytes) {
             SA_HIP_CHECK(hipMemcpyAsync(&dir_ends[0], b.qdir.as<u32>(), 4, hipMemcpyDeviceToHost, idx->stream));
             SA_HIP_CHECK(hipMemcpyAsync(&dir_ends[1], b.qdir.as<u32>() + (l.dir_entries - 1), 4, hipMemcpyDeviceToHost, idx->stream));
@@ -681,11 +785,10 @@ const void* sa_hip_index_sa_dev(const sa_hip_index* idx) { return (idx && idx->h
 void* sa_hip_index_stream(const sa_hip_index* idx) { return idx ? (void*)idx->stream : nullptr; }
 
 int sa_hip_index_deep_keys(sa_hip_index* idx, int mode) {
-    if (!idx || mode < 0 || mode > 2) return fail(SA_HIP_EINVAL, "sa_hip_index_deep_keys: invalid arguments");
+    IndexCall c(idx, "sa_hip_index_deep_keys");
+    if (!idx || mode < 0 || mode > 2) return fail(SA_HIP_EINVAL, c.who, "invalid arguments");
     if (idx->host) return 0;
-    std::lock_guard<std::mutex> lock(idx->mu);
-    int rc = set_device(idx->device);
-    if (rc) return rc;
+    if (c.lock() || c.current()) return c.rc;
     if (mode == 0) {   // never: drop them (8 n bytes back), large batches do not build them
         SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
         idx->k2_auto = false;
@@ -696,8 +799,7 @@ int sa_hip_index_deep_keys(sa_hip_index* idx, int mode) {
     }
     idx->k2_auto = true;
     if (mode == 2) {
-        if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_deep_keys: no index");
-        if ((rc = ensure_k2(idx))) return rc;
+        if (c.has_index() || (c.rc = ensure_k2(idx))) return c.rc;
         SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
     }
     return idx->b.k2_ready ? 1 : 0;
@@ -713,36 +815,28 @@ int sa_hip_index_sync(sa_hip_index* idx) {
 }
 
 int sa_hip_index_verify(sa_hip_index* idx, uint64_t* violations) {
-    if (!idx || !violations) return fail(SA_HIP_EINVAL, "sa_hip_index_verify: NULL argument");
-    std::lock_guard<std::mutex> g(idx->mu);   // has_index / n are only read under the lock (a concurrent build rewrites them)
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_verify: no index");
+    IndexCall c(idx, "sa_hip_index_verify");
+    if (c.lock("NULL argument", violations) || c.has_index()) return c.rc;   // has_index / n are only read under the lock (a concurrent build rewrites them)
     if (idx->host) { *violations = idx->host->verify(); return 0; }
-    int rc = set_device(idx->device);
-    if (rc) return rc;
+    if (c.current()) return c.rc;
     return idx->b.verify(violations);
 }
 
 int sa_hip_index_get_sa_u32(sa_hip_index* idx, uint32_t* out_host) {
-    if (!idx) return fail(SA_HIP_EINVAL, "sa_hip_index_get_sa_u32: NULL index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_get_sa_u32: no index");
-    if (!out_host && sa_hip_index_n(idx)) return fail(SA_HIP_EINVAL, "sa_hip_index_get_sa_u32: NULL output");
+    IndexCall c(idx, "sa_hip_index_get_sa_u32");
+    if (c.lock() || c.has_index()) return c.rc;
+    if (!out_host && sa_hip_index_n(idx)) return fail(SA_HIP_EINVAL, c.who, "NULL output");
     if (idx->host) { if (idx->host->n) memcpy(out_host, idx->host->sa.data(), (size_t)idx->host->n * 4); return 0; }
-    int rc = set_device(idx->device);
-    if (rc) return rc;
-    if (idx->b.n) SA_HIP_CHECK(hipMemcpyAsync(out_host, idx->b.sa, (size_t)idx->b.n * 4, hipMemcpyDeviceToHost, idx->stream));
-    SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
-    return 0;
+    return copy_to_host(c, out_host, idx->b.sa, (size_t)idx->b.n * 4);
 }
 
 int sa_hip_index_get_sa_i64(sa_hip_index* idx, int64_t* out_host) {
-    if (!idx) return fail(SA_HIP_EINVAL, "sa_hip_index_get_sa_i64: NULL index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_get_sa_i64: no index");
-    if (!out_host && sa_hip_index_n(idx)) return fail(SA_HIP_EINVAL, "sa_hip_index_get_sa_i64: NULL output");
+    IndexCall c(idx, "sa_hip_index_get_sa_i64");
+    if (c.lock() || c.has_index()) return c.rc;
+    if (!out_host && sa_hip_index_n(idx)) return fail(SA_HIP_EINVAL, c.who, "NULL output");
     if (idx->host) { for (u64 i = 0; i < idx->host->n; ++i) out_host[i] = (int64_t)idx->host->sa[i]; return 0; }
-    int rc = set_device(idx->device);
-    if (rc) return rc;
+    int rc;
+    if (c.current()) return c.rc;
     const u64 n = idx->b.n;
     if (n) {
         // widen on the device in slabs (libsais64.c:6248-6259 does this on the CPU, in place)
@@ -760,14 +854,11 @@ int sa_hip_index_get_sa_i64(sa_hip_index* idx, int64_t* out_host) {
 }
 
 int sa_hip_index_widen_device(sa_hip_index* idx, void* out_dev) {
-    if (!idx) return fail(SA_HIP_EINVAL, "sa_hip_index_widen_device: NULL index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (idx->host) return fail(SA_HIP_EHIP, "sa_hip_index_widen_device: the host path (no HIP device) has no device buffers");
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_widen_device: no index");
+    IndexCall c(idx, "sa_hip_index_widen_device");
+    if (c.lock() || c.device_form() || c.has_index()) return c.rc;
     const u64 n = idx->b.n;
-    if (!out_dev && n) return fail(SA_HIP_EINVAL, "sa_hip_index_widen_device: NULL output");
-    int rc = set_device(idx->device);
-    if (rc) return rc;
+    if (!out_dev && n) return fail(SA_HIP_EINVAL, c.who, "NULL output");
+    if (c.current()) return c.rc;
     SA_HIP_CHECK(hipEventRecord(idx->w_begin, idx->stream));
     if (n) hipLaunchKernelGGL(widen_kernel, dim3(stream_grid(n / 4 + 1, 256)), dim3(256), 0, idx->stream, (const u32*)idx->b.sa, n,
                               static_cast<int64_t*>(out_dev));
@@ -778,23 +869,20 @@ int sa_hip_index_widen_device(sa_hip_index* idx, void* out_dev) {
 }
 
 // (idx->mu held)
-static int get_sa_range_locked(sa_hip_index* idx, uint64_t first, uint64_t count, uint32_t* out_host) {
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_get_sa_range: no index");
-    const u64 n_idx = idx->host ? idx->host->n : idx->b.n;
-    if (first > n_idx || count > n_idx - first) return fail(SA_HIP_EINVAL, "sa_hip_index_get_sa_range: out of range");
-    if (!out_host && count) return fail(SA_HIP_EINVAL, "sa_hip_index_get_sa_range: NULL output");
+static int get_sa_range_locked(IndexCall& c, uint64_t first, uint64_t count, uint32_t* out_host) {
+    sa_hip_index* idx = c.idx;
+    if (c.has_index()) return c.rc;
+    const u64 n_idx = sa_hip_index_n(idx);
+    if (first > n_idx || count > n_idx - first) return fail(SA_HIP_EINVAL, c.who, "out of range");
+    if (!out_host && count) return fail(SA_HIP_EINVAL, c.who, "NULL output");
     if (idx->host) { if (count) memcpy(out_host, idx->host->sa.data() + first, (size_t)count * 4); return 0; }
-    int rc = set_device(idx->device);
-    if (rc) return rc;
-    if (count) SA_HIP_CHECK(hipMemcpyAsync(out_host, idx->b.sa + first, (size_t)count * 4, hipMemcpyDeviceToHost, idx->stream));
-    SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
-    return 0;
+    return copy_to_host(c, out_host, idx->b.sa + first, (size_t)count * 4);
 }
 
 int sa_hip_index_get_sa_range(sa_hip_index* idx, uint64_t first, uint64_t count, uint32_t* out_host) {
-    if (!idx) return fail(SA_HIP_EINVAL, "sa_hip_index_get_sa_range: NULL index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    return get_sa_range_locked(idx, first, count, out_host);
+    IndexCall c(idx, "sa_hip_index_get_sa_range");
+    if (c.lock()) return c.rc;
+    return get_sa_range_locked(c, first, count, out_host);
 }
 
 int sa_hip_index_get_freq(sa_hip_index* idx, uint64_t* freq256) {
@@ -805,45 +893,32 @@ int sa_hip_index_get_freq(sa_hip_index* idx, uint64_t* freq256) {
 
 int sa_hip_query_batch(sa_hip_index* idx, const uint8_t* patterns, const uint64_t* offsets, uint64_t Q,
                        sa_hip_pair_u32* out) {
-    if (!idx) return fail(SA_HIP_EINVAL, "sa_hip_query_batch: NULL index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_query_batch: no index");
+    IndexCall c(idx, "sa_hip_query_batch");
+    if (c.lock() || c.has_index()) return c.rc;
     if (Q == 0) return 0;
-    if (!offsets || !out) return fail(SA_HIP_EINVAL, "sa_hip_query_batch: NULL argument");
+    if (!offsets || !out) return fail(SA_HIP_EINVAL, c.who, "NULL argument");
     const u64 total = offsets[Q];
-    if (!patterns && total) return fail(SA_HIP_EINVAL, "sa_hip_query_batch: NULL patterns");
+    if (!patterns && total) return fail(SA_HIP_EINVAL, c.who, "NULL patterns");
     if (idx->host) {
         for (u64 i = 0; i < Q; ++i) out[i] = idx->host->query(patterns + offsets[i], offsets[i + 1] - offsets[i]);
         return 0;
     }
-    int rc = set_device(idx->device);
-    if (rc) return rc;
+    int rc;
+    if (c.current()) return c.rc;
     // a small batch (a handful of patterns: what a caller of the single-query interfaces sends) goes through the mapped pinned block
     // -- no staged copies, one launch, one synchronisation: 55 -> ~28 us for one pattern
-    constexpr u64 SMALL_Q = 448, SMALL_BYTES = 16384;
-    constexpr size_t SB_OUT = 0, SB_OFF = 4096, SB_PAT = 8192;
-    static_assert(SMALL_Q * 8 <= SB_OFF && (SMALL_Q + 1) * 8 <= SB_PAT - SB_OFF && SB_PAT + SMALL_BYTES + 64 <= QH_BYTES, "small-batch layout");
-    if (Q <= SMALL_Q && total <= SMALL_BYTES) {
-        if (!idx->qh_host) {
-            SA_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&idx->qh_host), QH_BYTES, hipHostMallocMapped));
-            SA_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&idx->qh_dev), idx->qh_host, 0));
-        }
-        u8* h = idx->qh_host;
-        u8* d = idx->qh_dev;
-        memcpy(h + SB_OFF, offsets, (size_t)(Q + 1) * 8);
-        if (total) memcpy(h + SB_PAT, patterns, (size_t)total);
-        memset(h + SB_PAT + total, 0, 64);
-        if ((rc = launch_query(idx, d + SB_PAT, reinterpret_cast<const u64*>(d + SB_OFF), Q, reinterpret_cast<sa_hip_pair_u32*>(d + SB_OUT)))) return rc;
+    if (Q <= QueryBlock::SMALL_Q && total <= QueryBlock::SMALL_BYTES) {
+        if ((rc = query_block(idx))) return rc;
+        const QueryBlock &h = idx->qh_host, &d = idx->qh_dev;
+        memcpy(h.sb_off(), offsets, (size_t)(Q + 1) * 8);
+        if (total) memcpy(h.sb_pat(), patterns, (size_t)total);
+        memset(h.sb_pat() + total, 0, 64);
+        if ((rc = launch_query(idx, d.sb_pat(), d.sb_off(), Q, d.sb_out()))) return rc;
         SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
-        memcpy(out, h + SB_OUT, (size_t)Q * sizeof(sa_hip_pair_u32));
+        memcpy(out, h.sb_out(), (size_t)Q * sizeof(sa_hip_pair_u32));
         return 0;
     }
-    if ((rc = idx->q_pat.ensure((size_t)total + 64))) return rc;
-    if ((rc = idx->q_off.ensure((size_t)(Q + 1) * 8))) return rc;
-    if ((rc = idx->q_out.ensure((size_t)Q * sizeof(sa_hip_pair_u32)))) return rc;
-    if (total) SA_HIP_CHECK(hipMemcpyAsync(idx->q_pat.p, patterns, total, hipMemcpyHostToDevice, idx->stream));
-    SA_HIP_CHECK(hipMemsetAsync(idx->q_pat.as<u8>() + total, 0, 64, idx->stream));
-    SA_HIP_CHECK(hipMemcpyAsync(idx->q_off.p, offsets, (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, idx->stream));
+    if ((rc = stage_batch(idx, nullptr, patterns, offsets, Q))) return rc;
     if ((rc = launch_query(idx, idx->q_pat.as<u8>(), idx->q_off.as<u64>(), Q, idx->q_out.as<sa_hip_pair_u32>()))) return rc;
     SA_HIP_CHECK(hipMemcpyAsync(out, idx->q_out.p, (size_t)Q * sizeof(sa_hip_pair_u32), hipMemcpyDeviceToHost, idx->stream));
     SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
@@ -853,93 +928,74 @@ int sa_hip_query_batch(sa_hip_index* idx, const uint8_t* patterns, const uint64_
 // (idx->mu held)
 static int query_hits_locked(sa_hip_index* idx, const uint8_t* pattern, uint64_t len, uint32_t max_hits,
                              sa_hip_pair_u32* range, uint32_t* hits, uint32_t* nhits) {
-    if (!range || !nhits || (!pattern && len) || (!hits && max_hits)) return fail(SA_HIP_EINVAL, "sa_hip_index_query_hits: NULL argument");
-    if (len > QH_BYTES - 64 - QH_OFF_PATTERN) return fail(SA_HIP_EINVAL, "sa_hip_index_query_hits: pattern longer than 47 KB");
-    if (max_hits > QH_MAX_HITS) max_hits = QH_MAX_HITS;
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_query_hits: no index");
+    IndexCall c(idx, "sa_hip_index_query_hits");
+    int rc;
+    if (!range || !nhits || (!pattern && len) || (!hits && max_hits)) return fail(SA_HIP_EINVAL, c.who, "NULL argument");
+    if ((rc = one_pattern_fits(c.who, len))) return rc;
+    if (max_hits > QueryBlock::MAX_HITS) max_hits = QueryBlock::MAX_HITS;
+    if (c.has_index()) return c.rc;
     if (idx->host) {
         const HostIndex& h = *idx->host;
         *range = h.query(pattern, len);
-        u32 count = 0;
-        if (range->first != 0xFFFFFFFFu && (u32)(range->second - range->first + 1u) != 0u) count = range->second - range->first + 1u;
-        if (count > max_hits) count = max_hits;
+        const u32 count = std::min(hits_of_range(*range), max_hits);
         for (u32 i = 0; i < count; ++i) hits[i] = h.sa[(u64)range->first + i];
         *nhits = count;
         return 0;
     }
-    int rc = set_device(idx->device);
-    if (rc) return rc;
-    if (!idx->qh_host) {
-        SA_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&idx->qh_host), QH_BYTES, hipHostMallocMapped));
-        SA_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&idx->qh_dev), idx->qh_host, 0));
-    }
-    u8* h = idx->qh_host;
-    u8* d = idx->qh_dev;
-    const u64 off[2] = {0, len};
-    memcpy(h + QH_OFF_OFFSETS, off, sizeof off);
-    if (len) memcpy(h + QH_OFF_PATTERN, pattern, len);
-    memset(h + QH_OFF_PATTERN + len, 0, 64);
+    if (c.current() || (c.rc = stage_one_pattern(idx, pattern, len))) return c.rc;
+    const QueryBlock &h = idx->qh_host, &d = idx->qh_dev;
     if (idx->b.sector_search == 2) {   // the product configuration: one launch
-        const QueryArgs qa = query_args(idx, d + QH_OFF_PATTERN, reinterpret_cast<const u64*>(d + QH_OFF_OFFSETS), 1, reinterpret_cast<sa_hip_pair_u32*>(d), 0);
+        const QueryArgs qa = one_pattern_args(idx);
         if (qa.keys32) hipLaunchKernelGGL(query_hits_one_kernel<true>, dim3(1), dim3(256), 0, idx->stream, qa, idx->b.qmap, (const u32*)idx->b.sa,
-                                          max_hits, reinterpret_cast<u32*>(d + QH_OFF_HITS), reinterpret_cast<u32*>(d + 8));
+                                          max_hits, d.hits(), d.nhits());
         else hipLaunchKernelGGL(query_hits_one_kernel<false>, dim3(1), dim3(256), 0, idx->stream, qa, idx->b.qmap, (const u32*)idx->b.sa,
-                                max_hits, reinterpret_cast<u32*>(d + QH_OFF_HITS), reinterpret_cast<u32*>(d + 8));
+                                max_hits, d.hits(), d.nhits());
     } else {
-        if ((rc = launch_query(idx, d + QH_OFF_PATTERN, reinterpret_cast<const u64*>(d + QH_OFF_OFFSETS), 1,
-                               reinterpret_cast<sa_hip_pair_u32*>(d)))) return rc;
-        hipLaunchKernelGGL(hits_copy_kernel, dim3(1), dim3(256), 0, idx->stream, (const u32*)idx->b.sa,
-                           reinterpret_cast<const sa_hip_pair_u32*>(d), max_hits, reinterpret_cast<u32*>(d + QH_OFF_HITS),
-                           reinterpret_cast<u32*>(d + 8));
+        if ((rc = launch_query(idx, d.pattern(), d.offsets(), 1, d.range()))) return rc;
+        hipLaunchKernelGGL(hits_copy_kernel, dim3(1), dim3(256), 0, idx->stream, (const u32*)idx->b.sa, (const sa_hip_pair_u32*)d.range(), max_hits,
+                           d.hits(), d.nhits());
     }
     SA_HIP_CHECK(hipGetLastError());
     SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
-    memcpy(range, h, sizeof *range);
-    memcpy(nhits, h + 8, 4);
-    if (*nhits) memcpy(hits, h + QH_OFF_HITS, (size_t)*nhits * 4);
+    *range = *h.range();
+    *nhits = *h.nhits();
+    if (*nhits) memcpy(hits, h.hits(), (size_t)*nhits * 4);
     return 0;
 }
 
 int sa_hip_index_query_hits(sa_hip_index* idx, const uint8_t* pattern, uint64_t len, uint32_t max_hits,
                             sa_hip_pair_u32* range, uint32_t* hits, uint32_t* nhits) {
-    if (!idx) return fail(SA_HIP_EINVAL, "sa_hip_index_query_hits: NULL index");
-    std::lock_guard<std::mutex> g(idx->mu);
+    IndexCall c(idx, "sa_hip_index_query_hits");
+    if (c.lock()) return c.rc;
     return query_hits_locked(idx, pattern, len, max_hits, range, hits, nhits);
 }
 
 int sa_hip_query_batch_device(sa_hip_index* idx, const void* patterns_dev, const void* offsets_dev, uint64_t Q,
                               void* out_dev) {
-    if (!idx) return fail(SA_HIP_EINVAL, "sa_hip_query_batch_device: NULL index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (idx->host) return fail(SA_HIP_EHIP, "sa_hip_query_batch_device: the host path (no HIP device) has no device buffers");
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_query_batch_device: no index");
+    IndexCall c(idx, "sa_hip_query_batch_device");
+    if (c.lock() || c.device_form() || c.has_index()) return c.rc;
     if (Q == 0) return 0;
-    if (!patterns_dev || !offsets_dev || !out_dev) return fail(SA_HIP_EINVAL, "sa_hip_query_batch_device: NULL argument");
-    int rc = set_device(idx->device);
-    if (rc) return rc;
+    if (!patterns_dev || !offsets_dev || !out_dev) return fail(SA_HIP_EINVAL, c.who, "NULL argument");
+    if (c.current()) return c.rc;
     return launch_query(idx, (const u8*)patterns_dev, (const u64*)offsets_dev, Q, (sa_hip_pair_u32*)out_dev);
 }
 
 int sa_hip_query_batch_device_fixed(sa_hip_index* idx, const void* patterns_dev, uint64_t pattern_len, uint64_t Q, void* out_dev) {
-    if (!idx) return fail(SA_HIP_EINVAL, "sa_hip_query_batch_device_fixed: NULL index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (idx->host) return fail(SA_HIP_EHIP, "sa_hip_query_batch_device_fixed: the host path (no HIP device) has no device buffers");
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_query_batch_device_fixed: no index");
+    IndexCall c(idx, "sa_hip_query_batch_device_fixed");
+    if (c.lock() || c.device_form() || c.has_index()) return c.rc;
     if (Q == 0) return 0;
-    if ((!patterns_dev && pattern_len) || !out_dev) return fail(SA_HIP_EINVAL, "sa_hip_query_batch_device_fixed: NULL argument");
-    int rc = set_device(idx->device);
-    if (rc) return rc;
+    if ((!patterns_dev && pattern_len) || !out_dev) return fail(SA_HIP_EINVAL, c.who, "NULL argument");
+    if (c.current()) return c.rc;
     return launch_query(idx, (const u8*)patterns_dev, nullptr, Q, (sa_hip_pair_u32*)out_dev, pattern_len);
 }
 
 int sa_hip_index_build_stats(const sa_hip_index* idx_c, sa_hip_build_stats* out) {
     sa_hip_index* idx = const_cast<sa_hip_index*>(idx_c);
-    if (!idx || !out) return fail(SA_HIP_EINVAL, "sa_hip_index_build_stats: NULL argument");
-    std::lock_guard<std::mutex> g(idx->mu);
+    IndexCall c(idx, "sa_hip_index_build_stats");
+    if (c.lock("NULL argument", out)) return c.rc;
     if (idx->host) { memset(out, 0, sizeof *out); out->n = idx->host->n; return 0; }
     if (idx->widen_ms < 0.0) {
-        int rc = set_device(idx->device);
-        if (rc) return rc;
+        if (c.current()) return c.rc;
         SA_HIP_CHECK(hipEventSynchronize(idx->w_end));
         float ms = 0.f;
         SA_HIP_CHECK(hipEventElapsedTime(&ms, idx->w_begin, idx->w_end));
@@ -952,12 +1008,10 @@ int sa_hip_index_build_stats(const sa_hip_index* idx_c, sa_hip_build_stats* out)
 
 int sa_hip_index_query_stats(const sa_hip_index* idx_c, sa_hip_query_stats* out) {
     sa_hip_index* idx = const_cast<sa_hip_index*>(idx_c);
-    if (!idx || !out) return fail(SA_HIP_EINVAL, "sa_hip_index_query_stats: NULL argument");
-    std::lock_guard<std::mutex> g(idx->mu);
+    IndexCall c(idx, "sa_hip_index_query_stats");
+    if (c.lock("NULL argument", out)) return c.rc;
     if (idx->host) { memset(out, 0, sizeof *out); return 0; }
-    int rc = set_device(idx->device);
-    if (rc) return rc;
-    if ((rc = resolve_query_events(idx, sa_hip_index::QRING))) return rc;
+    if (c.current() || (c.rc = resolve_query_events(idx, sa_hip_index::QRING))) return c.rc;
     idx->qstats.kernel_ms = idx->q_last_ms;
     idx->qstats.kernel_ms_sum = idx->q_sum_ms;
     idx->qstats.launches = idx->q_launches;
@@ -1011,255 +1065,253 @@ static int set_rows_locked_tail(sa_hip_index* idx) {   // (idx->mu held) the tab
 }
 
 int sa_hip_index_get_text(sa_hip_index* idx, uint8_t* out_host) {
-    if (!idx) return fail(SA_HIP_EINVAL, "sa_hip_index_get_text: NULL index");
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_get_text: no index");
-    if (!out_host && sa_hip_index_n(idx)) return fail(SA_HIP_EINVAL, "sa_hip_index_get_text: NULL output");
+    IndexCall c(idx, "sa_hip_index_get_text");
+    if (c.lock() || c.has_index()) return c.rc;
+    if (!out_host && sa_hip_index_n(idx)) return fail(SA_HIP_EINVAL, c.who, "NULL output");
     if (idx->host) { if (idx->host->n) memcpy(out_host, idx->host->text.data(), (size_t)idx->host->n); return 0; }
-    int rc = set_device(idx->device);
-    if (rc) return rc;
-    if (idx->b.n) SA_HIP_CHECK(hipMemcpyAsync(out_host, idx->b.text.p, (size_t)idx->b.n, hipMemcpyDeviceToHost, idx->stream));
-    SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
-    return 0;
+    return copy_to_host(c, out_host, idx->b.text.p, (size_t)idx->b.n);
 }
 
-// host path of the record retrieval (records.hpp): k beyond ROWS_K_MAX ("all rows"), and SA_HIP_HOST_ROWS=1 (diagnostic:
-// the tests compare the two paths row for row)
+// The record retrieval's switches (under SA_HIP_DIAG=1 only), read once at the top of every call.  SA_HIP_HOST_ROWS=1 sends every
+// k through the host path (records.hpp), which otherwise serves k beyond ROWS_K_MAX ("all rows"): the tests compare the two paths
+// row for row.  (The per-call form reads only that one.)
 static bool host_rows_forced() {
     const char* e = diag_env("SA_HIP_HOST_ROWS");
     return e && atoi(e) != 0;
+}
+struct RowsSwitches {
+    static bool is(const char* e, char c) { return e && e[0] == c; }
+    static u32 groups(const char* e) { const int v = e ? atoi(e) : 0; return v >= 1 && v <= 256 ? (u32)v : 8u; }
+    const bool host_rows = host_rows_forced();
+    const bool waves = !is(diag_env("SA_HIP_ROWS_WAVES"), '0');           // =0: no wave-per-range form (A/B, tests)
+    const u32 wave_groups = groups(diag_env("SA_HIP_ROWS_WAVE_GROUPS"));  // workgroups of the wave form per CU (A/B)
+    const bool lanes = !is(diag_env("SA_HIP_ROWS_LANES"), '0');           // =0: every query through the workgroup form (A/B, tests)
+    const bool trace = is(diag_env("SA_HIP_ROWS_TRACE"), '1');            // =1: one stderr line per large batch, where its time went
+    const bool ring = !is(diag_env("SA_HIP_ROWS_RING"), '0');             // =0: every batch down by plain copies (A/B, tests)
+};
+
+// rows need the table of sa_hip_index_set_rows; more rows than it holds cannot come back (k = 10^9, "all", must not size anything)
+static int rows_table(const sa_hip_index* idx, const char* who, u32* k) {
+    if (*k && idx->row_starts.empty()) return fail(SA_HIP_EINVAL, who, "no row table (sa_hip_index_set_rows)");
+    if ((u64)*k > idx->row_starts.size()) *k = (u32)idx->row_starts.size();
+    return 0;
+}
+
+static RowsArgs rows_args(const sa_hip_index* idx, const sa_hip_pair_u32* ranges, u64 q, u32 k, u32* out_rows, u32* out_counts) {
+    RowsArgs a;
+    a.sa = idx->b.sa; a.ranges = ranges; a.q = q;
+    a.row_starts = idx->rows_dev.as<u64>(); a.num_rows = idx->row_starts.size(); a.k = k;
+    a.coarse = (idx->rows_coarse_n > 1) ? idx->rows_coarse.as<u64>() : nullptr; a.coarse_n = idx->rows_coarse_n;
+    a.out_rows = out_rows; a.out_counts = out_counts;
+    return a;
+}
+
+// (idx->mu held) the distinct rows of a range on the host (records.hpp), the hits beyond first_hits fetched slab by slab
+static int host_rows_of_range(sa_hip_index* idx, const char* who, sa_hip_pair_u32 range, u32 k, const u32* first_hits, u32 n_first,
+                              uint64_t* row_ids, uint32_t* count) {
+    IndexCall sa_of(idx, "sa_hip_index_get_sa_range");
+    try {
+        std::vector<u64> rows;
+        const int rc = distinct_rows(idx->row_starts, range, k, first_hits, n_first,
+                                     [&](u64 pos, u64 n, u32* out) { return get_sa_range_locked(sa_of, pos, n, out); }, rows);
+        if (rc) return rc;
+        for (size_t i = 0; i < rows.size(); ++i) row_ids[i] = rows[i];
+        *count = (uint32_t)rows.size();
+    } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, who, "out of host memory"); }
+    return 0;
 }
 
 // (idx->mu held) ONE query: search + rows kernel through the pinned block, one synchronisation
 static int query_rows_device_locked(sa_hip_index* idx, const uint8_t* pattern, uint64_t len, uint32_t k, uint64_t* row_ids,
                                     uint32_t* num_rows, sa_hip_pair_u32* range) {
-    if (len > QH_BYTES - 64 - QH_OFF_PATTERN) return fail(SA_HIP_EINVAL, "sa_hip_index_query_rows: pattern longer than 47 KB");
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_query_rows: no index");
-    int rc = set_device(idx->device);
-    if (rc) return rc;
-    if (!idx->qh_host) {
-        SA_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&idx->qh_host), QH_BYTES, hipHostMallocMapped));
-        SA_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&idx->qh_dev), idx->qh_host, 0));
-    }
-    u8* h = idx->qh_host;
-    u8* d = idx->qh_dev;
-    const u64 off[2] = {0, len};
-    memcpy(h + QH_OFF_OFFSETS, off, sizeof off);
-    if (len) memcpy(h + QH_OFF_PATTERN, pattern, len);
-    memset(h + QH_OFF_PATTERN + len, 0, 64);
-    RowsArgs a;
-    a.sa = idx->b.sa; a.ranges = reinterpret_cast<const sa_hip_pair_u32*>(d); a.q = 1;
-    a.row_starts = idx->rows_dev.as<u64>(); a.num_rows = idx->row_starts.size(); a.k = k;
-    a.coarse = (idx->rows_coarse_n > 1) ? idx->rows_coarse.as<u64>() : nullptr; a.coarse_n = idx->rows_coarse_n;
-    a.out_rows = reinterpret_cast<u32*>(d + QH_OFF_HITS); a.out_counts = reinterpret_cast<u32*>(d + 8);
+    IndexCall c(idx, "sa_hip_index_query_rows");
+    if ((c.rc = one_pattern_fits(c.who, len)) || c.has_index() || c.current() || (c.rc = stage_one_pattern(idx, pattern, len))) return c.rc;
+    const QueryBlock &h = idx->qh_host, &d = idx->qh_dev;
+    const RowsArgs a = rows_args(idx, d.range(), 1, k, d.hits(), d.nhits());
     if (idx->b.sector_search == 2 && k <= ROWS_K_SMALL) {
         // the product configuration: search + rows in ONE launch (no events: this path is not part of the query statistics)
-        const QueryArgs qa = query_args(idx, d + QH_OFF_PATTERN, reinterpret_cast<const u64*>(d + QH_OFF_OFFSETS), 1, reinterpret_cast<sa_hip_pair_u32*>(d), 0);
+        const QueryArgs qa = one_pattern_args(idx);
         if (qa.keys32) hipLaunchKernelGGL((query_rows_one_kernel<true, ROWS_SLOTS_SMALL>), dim3(1), dim3(256), 0, idx->stream, qa, idx->b.qmap, a);
         else hipLaunchKernelGGL((query_rows_one_kernel<false, ROWS_SLOTS_SMALL>), dim3(1), dim3(256), 0, idx->stream, qa, idx->b.qmap, a);
     } else {
-        if ((rc = launch_query(idx, d + QH_OFF_PATTERN, reinterpret_cast<const u64*>(d + QH_OFF_OFFSETS), 1,
-                               reinterpret_cast<sa_hip_pair_u32*>(d)))) return rc;
+        if (int rc = launch_query(idx, d.pattern(), d.offsets(), 1, d.range())) return rc;
         launch_rows(idx->stream, a);
     }
     SA_HIP_CHECK(hipGetLastError());
     SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
-    if (range) memcpy(range, h, sizeof *range);
-    u32 n = 0;
-    memcpy(&n, h + 8, 4);
-    const u32* rows = reinterpret_cast<const u32*>(h + QH_OFF_HITS);
-    for (u32 i = 0; i < n; ++i) row_ids[i] = rows[i];
+    if (range) *range = *h.range();
+    const u32 n = *h.nhits();
+    for (u32 i = 0; i < n; ++i) row_ids[i] = h.hits()[i];
     *num_rows = n;
     return 0;
 }
 
 int sa_hip_index_query_rows(sa_hip_index* idx, const uint8_t* pattern, uint64_t len, uint32_t k, uint64_t* row_ids,
                             uint32_t* num_rows, sa_hip_pair_u32* range) {
-    if (!idx || !num_rows || (!row_ids && k) || (!pattern && len)) return fail(SA_HIP_EINVAL, "sa_hip_index_query_rows: NULL argument");
+    IndexCall c(idx, "sa_hip_index_query_rows");
+    if (!idx || !num_rows || (!row_ids && k) || (!pattern && len)) return fail(SA_HIP_EINVAL, c.who, "NULL argument");
     *num_rows = 0;
+    c.lock();   // the search, the slabs of hits and the row table under ONE acquisition
+    if ((c.rc = rows_table(idx, c.who, &k))) return c.rc;
+    if (k && k <= ROWS_K_MAX && !host_rows_forced() && !idx->host) return query_rows_device_locked(idx, pattern, len, k, row_ids, num_rows, range);
+    const u32 cap = k ? std::min<u32>(std::max<u32>(4u * k, 1024u), QueryBlock::MAX_HITS) : 0u;
     sa_hip_pair_u32 rg;
     u32 nh = 0;
-    std::lock_guard<std::mutex> g(idx->mu);   // the search, the slabs of hits and the row table under ONE acquisition
-    if (k && idx->row_starts.empty()) return fail(SA_HIP_EINVAL, "sa_hip_index_query_rows: no row table (sa_hip_index_set_rows)");
-    // more rows than the table holds cannot come back: k = 10^9 ("all") must not size anything
-    if ((u64)k > idx->row_starts.size()) k = (u32)idx->row_starts.size();
-    if (k && k <= ROWS_K_MAX && !host_rows_forced() && !idx->host) return query_rows_device_locked(idx, pattern, len, k, row_ids, num_rows, range);
-    const u32 cap = k ? std::min<u32>(std::max<u32>(4u * k, 1024u), QH_MAX_HITS) : 0u;
     try {
         std::vector<u32> first(cap ? cap : 1);
-        int rc = query_hits_locked(idx, pattern, len, cap, &rg, first.data(), &nh);
-        if (rc) return rc;
+        if ((c.rc = query_hits_locked(idx, pattern, len, cap, &rg, first.data(), &nh))) return c.rc;
         if (range) *range = rg;
-        const HostU64Array& starts = idx->row_starts;
-        if (starts.empty()) return 0;
-        std::vector<u64> rows;
-        rc = distinct_rows(starts, rg, k, first.data(), nh,
-                           [&](u64 pos, u64 count, u32* out) { return get_sa_range_locked(idx, pos, count, out); }, rows);
-        if (rc) return rc;
-        for (size_t i = 0; i < rows.size(); ++i) row_ids[i] = rows[i];
-        *num_rows = (uint32_t)rows.size();
-    } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, "sa_hip_index_query_rows: out of host memory"); }
+        return host_rows_of_range(idx, c.who, rg, k, first.data(), nh, row_ids, num_rows);
+    } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, c.who, "out of host memory"); }
+}
+
+// ---- the batched form: one search launch for all the ranges, one rows launch for all the hits -> rows ------------------------
+// A large batch moves its host legs through the process's ring of pinned slabs (host_io.hpp): patterns and offsets up, counts,
+// ranges and the Q x k row ids down as u32, widened into the caller's uint64[Q][k] by the ring's worker threads while the
+// next slabs arrive -- instead of one pageable copy into a Q x k vector (allocated and page-faulted per call) and one
+// thread widening it (1e7 patterns, k = 16: 353 -> see profiles/r04_n_rows_batch.log).  Same bytes, same results.
+// (batches whose Q x k row ids take less than this go down by one plain copy)
+static constexpr size_t ROWS_RING_MIN_BYTES = 32u << 20;
+
+struct RowsBatch {   // the caller's arrays; k clamped to the row table, k_in the stride of row_ids
+    u64 Q; u32 k, k_in;
+    uint64_t* row_ids; uint32_t* counts; sa_hip_pair_u32* ranges;
+};
+
+// where the time of a batch through the ring went, lap by lap, for its trace line (SA_HIP_ROWS_TRACE=1)
+struct RowsTrace {
+    const bool on;
+    Clock::time_point mark = Clock::now();
+    double up = 0, kern = 0, small = 0, rows = 0;
+    void lap(double& ms) { if (on) { ms += ms_since(mark); mark = Clock::now(); } }
+};
+
+// the ring for this batch, held under g_oneshot.mu through `lock`; nullptr: the plain copies
+static int rows_batch_ring(const sa_hip_index* idx, std::unique_lock<std::mutex>& lock, PinnedRing** ring) {
+    lock = std::unique_lock<std::mutex>(g_oneshot.mu);
+    if (!g_oneshot.ring.ready) { if (int rc = g_oneshot.ring.init()) return rc; }
+    if (g_oneshot.ring.device == idx->device) *ring = &g_oneshot.ring;
+    else lock.unlock();   // (the ring's copy stream lives on another device)
     return 0;
 }
 
-// (batches whose Q x k row ids take less than this go down by one plain copy; SA_HIP_ROWS_RING=0: always -- A/B, tests)
-static constexpr size_t ROWS_RING_MIN_BYTES = 32u << 20;
-static bool rows_waves_off() { const char* e = diag_env("SA_HIP_ROWS_WAVES"); return e && e[0] == '0'; }   // A/B, tests: no wave-per-range form
-static u32 rows_wave_groups() { const char* e = diag_env("SA_HIP_ROWS_WAVE_GROUPS"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 256 ? (u32)v : 8u; }   // A/B: workgroups of the wave form per CU
-static bool rows_lanes_off() { const char* e = diag_env("SA_HIP_ROWS_LANES"); return e && e[0] == '0'; }   // A/B, tests: every query through the workgroup form
-static bool rows_trace_on() { const char* e = diag_env("SA_HIP_ROWS_TRACE"); return e && e[0] == '1'; }   // one stderr line per large batch: where its time went
-static bool rows_ring_off() { const char* e = diag_env("SA_HIP_ROWS_RING"); return e && e[0] == '0'; }
+// device rows: ONE rows launch over q_out into r_rows / r_counts, no per-query synchronisation ...
+static int rows_batch_launch(sa_hip_index* idx, const RowsSwitches& sw, const RowsBatch& o) {
+    int rc;
+    if ((rc = idx->r_rows.ensure((size_t)o.Q * o.k * 4)) || (rc = idx->r_counts.ensure((size_t)o.Q * 4))) return rc;
+    const bool lanes = o.Q >= ROWS_LANE_MIN_BATCH && sw.lanes;
+    if (lanes && (rc = idx->r_pending.ensure((2 * (size_t)o.Q + 2) * 4))) return rc;
+    launch_rows(idx->stream, rows_args(idx, idx->q_out.as<sa_hip_pair_u32>(), o.Q, o.k, idx->r_rows.as<u32>(), idx->r_counts.as<u32>()),
+                lanes ? idx->r_pending.as<u32>() : nullptr, sw.waves, sw.wave_groups);
+    SA_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ... their download through the ring: counts and ranges, then the row ids in pieces of whole queries, widened by the workers ...
+static int rows_batch_down_ring(sa_hip_index* idx, PinnedRing& ring, const RowsBatch& o, RowsTrace& t) {
+    int rc;
+    SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
+    t.lap(t.kern);
+    if ((rc = ring_download<u32>(ring, idx->device, idx->r_counts.as<u32>(), o.counts, (size_t)o.Q))) return rc;
+    if (o.ranges && (rc = ring_download<u32>(ring, idx->device, idx->q_out.as<u32>(), reinterpret_cast<u32*>(o.ranges), (size_t)o.Q * 2))) return rc;
+    t.lap(t.small);
+    const size_t per_q = (size_t)o.k * 4;                                        // k <= ROWS_K_MAX: at most 16 KB
+    // whole queries per piece; about 32 pieces (1 MB .. one slab) so that a mid-size batch still spreads over all workers
+    const size_t target = std::min<size_t>(PinnedRing::SLAB_BYTES, std::max<size_t>((size_t)1 << 20, (size_t)o.Q * per_q / 32));
+    const size_t piece = std::max<size_t>(per_q, (target / per_q) * per_q);
+    const u32 k = o.k, k_in = o.k_in;
+    const u32* counts = o.counts;
+    u64* row_ids = o.row_ids;
+    rc = ring_download_pieces(ring, idx->device, idx->r_rows.as<u8>(), (size_t)o.Q * per_q, piece,
+                              [=](const u8* p, size_t off, size_t len) {
+                                  const u32* in = reinterpret_cast<const u32*>(p);
+                                  const u64 q0 = off / per_q, nq = len / per_q;
+                                  for (u64 j = 0; j < nq; ++j) {
+                                      const u32 c = counts[q0 + j];
+                                      u64* out = row_ids + (q0 + j) * k_in;
+                                      const u32* r = in + j * k;
+                                      for (u32 i = 0; i < c; ++i) out[i] = r[i];
+                                  }
+                              });
+    t.lap(t.rows);
+    if (t.on) fprintf(stderr, "[sa_hip rows batch] Q=%llu k=%u: patterns+offsets up %.2f ms, search+rows kernels %.2f, counts+ranges down %.2f, row ids down+widened %.2f (pieces of %zu bytes)\n",
+                      (unsigned long long)o.Q, o.k, t.up, t.kern, t.small, t.rows, piece);
+    return rc;
+}
+
+// ... or by plain copies (the ranges are already on their way down)
+static int rows_batch_down_plain(sa_hip_index* idx, const RowsBatch& o) {
+    std::vector<u32> rows32((size_t)o.Q * o.k);
+    SA_HIP_CHECK(hipMemcpyAsync(o.counts, idx->r_counts.p, (size_t)o.Q * 4, hipMemcpyDeviceToHost, idx->stream));
+    SA_HIP_CHECK(hipMemcpyAsync(rows32.data(), idx->r_rows.p, (size_t)o.Q * o.k * 4, hipMemcpyDeviceToHost, idx->stream));
+    SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
+    for (u64 q = 0; q < o.Q; ++q)
+        for (u32 i = 0; i < o.counts[q]; ++i) o.row_ids[q * o.k_in + i] = rows32[q * o.k + i];
+    return 0;
+}
+
+// host rows (the host path; k beyond ROWS_K_MAX; SA_HIP_HOST_ROWS=1): every range resolved on the host
+static int rows_batch_host_rows(sa_hip_index* idx, const char* who, const RowsBatch& o, const sa_hip_pair_u32* rg_host) {
+    for (u64 q = 0; o.k && q < o.Q; ++q)
+        if (int rc = host_rows_of_range(idx, who, rg_host[q], o.k, nullptr, 0, o.row_ids + q * o.k_in, &o.counts[q])) return rc;
+    return 0;
+}
 
 int sa_hip_index_query_rows_batch(sa_hip_index* idx, const uint8_t* patterns, const uint64_t* offsets, uint64_t Q, uint32_t k,
                                   uint64_t* row_ids, uint32_t* counts, sa_hip_pair_u32* ranges) {
-    if (!idx || (Q && (!offsets || !counts || (!row_ids && k)))) return fail(SA_HIP_EINVAL, "sa_hip_index_query_rows_batch: NULL argument");
+    IndexCall c(idx, "sa_hip_index_query_rows_batch");
+    if (!idx || (Q && (!offsets || !counts || (!row_ids && k)))) return fail(SA_HIP_EINVAL, c.who, "NULL argument");
     if (Q == 0) return 0;
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_query_rows_batch: no index");
-    const u64 total = offsets[Q];
-    if (!patterns && total) return fail(SA_HIP_EINVAL, "sa_hip_index_query_rows_batch: NULL patterns");
+    const RowsSwitches sw;
+    if (c.lock() || c.has_index()) return c.rc;
+    if (!patterns && offsets[Q]) return fail(SA_HIP_EINVAL, c.who, "NULL patterns");
     const u32 k_in = k;
-    if (k && idx->row_starts.empty()) return fail(SA_HIP_EINVAL, "sa_hip_index_query_rows_batch: no row table (sa_hip_index_set_rows)");
-    if ((u64)k > idx->row_starts.size()) k = (u32)idx->row_starts.size();
+    if ((c.rc = rows_table(idx, c.who, &k))) return c.rc;
+    const RowsBatch o{Q, k, k_in, row_ids, counts, ranges};
     for (u64 i = 0; i < Q; ++i) counts[i] = 0;
-    if (idx->host) {
-        try {
-            std::vector<u64> rows;
-            for (u64 q = 0; q < Q; ++q) {
-                const sa_hip_pair_u32 rg = idx->host->query(patterns + offsets[q], offsets[q + 1] - offsets[q]);
-                if (ranges) ranges[q] = rg;
-                if (!k) continue;
-                int rc = distinct_rows(idx->row_starts, rg, k, nullptr, 0,
-                                       [&](u64 pos, u64 count, u32* out) { return get_sa_range_locked(idx, pos, count, out); }, rows);
-                if (rc) return rc;
-                for (size_t i = 0; i < rows.size(); ++i) row_ids[q * k_in + i] = rows[i];
-                counts[q] = (u32)rows.size();
-            }
-        } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, "sa_hip_index_query_rows_batch: out of host memory"); }
-        return 0;
-    }
-    int rc = set_device(idx->device);
-    if (rc) return rc;
-    // ONE search launch for all the ranges
-    if ((rc = idx->q_pat.ensure((size_t)total + 64))) return rc;
-    if ((rc = idx->q_off.ensure((size_t)(Q + 1) * 8))) return rc;
-    if ((rc = idx->q_out.ensure((size_t)Q * sizeof(sa_hip_pair_u32)))) return rc;
-    const bool device_rows = k && k <= ROWS_K_MAX && !host_rows_forced();
-    // A large batch moves its host legs through the process's ring of pinned slabs (host_io.hpp): patterns and offsets up, counts,
-    // ranges and the Q x k row ids down as u32, widened into the caller's uint64[Q][k] by the ring's worker threads while the
-    // next slabs arrive -- instead of one pageable copy into a Q x k vector (allocated and page-faulted per call) and one
-    // thread widening it (1e7 patterns, k = 16: 353 -> see profiles/r04_n_rows_batch.log).  Same bytes, same results.
-    std::unique_lock<std::mutex> ring_lock;
-    PinnedRing* ring = nullptr;
-    if (device_rows && (size_t)Q * k * 4 >= ROWS_RING_MIN_BYTES && !rows_ring_off()) {
-        ring_lock = std::unique_lock<std::mutex>(g_oneshot.mu);
-        if (!g_oneshot.ring.ready && (rc = g_oneshot.ring.init())) return rc;
-        if (g_oneshot.ring.device == idx->device) ring = &g_oneshot.ring;
-        else ring_lock.unlock();   // (the ring's copy stream lives on another device: the plain copies below)
-    }
-    const bool trace = ring && rows_trace_on();
-    auto t_mark = std::chrono::steady_clock::now();
-    double t_up = 0, t_kern = 0, t_small = 0, t_rows = 0;
-    auto lap = [&](double& acc) { const auto now = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::milli>(now - t_mark).count(); t_mark = now; };
-    if (ring) {
-        if ((rc = ring_upload(*ring, idx->stream, idx->device, idx->q_pat.p, patterns, (size_t)total))) return rc;
-        if ((rc = ring_upload(*ring, idx->stream, idx->device, idx->q_off.p, reinterpret_cast<const u8*>(offsets), (size_t)(Q + 1) * 8))) return rc;
-        lap(t_up);
-    } else {
-        if (total) SA_HIP_CHECK(hipMemcpyAsync(idx->q_pat.p, patterns, total, hipMemcpyHostToDevice, idx->stream));
-        SA_HIP_CHECK(hipMemcpyAsync(idx->q_off.p, offsets, (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, idx->stream));
-    }
-    SA_HIP_CHECK(hipMemsetAsync(idx->q_pat.as<u8>() + total, 0, 64, idx->stream));
-    if ((rc = launch_query(idx, idx->q_pat.as<u8>(), idx->q_off.as<u64>(), Q, idx->q_out.as<sa_hip_pair_u32>()))) return rc;
     try {
         std::vector<sa_hip_pair_u32> rg_host;
-        if (!ring && (ranges || !device_rows)) {
+        if (idx->host) {   // host path: the search by the host index
             rg_host.resize(Q);
-            SA_HIP_CHECK(hipMemcpyAsync(rg_host.data(), idx->q_out.p, (size_t)Q * sizeof(sa_hip_pair_u32), hipMemcpyDeviceToHost, idx->stream));
-        }
-        if (device_rows) {
-            // ... ONE rows launch for all the hits -> rows, one copy back: no per-query synchronisation
-            if ((rc = idx->r_rows.ensure((size_t)Q * k * 4))) return rc;
-            if ((rc = idx->r_counts.ensure((size_t)Q * 4))) return rc;
-            const bool lanes = Q >= ROWS_LANE_MIN_BATCH && !rows_lanes_off();
-            if (lanes && (rc = idx->r_pending.ensure((2 * (size_t)Q + 2) * 4))) return rc;
-            RowsArgs a;
-            a.sa = idx->b.sa; a.ranges = idx->q_out.as<sa_hip_pair_u32>(); a.q = Q;
-            a.row_starts = idx->rows_dev.as<u64>(); a.num_rows = idx->row_starts.size(); a.k = k;
-            a.coarse = (idx->rows_coarse_n > 1) ? idx->rows_coarse.as<u64>() : nullptr; a.coarse_n = idx->rows_coarse_n;
-            a.out_rows = idx->r_rows.as<u32>(); a.out_counts = idx->r_counts.as<u32>();
-            launch_rows(idx->stream, a, lanes ? idx->r_pending.as<u32>() : nullptr, !rows_waves_off(), rows_wave_groups());
-            SA_HIP_CHECK(hipGetLastError());
-            if (ring) {
+            for (u64 q = 0; q < Q; ++q) rg_host[q] = idx->host->query(patterns + offsets[q], offsets[q + 1] - offsets[q]);
+            c.rc = rows_batch_host_rows(idx, c.who, o, rg_host.data());
+        } else {           // stage, search, then the rows on the device (down by ring or by plain copies) or on the host
+            if (c.current()) return c.rc;
+            const bool device_rows = k && k <= ROWS_K_MAX && !sw.host_rows;
+            std::unique_lock<std::mutex> ring_lock;
+            PinnedRing* ring = nullptr;
+            if (device_rows && (size_t)Q * k * 4 >= ROWS_RING_MIN_BYTES && sw.ring && (c.rc = rows_batch_ring(idx, ring_lock, &ring))) return c.rc;
+            RowsTrace t{ring && sw.trace};
+            if ((c.rc = stage_batch(idx, ring, patterns, offsets, Q))) return c.rc;
+            t.lap(t.up);
+            if ((c.rc = launch_query(idx, idx->q_pat.as<u8>(), idx->q_off.as<u64>(), Q, idx->q_out.as<sa_hip_pair_u32>()))) return c.rc;
+            if (!ring && (ranges || !device_rows)) {
+                rg_host.resize(Q);
+                SA_HIP_CHECK(hipMemcpyAsync(rg_host.data(), idx->q_out.p, (size_t)Q * sizeof(sa_hip_pair_u32), hipMemcpyDeviceToHost, idx->stream));
+            }
+            if (device_rows) {
+                if ((c.rc = rows_batch_launch(idx, sw, o))) return c.rc;
+                if (ring) return rows_batch_down_ring(idx, *ring, o, t);
+                c.rc = rows_batch_down_plain(idx, o);
+            } else {
                 SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
-                lap(t_kern);
-                if ((rc = ring_download<u32>(*ring, idx->device, idx->r_counts.as<u32>(), counts, (size_t)Q))) return rc;
-                if (ranges && (rc = ring_download<u32>(*ring, idx->device, idx->q_out.as<u32>(), reinterpret_cast<u32*>(ranges), (size_t)Q * 2))) return rc;
-                lap(t_small);
-                const size_t per_q = (size_t)k * 4;                                        // k <= ROWS_K_MAX: at most 16 KB
-                // whole queries per piece; about 32 pieces (1 MB .. one slab) so that a mid-size batch still spreads over all workers
-                const size_t target = std::min<size_t>(PinnedRing::SLAB_BYTES, std::max<size_t>((size_t)1 << 20, (size_t)Q * per_q / 32));
-                const size_t piece = std::max<size_t>(per_q, (target / per_q) * per_q);
-                rc = ring_download_pieces(*ring, idx->device, idx->r_rows.as<u8>(), (size_t)Q * per_q, piece,
-                                          [&](const u8* p, size_t off, size_t len) {
-                                              const u32* in = reinterpret_cast<const u32*>(p);
-                                              const u64 q0 = off / per_q, nq = len / per_q;
-                                              for (u64 j = 0; j < nq; ++j) {
-                                                  const u32 c = counts[q0 + j];
-                                                  u64* o = row_ids + (q0 + j) * k_in;
-                                                  const u32* r = in + j * k;
-                                                  for (u32 i = 0; i < c; ++i) o[i] = r[i];
-                                              }
-                                          });
-                lap(t_rows);
-                if (trace) fprintf(stderr, "[sa_hip rows batch] Q=%llu k=%u: patterns+offsets up %.2f ms, search+rows kernels %.2f, counts+ranges down %.2f, row ids down+widened %.2f (pieces of %zu bytes)\n",
-                                   (unsigned long long)Q, k, t_up, t_kern, t_small, t_rows, piece);
-                return rc;
-            }
-            std::vector<u32> rows32((size_t)Q * k);
-            SA_HIP_CHECK(hipMemcpyAsync(counts, idx->r_counts.p, (size_t)Q * 4, hipMemcpyDeviceToHost, idx->stream));
-            SA_HIP_CHECK(hipMemcpyAsync(rows32.data(), idx->r_rows.p, (size_t)Q * k * 4, hipMemcpyDeviceToHost, idx->stream));
-            SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
-            for (u64 q = 0; q < Q; ++q)
-                for (u32 i = 0; i < counts[q]; ++i) row_ids[q * k_in + i] = rows32[q * k + i];
-        } else {
-            SA_HIP_CHECK(hipStreamSynchronize(idx->stream));
-            if (k) {
-                std::vector<u64> rows;
-                for (u64 q = 0; q < Q; ++q) {
-                    rc = distinct_rows(idx->row_starts, rg_host[q], k, nullptr, 0,
-                                       [&](u64 pos, u64 count, u32* out) { return get_sa_range_locked(idx, pos, count, out); }, rows);
-                    if (rc) return rc;
-                    for (size_t i = 0; i < rows.size(); ++i) row_ids[q * k_in + i] = rows[i];
-                    counts[q] = (u32)rows.size();
-                }
+                c.rc = rows_batch_host_rows(idx, c.who, o, rg_host.data());
             }
         }
-        if (ranges) memcpy(ranges, rg_host.data(), (size_t)Q * sizeof(sa_hip_pair_u32));
-    } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, "sa_hip_index_query_rows_batch: out of host memory"); }
-    return 0;
+        if (!c.rc && ranges) memcpy(ranges, rg_host.data(), (size_t)Q * sizeof(sa_hip_pair_u32));
+    } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, c.who, "out of host memory"); }
+    return c.rc;
 }
 
 int sa_hip_index_rows_for_range(sa_hip_index* idx, sa_hip_pair_u32 range, uint32_t k, uint64_t* row_ids, uint32_t* num_rows) {
-    if (!idx || !num_rows || (!row_ids && k)) return fail(SA_HIP_EINVAL, "sa_hip_index_rows_for_range: NULL argument");
+    IndexCall c(idx, "sa_hip_index_rows_for_range");
+    if (!idx || !num_rows || (!row_ids && k)) return fail(SA_HIP_EINVAL, c.who, "NULL argument");
     *num_rows = 0;
-    std::lock_guard<std::mutex> g(idx->mu);
-    if (!idx->has_index) return fail(SA_HIP_EINVAL, "sa_hip_index_rows_for_range: no index");
-    if (range.first != 0xFFFFFFFFu && (u32)(range.second - range.first + 1u) != 0u &&
-        ((u64)range.second >= (idx->host ? idx->host->n : idx->b.n) || range.first > range.second)) return fail(SA_HIP_EINVAL, "sa_hip_index_rows_for_range: range outside the suffix array");
-    if (k && idx->row_starts.empty()) return fail(SA_HIP_EINVAL, "sa_hip_index_rows_for_range: no row table (sa_hip_index_set_rows)");
-    if ((u64)k > idx->row_starts.size()) k = (u32)idx->row_starts.size();
-    try {
-        const HostU64Array& starts = idx->row_starts;
-        if (starts.empty()) return 0;
-        std::vector<u64> rows;
-        int rc = distinct_rows(starts, range, k, nullptr, 0,
-                               [&](u64 pos, u64 count, u32* out) { return get_sa_range_locked(idx, pos, count, out); }, rows);
-        if (rc) return rc;
-        for (size_t i = 0; i < rows.size(); ++i) row_ids[i] = rows[i];
-        *num_rows = (uint32_t)rows.size();
-    } catch (const std::bad_alloc&) { return fail(SA_HIP_ENOMEM, "sa_hip_index_rows_for_range: out of host memory"); }
-    return 0;
+    if (c.lock() || c.has_index()) return c.rc;
+    if (hits_of_range(range) && ((u64)range.second >= sa_hip_index_n(idx) || range.first > range.second))
+        return fail(SA_HIP_EINVAL, c.who, "range outside the suffix array");
+    if ((c.rc = rows_table(idx, c.who, &k))) return c.rc;
+    return host_rows_of_range(idx, c.who, range, k, nullptr, 0, row_ids, num_rows);
 }
 
 static int csv_index_finish(sa_hip_csv_index* c) {
@@ -1490,7 +1542,7 @@ sa_hip_pair_u32 sa_hip_get_substring_positions_file(sa_hip_csv_index* c, const c
     sa_hip_pair_u32 q;
     if (sa_hip_index_query_hits(c->idx, reinterpret_cast<const uint8_t*>(substring), strlen(substring), 0, &q, nullptr, &nh)) return r;
     // engine.c:962-965: start / end are only ever set on an exact match, so ANY miss is {UINT32_MAX, UINT32_MAX}
-    if (q.first == 0xFFFFFFFFu || (u32)(q.second - q.first + 1u) == 0u) return r;
+    if (hits_of_range(q) == 0) return r;
     return q;
 }
 
@@ -1543,7 +1595,7 @@ uint32_t sa_hip_get_matching_records(const char* str, const sa_hip_SuffixArray_s
                                      char** matching_records) {
     if (!str || !s || !substring || (!matching_records && k) || (!s->suffix_array && s->n)) { fail(SA_HIP_EINVAL, "sa_hip_get_matching_records: NULL argument"); return 0; }
     const sa_hip_pair_u32 rg = sa_hip_get_substring_positions(str, s, substring);
-    if (rg.first == 0xFFFFFFFFu || (u32)(rg.second - rg.first + 1u) == 0u) return 0;   // engine.c:1181-1185
+    if (hits_of_range(rg) == 0) return 0;   // engine.c:1181-1185
     const u64 n = s->n;
     u32 made = 0;
     try {

@@ -69,6 +69,12 @@ static int check_csv(const char* dir) {
     }
     sa_hip_pair_u32 miss = {5, 4};
     REQUIRE(distinct_rows(starts, miss, 10, nullptr, 0, fetch, rows) == 0 && rows.empty());
+    // hits_of_range (common.hpp), the one spelling of a range's hit count: both miss encodings, the wrap at first = 0, the whole array
+    const sa_hip_pair_u32 absent = {0xFFFFFFFFu, 0xFFFFFFFFu}, wrap = {0, 0xFFFFFFFFu}, one = {7, 7}, all = {0, 0xFFFFFFFEu};
+    REQUIRE(hits_of_range(miss) == 0 && hits_of_range(absent) == 0 && hits_of_range(wrap) == 0);
+    REQUIRE(hits_of_range(one) == 1 && hits_of_range(rg) == (u32)fake.size() - 14 && hits_of_range(all) == 0xFFFFFFFFu);
+    REQUIRE(distinct_rows(starts, absent, 10, nullptr, 0, fetch, rows) == 0 && rows.empty());
+    REQUIRE(distinct_rows(starts, wrap, 10, nullptr, 0, fetch, rows) == 0 && rows.empty());
     csv_free(&ref);
     remove(path.c_str());
     return 0;
