@@ -1377,6 +1377,56 @@ int sa_hip_token_shards_score_batch(sa_hip_token_shards* set, const int32_t* pat
                                     sa_hip_token_score_head* heads);
 int sa_hip_token_shards_score_info(const sa_hip_token_shards* set, sa_hip_token_shards_score_stats* out);
 
+/* (6k) top-k next symbols and draws from a span (csrc/token_top.hpp, csrc/capi_token_top.hpp): which k symbols follow a context
+ * most often, and a next symbol drawn with the corpus's probability.  All results are exact.
+ *
+ * Spans, modes, need_next and max_length are those of (6b); start = first + ended and total = count - ended are the ranks of a
+ * span that have a next symbol s(r) = T[SA[r] + length], non-decreasing in r.
+ *   top     the walked ranks are [start, start + walked), walked = budget ? min(total, budget) : total.  Where (6b) gives the cap
+ *           smallest symbols, this gives the k (1 .. 64) most frequent among the walked ranks: symbols[i * k ..] and
+ *           counts[i * k ..] sorted by count descending, ties by symbol ascending; a symbol whose ranks the budget cuts counts
+ *           with those inside.  Cells beyond heads[i].written are not written.  The answer is the true top-k of the span iff
+ *           budget == 0 || total <= budget.
+ *   sample  m draws per span, draws[i * m + j] any uint64: rank = start + floor(draw * total / 2^64), symbol = s(rank), to
+ *           symbols[i * m + j] and (unless NULL) ranks[i * m + j]; total == 0 gives symbol -1 and rank 0xFFFFFFFF.  Nothing random
+ *           happens on the device: the same draws give the same answers, and a uniform draw gives every next symbol its corpus
+ *           probability count / total to within 2^-64 * total.
+ *
+ * Errors: a NULL handle or argument, mode or need_next other than 0 / 1, k == 0, k > 64, m == 0, Q * k or Q * m >= 2^31 and
+ * descending offsets return -1 before any HIP call; Q == 0 is a no-op.  The device forms are asynchronous on the handle's stream
+ * until sa_hip_token_index_sync and chain behind sa_hip_token_index_spans_batch_device without a host trip; like
+ * sa_hip_token_index_next_batch_device they trust nothing: first and count are clamped to the array, and an array that is not the
+ * suffix array gives unspecified entries from bounded loops.  The host forms stage through buffers of the handle. */
+typedef struct sa_hip_token_top {
+    uint32_t written;   /* entries written, = min(k, distinct)                                        */
+    uint32_t distinct;  /* distinct next symbols among the walked ranks                               */
+    uint32_t covered;   /* sum of the written counts                                                  */
+    uint32_t total;     /* count - ended (as sa_hip_token_next.total); walked = budget ? min(total, budget) : total */
+} sa_hip_token_top;
+
+typedef struct sa_hip_token_top_info {
+    uint64_t q;            /* spans of the last top or sample launch                            */
+    double   spans_ms;     /* HIP-event time of the last span launch (the call waits for it)    */
+    double   top_ms;       /* ... of the last top launch                                        */
+    double   sample_ms;    /* ... of the last sample launch                                     */
+} sa_hip_token_top_info;
+
+/* spans_dev: sa_hip_token_span[Q]; symbols_dev: int32[Q * k]; counts_dev: uint32[Q * k]; heads_dev: sa_hip_token_top[Q]. */
+int sa_hip_token_index_top_batch_device(sa_hip_token_index* t, const void* spans_dev, uint64_t Q, uint32_t k, uint32_t budget,
+                                        void* symbols_dev, void* counts_dev, void* heads_dev);
+/* Both steps from host contexts: spans (may be NULL), symbols, counts and heads out. */
+int sa_hip_token_index_top_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                 int mode, uint32_t max_length, int need_next, uint32_t k, uint32_t budget,
+                                 sa_hip_token_span* spans, int32_t* symbols, uint32_t* counts, sa_hip_token_top* heads);
+/* draws_dev: uint64[Q * m]; symbols_dev: int32[Q * m]; ranks_dev: uint32[Q * m], may be NULL. */
+int sa_hip_token_index_sample_batch_device(sa_hip_token_index* t, const void* spans_dev, uint64_t Q, const void* draws_dev,
+                                           uint32_t m, void* symbols_dev, void* ranks_dev);
+/* Both steps from host contexts and host draws: spans (may be NULL), symbols and ranks (may be NULL) out. */
+int sa_hip_token_index_sample_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                    int mode, uint32_t max_length, int need_next, const uint64_t* draws, uint32_t m,
+                                    sa_hip_token_span* spans, int32_t* symbols, uint32_t* ranks);
+int sa_hip_token_index_top_info(const sa_hip_token_index* t, sa_hip_token_top_info* out);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 
 /* Per-build statistics of the last build on this handle (roofline accounting). */

@@ -23,7 +23,8 @@ MATCH_HEAD_DTYPE = np.dtype([("written", "<u4"), ("maximal", "<u4"), ("longest",
 SCORE_DTYPE = np.dtype([("length", "<u4"), ("context_count", "<u4"), ("token_count", "<u4"), ("first", "<u4")])  # sa_hip_token_score
 SCORE_HEAD_DTYPE = np.dtype([("scored", "<u4"), ("seen", "<u4"), ("certain", "<u4"), ("longest", "<u4"),
                              ("length_sum", "<u8")])                                                       # sa_hip_token_score_head
-TOKEN_ALL_MAX = 16                                                                                          # SA_HIP_TOKEN_ALL_MAX
+TOP_DTYPE = np.dtype([("written", "<u4"), ("distinct", "<u4"), ("covered", "<u4"), ("total", "<u4")])       # sa_hip_token_top
+TOKEN_ALL_MAX = 16                                                                                         # SA_HIP_TOKEN_ALL_MAX
 SHARDS_NEXT_DTYPE = np.dtype([("written", "<u4"), ("length", "<u4"), ("covered", "<u8"), ("total", "<u8")])  # sa_hip_token_shards_next
 SHARDS_MATCH_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("count", "<u8")])                      # sa_hip_token_shards_match
 SHARDS_SCORE_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("context_count", "<u8"),
@@ -68,6 +69,8 @@ EXPORTS = [
     "sa_hip_token_index_match_docs_batch", "sa_hip_token_index_match_info",
     "sa_hip_token_index_score_batch_device", "sa_hip_token_index_score_docs_batch_device", "sa_hip_token_index_score_batch",
     "sa_hip_token_index_score_info",
+    "sa_hip_token_index_top_batch_device", "sa_hip_token_index_top_batch", "sa_hip_token_index_sample_batch_device",
+    "sa_hip_token_index_sample_batch", "sa_hip_token_index_top_info",
     "sa_hip_token_shards_create", "sa_hip_token_shards_destroy", "sa_hip_token_shards_shard", "sa_hip_token_shards_sync",
     "sa_hip_token_shards_info", "sa_hip_token_shards_query_batch", "sa_hip_token_shards_query_batch_device",
     "sa_hip_token_shards_spans_batch", "sa_hip_token_shards_spans_batch_device", "sa_hip_token_shards_next_batch",
@@ -278,6 +281,18 @@ class TokenScoreInfo(C.Structure):
     """sa_hip_token_score_info: the last match, score and score-docs launches of a token index."""
     _fields_ = [("q", C.c_uint64), ("positions", C.c_uint64), ("match_ms", C.c_double), ("score_ms", C.c_double),
                 ("docs_ms", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class TokenTop(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("distinct", C.c_uint32), ("covered", C.c_uint32), ("total", C.c_uint32)]
+
+
+class TokenTopInfo(C.Structure):
+    """sa_hip_token_top_info: the last span, top and sample launches of a token index."""
+    _fields_ = [("q", C.c_uint64), ("spans_ms", C.c_double), ("top_ms", C.c_double), ("sample_ms", C.c_double)]
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -673,6 +688,16 @@ def lib():
     L.sa_hip_token_index_score_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, vp]
     L.sa_hip_token_index_score_info.restype = C.c_int
     L.sa_hip_token_index_score_info.argtypes = [vp, C.POINTER(TokenScoreInfo)]
+    L.sa_hip_token_index_top_batch_device.restype = C.c_int
+    L.sa_hip_token_index_top_batch_device.argtypes = [vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_index_top_batch.restype = C.c_int
+    L.sa_hip_token_index_top_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_index_sample_batch_device.restype = C.c_int
+    L.sa_hip_token_index_sample_batch_device.argtypes = [vp, vp, u64, vp, C.c_uint32, vp, vp]
+    L.sa_hip_token_index_sample_batch.restype = C.c_int
+    L.sa_hip_token_index_sample_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, vp, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_index_top_info.restype = C.c_int
+    L.sa_hip_token_index_top_info.argtypes = [vp, C.POINTER(TokenTopInfo)]
     L.sa_hip_token_shards_create.restype = C.c_int
     L.sa_hip_token_shards_create.argtypes = [C.POINTER(vp), vp, C.c_uint32]
     L.sa_hip_token_shards_destroy.restype = None
@@ -1527,6 +1552,48 @@ class TokenIndex(_TokenHandle):
 
     def next_info(self):
         return self._info(self._lib.sa_hip_token_index_next_info, TokenNextInfo)
+
+    def top_batch_device(self, spans_dev_ptr, q, k, budget, symbols_dev_ptr, counts_dev_ptr, heads_dev_ptr):
+        """The k most frequent next symbols of q device spans (among the first `budget` ranks of each; 0: all); asynchronous on
+        the handle's stream until sync()."""
+        check(self._lib.sa_hip_token_index_top_batch_device(self._h, spans_dev_ptr, q, int(k), int(budget), symbols_dev_ptr, counts_dev_ptr,
+                                                            heads_dev_ptr))
+
+    def top_batch(self, patterns, k=8, mode=0, max_length=0, need_next=True, budget=0, fill=0):
+        """Spans as in spans_batch, then their k (1 .. 64) most frequent next symbols.  -> dict: spans [Q], symbols int32[Q, k] and
+        counts uint32[Q, k] sorted by count descending, then symbol ascending, heads (written, distinct, covered, total)[Q].
+        Cells beyond heads['written'] keep `fill`."""
+        buf, off, q = self._contexts(patterns)
+        k = int(k)
+        spans, heads = _rows(q, SPAN_DTYPE), _rows(q, TOP_DTYPE)
+        sym, cnt = _rows(q, np.int32, k, fill), _rows(q, np.uint32, k, fill)
+        self._call(q, self._lib.sa_hip_token_index_top_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)), k,
+                   int(budget), _ptr(spans), _ptr(sym), _ptr(cnt), _ptr(heads))
+        return {"spans": spans[:q], "symbols": sym[:q], "counts": cnt[:q], "heads": heads[:q]}
+
+    def sample_batch_device(self, spans_dev_ptr, q, draws_dev_ptr, m, symbols_dev_ptr, ranks_dev_ptr=None):
+        """m next symbols per device span, one per uint64 draw; asynchronous on the handle's stream until sync()."""
+        check(self._lib.sa_hip_token_index_sample_batch_device(self._h, spans_dev_ptr, q, draws_dev_ptr, int(m), symbols_dev_ptr, ranks_dev_ptr))
+
+    def sample_batch(self, patterns, draws, mode=1, max_length=0, need_next=True):
+        """Spans as in spans_batch, then one next symbol per draw: draws uint64[Q, m] (or [Q]: m = 1), rank = first + ended +
+        floor(draw * total / 2^64).  -> dict: spans [Q], symbols int32[Q, m] (-1 where nothing follows), ranks uint32[Q, m]
+        (0xFFFFFFFF there)."""
+        buf, off, q = self._contexts(patterns)
+        draws = np.ascontiguousarray(draws, dtype=np.uint64)
+        if draws.ndim == 1:
+            draws = draws.reshape(-1, 1)
+        if draws.ndim != 2 or draws.shape[0] != q or (q and draws.shape[1] == 0):
+            raise ValueError("draws: uint64[Q, m], m >= 1")
+        m = draws.shape[1]
+        spans = _rows(q, SPAN_DTYPE)
+        sym, ranks = _rows(q, np.int32, m), _rows(q, np.uint32, m)
+        self._call(q, self._lib.sa_hip_token_index_sample_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)),
+                   _ptr(draws), m, _ptr(spans), _ptr(sym), _ptr(ranks))
+        return {"spans": spans[:q], "symbols": sym[:q], "ranks": ranks[:q]}
+
+    def top_info(self):
+        return self._info(self._lib.sa_hip_token_index_top_info, TokenTopInfo)
 
     def set_documents(self, starts):
         """starts: the first text position of every document (starts[0] == 0, non-decreasing, <= n); None removes the documents."""

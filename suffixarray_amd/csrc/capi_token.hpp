@@ -1,7 +1,8 @@
 // capi_token.hpp -- the C ABI of the token index (include/sa_hip.h section 6), included by sa_capi.hip (same translation unit).
 // The kernels and the search structures are csrc/token_query.hpp, spans and next symbols csrc/token_next.hpp, documents csrc/token_docs.hpp (their entry points:
 // capi_token_docs.hpp), per-document counts and AND groups csrc/token_all.hpp (capi_token_all.hpp), matching statistics csrc/token_match.hpp
-// (capi_token_match.hpp), infinity-gram scores csrc/token_score.hpp (capi_token_score.hpp); the suffix array of sa_hip_token_index_build comes from
+// (capi_token_match.hpp), infinity-gram scores csrc/token_score.hpp (capi_token_score.hpp), top-k next symbols and draws
+// csrc/token_top.hpp (capi_token_top.hpp); the suffix array of sa_hip_token_index_build comes from
 // the build behind sa_hip_libsais_int_device (capi_dropins.hpp: int_device).
 // What the capi_token*.hpp files share is here and in two small headers: the stopwatches (launch_timer.hpp), the upload of a host
 // batch of contexts (token_upload), and the way of staged heads and rows to the caller (token_rows_out; its row copy is
@@ -54,11 +55,17 @@ struct sa_hip_token_index {
     DevBuf sc_scores, sc_heads;              // staging of the host form (its matches go to m_spans)
     LaunchTimer tm_sc, tm_sd;                // the last score launch (q: positions) / score docs launch (q: documents)
     u64 sc_last = 0;                         // documents of the last launch of either kind
+    // top-k next symbols and draws (token_top.hpp, capi_token_top.hpp); the host forms stage through s_spans, s_sym, s_cnt, s_heads
+    DevBuf tp_draws;                         // staging of the host form's draws
+    LaunchTimer tm_tp, tm_sm;                // the last top / sample launch
+    u64 tp_last = 0;                         // spans of the last launch of either kind
 
-    std::array<LaunchTimer*, 11> timers() { return {&tm_q, &tm_sp, &tm_nx, &tm_lc, &tm_dc, &tm_tf, &tm_al, &tm_mt, &tm_md, &tm_sc, &tm_sd}; }
+    std::array<LaunchTimer*, 13> timers() {
+        return {&tm_q, &tm_sp, &tm_nx, &tm_lc, &tm_dc, &tm_tf, &tm_al, &tm_mt, &tm_md, &tm_sc, &tm_sd, &tm_tp, &tm_sm};
+    }
     auto buffers() {                         // every DevBuf member above (x, docs and ranks release their own)
         return std::array{&q_pat, &q_off, &q_out, &s_spans, &s_sym, &s_cnt, &s_heads, &s_list, &d_docs, &d_offs, &d_heads, &a_goff, &a_cnt,
-                          &a_wr, &m_spans, &m_pos, &m_out, &m_heads, &sc_scores, &sc_heads};
+                          &a_wr, &m_spans, &m_pos, &m_out, &m_heads, &sc_scores, &sc_heads, &tp_draws};
     }
 };
 

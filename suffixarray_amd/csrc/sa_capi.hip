@@ -1695,6 +1695,7 @@ int sa_hip_read_suffix_array(sa_hip_SuffixArray_struct* s, const char* sa_filena
 #include "capi_token_all.hpp"
 #include "capi_token_match.hpp"
 #include "capi_token_score.hpp"
+#include "capi_token_top.hpp"
 #include "capi_token_shards.hpp"
 #include "capi_token_shard_match.hpp"
 #include "capi_token_shard_score.hpp"

@@ -119,6 +119,24 @@ __device__ __forceinline__ Walk tq_walk_of(const View& x, const sa_hip_token_spa
     return w;
 }
 
+// The jump step of a wave (tq_next_kernel, tq_top_kernel of token_top.hpp): rank lo holds cur, the ranks (lo, hi) are not known.
+// Every step samples 64 evenly spaced ranks and narrows to the 1/64 slice where the run of cur ends, until <= 64 ranks are left
+// (<= NEXT_JUMP_STEPS steps); -> the last rank known to hold cur, the same in every lane.
+__device__ __forceinline__ u32 tq_jump_run(const View& x, int lane, int32_t cur, u32 length, u32 lo, u32 hi) {
+    for (int step = 0; step < NEXT_JUMP_STEPS && hi - lo - 1 > (u32)WAVE; ++step) {
+        const u32 stride = (hi - lo - 1 + (u32)WAVE - 1) / (u32)WAVE;
+        const u64 q = (u64)lo + (u64)(lane + 1) * stride;
+        int32_t sq = 0;
+        const bool eq = q < hi && tq_next_symbol(x, (u32)q, length, &sq) && sq == cur;
+        const u64 b = __ballot(eq);
+        const u32 lead = b == ~0ull ? (u32)WAVE : (u32)__ffsll((unsigned long long)~b) - 1u;   // samples still equal
+        const u64 cut = (u64)lo + (u64)(lead + 1) * stride;                                    // the first that is not
+        if (lead < (u32)WAVE && cut < hi) hi = (u32)cut;
+        lo += lead * stride;
+    }
+    return lo;
+}
+
 // One wave per span.  list == nullptr: span w of all Q; else span list[w] of the *n_list entries tq_next_lane_kernel left.
 __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_next_kernel(View x, NextArgs g, const u32* __restrict__ list,
                                                                     const u32* __restrict__ n_list, const int jump) {
@@ -153,19 +171,7 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_next_kernel(View x, Next
                 // the window is all the running symbol
                 u32 lo = a + nact - 1;                       // known to hold cur
                 u32 hi = k.end;                              // (lo, hi): not known
-                if (jump && hi - lo - 1 > NEXT_JUMP_MIN) {
-                    for (int step = 0; step < NEXT_JUMP_STEPS && hi - lo - 1 > (u32)WAVE; ++step) {
-                        const u32 stride = (hi - lo - 1 + (u32)WAVE - 1) / (u32)WAVE;
-                        const u64 q = (u64)lo + (u64)(lane + 1) * stride;
-                        int32_t sq = 0;
-                        const bool eq = q < hi && tq_next_symbol(x, (u32)q, k.length, &sq) && sq == cur;
-                        const u64 b = __ballot(eq);
-                        const u32 lead = b == ~0ull ? (u32)WAVE : (u32)__ffsll((unsigned long long)~b) - 1u;   // samples still equal
-                        const u64 cut = (u64)lo + (u64)(lead + 1) * stride;                                    // the first that is not
-                        if (lead < (u32)WAVE && cut < hi) hi = (u32)cut;
-                        lo += lead * stride;
-                    }
-                }
+                if (jump && hi - lo - 1 > NEXT_JUMP_MIN) lo = tq_jump_run(x, lane, cur, k.length, lo, hi);
                 a = lo + 1;
                 continue;
             }

@@ -5,6 +5,8 @@
     ti.positions([464, 2068], limit=10)    # where: text positions in suffix order
     ti.next_token_counts([464, 2068])      # {token: count} of what follows the n-gram
     ti.next_tokens(contexts, cap=64, longest_suffix=True)   # the same per context, backing off to its longest suffix that occurs
+    ti.top_next_tokens(contexts, k=8)      # the k most frequent next tokens per context, by count descending
+    ti.sample_next(contexts, samples=4, seed=0)             # next tokens drawn with the corpus's probability: int32[Q, samples]
     ti = TokenIndex(tokens, doc_starts=starts)              # ... with documents: document d is tokens[starts[d] : starts[d + 1]]
     ti.locate([464, 2068], limit=10)       # where, as (document, offset inside it)
     ti.document_counts([[464, 2068], [11]])   # in how many documents every n-gram occurs
@@ -165,6 +167,29 @@ class TokenIndex:
         r = self.next_tokens([list(ngram)], cap=cap, longest_suffix=longest_suffix, max_length=max_length)
         w = int(r["written"][0])
         return {int(s): int(c) for s, c in zip(r["symbols"][0, :w], r["counts"][0, :w])}
+
+    def top_next_tokens(self, ngrams, k=8, longest_suffix=False, max_length=None, budget=None):
+        """The k (1 .. 64) most frequent tokens behind every n-gram.  -> dict of arrays: symbols int32[Q, k] and counts
+        uint32[Q, k], by count descending, ties by token ascending, of which the first written[i] = min(k, distinct[i]) are valid
+        in row i; distinct[i] = the distinct next tokens, covered[i] = the sum of the written counts, total[i] = occurrences that
+        have a next token; spans as in _capi.TokenIndex.spans_batch.  budget: only the first `budget` occurrences in suffix order
+        are walked (the tokens with the smallest ids); exact[i] = every occurrence was walked, so row i is the true top-k.
+        longest_suffix: as in next_tokens."""
+        r = self._idx.top_batch(ngrams, k=k, mode=1 if longest_suffix else 0, max_length=max_length or 0, need_next=True, budget=budget or 0)
+        h = r["heads"]
+        return {"symbols": r["symbols"], "counts": r["counts"], "written": h["written"].copy(), "distinct": h["distinct"].copy(),
+                "covered": h["covered"].copy(), "total": h["total"].copy(), "exact": h["total"] <= (budget or 0xFFFFFFFF),
+                "spans": r["spans"]}
+
+    def sample_next(self, ngrams, draws=None, samples=1, seed=None, longest_suffix=True, max_length=None):
+        """Next tokens drawn with the corpus's probability: int32[Q, samples], -1 where nothing follows.  draws: uint64[Q, samples]
+        (or [Q]), draw d picks the occurrence floor(d * total / 2^64) of the context's total in suffix order -- the same draws
+        give the same tokens; without them they come from np.random.default_rng(seed).  longest_suffix: a context backs off to
+        its longest suffix (at most max_length symbols) that has a next token."""
+        q = len(ngrams[1]) - 1 if isinstance(ngrams, tuple) else len(ngrams)
+        if draws is None:
+            draws = np.random.default_rng(seed).integers(0, 2 ** 64, size=(q, int(samples)), dtype=np.uint64)
+        return self._idx.sample_batch(ngrams, draws, mode=1 if longest_suffix else 0, max_length=max_length or 0, need_next=True)["symbols"]
 
     def matching_statistics(self, docs, max_length=None):
         """Which parts of query texts stand verbatim in the corpus.  docs: a list of int sequences.  -> one (length, count, first)
