@@ -1427,6 +1427,68 @@ int sa_hip_token_index_sample_batch(sa_hip_token_index* t, const int32_t* patter
                                     sa_hip_token_span* spans, int32_t* symbols, uint32_t* ranks);
 int sa_hip_token_index_top_info(const sa_hip_token_index* t, sa_hip_token_top_info* out);
 
+/* (6l) top-k next symbols and draws over a shard set (csrc/token_shard_top.hpp, csrc/capi_token_shard_top.hpp): the calls of (6k)
+ * answered over all shards of a set.  All results are exact.  An exact top-k of counts summed over shards cannot be merged from
+ * the shards' own top-k lists (a symbol that is (k+1)-th in every shard can be first overall), so one kernel walks the S spans of a
+ * context side by side and sums equal symbols as it goes; it keeps no per-shard lists: no scratch budget, no chunks.
+ *
+ * Spans, modes, need_next, max_length and the layout spans[s * Q + i] are those of (6c).  For shard s of context i: start_s =
+ * first + ended and total_s = count - ended (both after clamping to the shard's array); total = sum over s of total_s, a uint64.
+ *   top     the continuations of a context are taken in the set's merged order, ascending by next symbol -- the suffix order of a
+ *           single index over the whole corpus; walked = budget ? min(total, budget) : total, budget a uint64.  The k (1 .. 64)
+ *           most frequent next symbols among the first `walked` continuations, their counts summed over the shards as uint64:
+ *           symbols[i * k ..] (int32) and counts[i * k ..] (uint64) sorted by count descending, ties by symbol ascending.  The
+ *           merged run that the budget cuts counts with what lies inside (which shard's ranks those are does not matter: only the
+ *           sum is reported).  Cells beyond heads[i].written are not written.  The answer is the true top-k iff budget == 0 ||
+ *           total <= budget.  With these definitions the answer equals what sa_hip_token_index_top_batch gives on one index over
+ *           the uncut corpus, at every S.
+ *   sample  m draws per context, draws[i * m + j] any uint64: r = floor(draw * total / 2^64).  The continuations are numbered
+ *           shard-major -- shard 0's ranks [start_0, start_0 + total_0) first, then shard 1's, and so on: s is the shard with
+ *           before_s <= r < before_s + total_s, rank = start_s + (r - before_s), symbol = s_s(rank) read at that shard's span
+ *           length.  symbols int32[Q * m], shards_out uint32[Q * m] and ranks uint32[Q * m]; the last two may be NULL, each on
+ *           its own.  total == 0 gives -1 / 0xFFFFFFFF / 0xFFFFFFFF.  Nothing random happens on the device, and a uniform draw
+ *           gives every next symbol count / total, its probability over the whole corpus.  The mapping from draw to symbol is
+ *           shard-major, not symbol-major: for S > 1 it differs from that of a single index over the uncut corpus (6k); the
+ *           distribution is the same, and at S == 1 the mapping is identical.
+ *
+ * Errors: a NULL set or required pointer, mode or need_next other than 0 / 1, k == 0, k > 64, m == 0, Q * k or Q * m >= 2^31 and
+ * descending offsets return -1 before any HIP call (Q * k < 2^31 and S <= 64 keep Q * S within one launch: there is no separate
+ * limit); Q == 0 is a no-op.  The device forms are asynchronous on the set's stream until sa_hip_token_shards_sync and chain behind
+ * sa_hip_token_shards_spans_batch_device without a host trip; they trust nothing: spans are clamped per shard, every loop is
+ * bounded, and an array that is not the suffix array gives unspecified entries, never an access outside the buffers.  The host
+ * forms stage through buffers of the set. */
+typedef struct sa_hip_token_shards_top {
+    uint32_t written;   /* entries written, = min(k, distinct)                                        */
+    uint32_t distinct;  /* merged next symbols among the walked continuations                         */
+    uint32_t length;    /* the largest `length` among the context's S spans (as sa_hip_token_shards_next.length) */
+    uint32_t shards;    /* shards with total_s > 0                                                    */
+    uint64_t covered;   /* sum of the written counts                                                  */
+    uint64_t total;     /* sum over s of total_s; walked = budget ? min(total, budget) : total       */
+} sa_hip_token_shards_top;
+
+typedef struct sa_hip_token_shards_top_stats {
+    uint64_t q;            /* contexts of the last top or sample launch                         */
+    double   spans_ms;     /* HIP-event time of the last spans launch (the call waits for it)   */
+    double   top_ms;       /* ... of the last top launch                                        */
+    double   sample_ms;    /* ... of the last sample launch                                     */
+} sa_hip_token_shards_top_stats;
+
+/* spans_dev: sa_hip_token_span[S * Q]; symbols_dev: int32[Q * k]; counts_dev: uint64[Q * k]; heads_dev: sa_hip_token_shards_top[Q]. */
+int sa_hip_token_shards_top_batch_device(sa_hip_token_shards* set, const void* spans_dev, uint64_t Q, uint32_t k, uint64_t budget,
+                                         void* symbols_dev, void* counts_dev, void* heads_dev);
+/* Both steps from host contexts: spans[S * Q] (may be NULL), symbols, counts and heads out. */
+int sa_hip_token_shards_top_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                  int mode, uint32_t max_length, int need_next, uint32_t k, uint64_t budget,
+                                  sa_hip_token_span* spans, int32_t* symbols, uint64_t* counts, sa_hip_token_shards_top* heads);
+/* draws_dev: uint64[Q * m]; symbols_dev: int32[Q * m]; shards_dev and ranks_dev: uint32[Q * m], each may be NULL. */
+int sa_hip_token_shards_sample_batch_device(sa_hip_token_shards* set, const void* spans_dev, uint64_t Q, const void* draws_dev,
+                                            uint32_t m, void* symbols_dev, void* shards_dev, void* ranks_dev);
+/* Both steps from host contexts and host draws: spans[S * Q] (may be NULL), symbols, shards_out and ranks (may be NULL) out. */
+int sa_hip_token_shards_sample_batch(sa_hip_token_shards* set, const int32_t* patterns, const uint64_t* offsets, uint64_t Q,
+                                     int mode, uint32_t max_length, int need_next, const uint64_t* draws, uint32_t m,
+                                     sa_hip_token_span* spans, int32_t* symbols, uint32_t* shards_out, uint32_t* ranks);
+int sa_hip_token_shards_top_info(const sa_hip_token_shards* set, sa_hip_token_shards_top_stats* out);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 
 /* Per-build statistics of the last build on this handle (roofline accounting). */

@@ -29,6 +29,8 @@ SHARDS_NEXT_DTYPE = np.dtype([("written", "<u4"), ("length", "<u4"), ("covered",
 SHARDS_MATCH_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("count", "<u8")])                      # sa_hip_token_shards_match
 SHARDS_SCORE_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("context_count", "<u8"),
                                ("token_count", "<u8")])                                                    # sa_hip_token_shards_score
+SHARDS_TOP_DTYPE = np.dtype([("written", "<u4"), ("distinct", "<u4"), ("length", "<u4"), ("shards", "<u4"), ("covered", "<u8"),
+                             ("total", "<u8")])                                                            # sa_hip_token_shards_top
 SHARDS_LOCATE_DTYPE = np.dtype([("written", "<u4"), ("reserved", "<u4"), ("count", "<u8")])                  # sa_hip_token_shards_locate
 SHARDS_DOCS_DTYPE = np.dtype([("written", "<u4"), ("reserved", "<u4"), ("examined", "<u8"), ("distinct", "<u8"),
                               ("count", "<u8")])                                                            # sa_hip_token_shards_docs
@@ -79,6 +81,8 @@ EXPORTS = [
     "sa_hip_token_shards_match_docs_batch", "sa_hip_token_shards_match_info",
     "sa_hip_token_shards_score_batch_device", "sa_hip_token_shards_score_docs_batch_device", "sa_hip_token_shards_score_batch",
     "sa_hip_token_shards_score_info",
+    "sa_hip_token_shards_top_batch_device", "sa_hip_token_shards_top_batch", "sa_hip_token_shards_sample_batch_device",
+    "sa_hip_token_shards_sample_batch", "sa_hip_token_shards_top_info",
     "sa_hip_token_shards_set_documents", "sa_hip_token_shards_adopt_documents", "sa_hip_token_shards_doc_bases",
     "sa_hip_token_shards_docs_info", "sa_hip_token_shards_locate_batch_device", "sa_hip_token_shards_locate_batch",
     "sa_hip_token_shards_docs_batch_device", "sa_hip_token_shards_docs_batch", "sa_hip_token_shards_docs_merge_device",
@@ -331,6 +335,19 @@ class TokenShardsScoreStats(C.Structure):
     """sa_hip_token_shards_score_stats: the last match, score and score-docs launches of a shard set."""
     _fields_ = [("q", C.c_uint64), ("positions", C.c_uint64), ("match_ms", C.c_double), ("score_ms", C.c_double),
                 ("docs_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenShardsTop(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("distinct", C.c_uint32), ("length", C.c_uint32), ("shards", C.c_uint32),
+                ("covered", C.c_uint64), ("total", C.c_uint64)]
+
+
+class TokenShardsTopStats(C.Structure):
+    """sa_hip_token_shards_top_stats: the last spans, top and sample launches of a shard set."""
+    _fields_ = [("q", C.c_uint64), ("spans_ms", C.c_double), ("top_ms", C.c_double), ("sample_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -740,6 +757,16 @@ def lib():
     L.sa_hip_token_shards_score_batch.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, vp, vp]
     L.sa_hip_token_shards_score_info.restype = C.c_int
     L.sa_hip_token_shards_score_info.argtypes = [vp, C.POINTER(TokenShardsScoreStats)]
+    L.sa_hip_token_shards_top_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_top_batch_device.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, vp, vp]
+    L.sa_hip_token_shards_top_batch.restype = C.c_int
+    L.sa_hip_token_shards_top_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, u64, vp, vp, vp, vp]
+    L.sa_hip_token_shards_sample_batch_device.restype = C.c_int
+    L.sa_hip_token_shards_sample_batch_device.argtypes = [vp, vp, u64, vp, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_shards_sample_batch.restype = C.c_int
+    L.sa_hip_token_shards_sample_batch.argtypes = [vp, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, vp, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_shards_top_info.restype = C.c_int
+    L.sa_hip_token_shards_top_info.argtypes = [vp, C.POINTER(TokenShardsTopStats)]
     L.sa_hip_token_shards_set_documents.restype = C.c_int
     L.sa_hip_token_shards_set_documents.argtypes = [vp, vp, vp]
     L.sa_hip_token_shards_adopt_documents.restype = C.c_int
@@ -1947,6 +1974,51 @@ class TokenShards(_TokenHandle):
 
     def score_info(self):
         return self._info(self._lib.sa_hip_token_shards_score_info, TokenShardsScoreStats)
+
+    def top_batch_device(self, spans_dev_ptr, q, k, budget, symbols_dev_ptr, counts_dev_ptr, heads_dev_ptr):
+        """The k most frequent next symbols of q contexts from their S * q device spans, counts summed over the shards (among the
+        first `budget` merged continuations of each; 0: all); asynchronous on the set's stream until sync()."""
+        check(self._lib.sa_hip_token_shards_top_batch_device(self._h, spans_dev_ptr, q, int(k), int(budget), symbols_dev_ptr, counts_dev_ptr,
+                                                             heads_dev_ptr))
+
+    def top_batch(self, patterns, k=8, mode=0, max_length=0, need_next=True, budget=0, fill=0):
+        """Spans as in spans_batch, then the k (1 .. 64) most frequent next symbols over all shards.  -> dict: spans [S, Q], symbols
+        int32[Q, k] and counts uint64[Q, k] sorted by count descending, then symbol ascending, heads (written, distinct, length,
+        shards, covered, total)[Q].  Cells beyond heads['written'] keep `fill`."""
+        buf, off, q = self._contexts(patterns)
+        k = int(k)
+        spans, heads = self._shard_rows(q, SPAN_DTYPE), _rows(q, SHARDS_TOP_DTYPE)
+        sym, cnt = _rows(q, np.int32, k, fill), _rows(q, np.uint64, k, fill)
+        self._call(q, self._lib.sa_hip_token_shards_top_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)), k,
+                   int(budget), _ptr(spans), _ptr(sym), _ptr(cnt), _ptr(heads))
+        return {"spans": spans[:, :q], "symbols": sym[:q], "counts": cnt[:q], "heads": heads[:q]}
+
+    def sample_batch_device(self, spans_dev_ptr, q, draws_dev_ptr, m, symbols_dev_ptr, shards_dev_ptr=None, ranks_dev_ptr=None):
+        """m next symbols per context from its S device spans, one per uint64 draw; asynchronous on the set's stream until sync()."""
+        check(self._lib.sa_hip_token_shards_sample_batch_device(self._h, spans_dev_ptr, q, draws_dev_ptr, int(m), symbols_dev_ptr,
+                                                                shards_dev_ptr, ranks_dev_ptr))
+
+    def sample_batch(self, patterns, draws, mode=1, max_length=0, need_next=True, shards=True, ranks=True):
+        """Spans as in spans_batch, then one next symbol per draw: draws uint64[Q, m] (or [Q]: m = 1) pick continuation
+        floor(draw * total / 2^64) of the context's total, the continuations numbered shard by shard.  -> dict: spans [S, Q],
+        symbols int32[Q, m] (-1 where nothing follows), shards and ranks uint32[Q, m] (0xFFFFFFFF there; None when not asked for)."""
+        buf, off, q = self._contexts(patterns)
+        draws = np.ascontiguousarray(draws, dtype=np.uint64)
+        if draws.ndim == 1:
+            draws = draws.reshape(-1, 1)
+        if draws.ndim != 2 or draws.shape[0] != q or (q and draws.shape[1] == 0):
+            raise ValueError("draws: uint64[Q, m], m >= 1")
+        m = draws.shape[1]
+        spans = self._shard_rows(q, SPAN_DTYPE)
+        sym = _rows(q, np.int32, m)
+        sh = _rows(q, np.uint32, m) if shards else None
+        rk = _rows(q, np.uint32, m) if ranks else None
+        self._call(q, self._lib.sa_hip_token_shards_sample_batch, _ptr(buf), _ptr(off), q, int(mode), int(max_length), int(bool(need_next)),
+                   _ptr(draws), m, _ptr(spans), _ptr(sym), _ptr(sh), _ptr(rk))
+        return {"spans": spans[:, :q], "symbols": sym[:q], "shards": sh[:q] if shards else None, "ranks": rk[:q] if ranks else None}
+
+    def top_info(self):
+        return self._info(self._lib.sa_hip_token_shards_top_info, TokenShardsTopStats)
 
     def set_documents(self, starts):
         """starts: one table per shard as TokenIndex.set_documents takes it (every table is checked before a shard is touched);

@@ -1,7 +1,8 @@
 // capi_token_shards.hpp -- the C ABI of the shard set (include/sa_hip.h section 6c), included by sa_capi.hip behind capi_token.hpp
 // (same translation unit).  The kernels are csrc/token_shards.hpp; the per-shard next symbols are tq::launch_next of every shard.
 // Matching statistics over the set: capi_token_shard_match.hpp; documents over the set: capi_token_shard_docs.hpp; per-document
-// counts and AND groups over the set: capi_token_shard_all.hpp; infinity-gram scores over the set: capi_token_shard_score.hpp.
+// counts and AND groups over the set: capi_token_shard_all.hpp; infinity-gram scores over the set: capi_token_shard_score.hpp;
+// top-k next symbols and draws over the set: capi_token_shard_top.hpp.
 // The stopwatches, the upload of a host batch and token_rows_out are capi_token.hpp's.  What the families of the set share is here:
 // the spans of a host batch (shards_stage_spans) and the walk of a chunked call (shards_chunks: chunk size, per-chunk stopwatch,
 // output pointers of the host and the device form, the way of a chunk's rows to the caller), which the next symbols, the documents
@@ -65,14 +66,19 @@ struct sa_hip_token_shards {
     DevBuf sc_scores, sc_heads;              // staging of the host form (its per-shard spans go through m_per)
     LaunchTimer tm_sc, tm_sd;                // the last score launches (q: positions) / score docs launch (q: documents)
     u64 sc_last = 0;                         // documents of the last launch of either kind
+    // top-k next symbols and draws (token_shard_top.hpp, capi_token_shard_top.hpp); the host forms stage through o_sym, o_cnt, o_heads
+    bool top_fast = true;                    // SA_HIP_TOKEN_SHARD_TOP_FAST=0: every context through the merge walk, one live shard or not
+    DevBuf tp_draws, tp_at;                  // staging of the host sample form: its draws; shards and ranks, u32[Q * m] each
+    LaunchTimer tm_tp, tm_sm;                // the last top / sample launch
+    u64 tp_last = 0;                         // contexts of the last launch of either kind
 
     const tq::View* table() const { return tab.as<tq::View>(); }
-    std::array<LaunchTimer*, 8> timers() { return {&tm_r, &tm_sp, &tm_mt, &tm_md, &tm_lc, &tm_tf, &tm_sc, &tm_sd}; }
+    std::array<LaunchTimer*, 10> timers() { return {&tm_r, &tm_sp, &tm_mt, &tm_md, &tm_lc, &tm_tf, &tm_sc, &tm_sd, &tm_tp, &tm_sm}; }
     auto buffers() {                         // every DevBuf member above
         return std::array{&tab, &q_pat, &q_off, &r_per, &r_tot, &s_spans, &s_len, &s_tot, &l_sym, &l_cnt, &l_heads, &l_list, &o_sym, &o_cnt,
                           &o_heads, &m_ms, &m_per, &m_merged, &m_pos, &m_out, &m_heads, &dtab, &dbase, &d_docs, &d_offs, &d_heads, &d_sum,
                           &od_docs, &od_offs, &od_heads, &rtab, &a_docs, &a_offs, &a_heads, &a_plan, &a_groups, &a_sum, &oa_heads, &c_docs,
-                          &c_cnt, &c_wr, &a_goff, &sc_w, &sc_scores, &sc_heads};
+                          &c_cnt, &c_wr, &a_goff, &sc_w, &sc_scores, &sc_heads, &tp_draws, &tp_at};
     }
 };
 
@@ -225,6 +231,7 @@ int sa_hip_token_shards_create(sa_hip_token_shards** out, sa_hip_token_index* co
     if (!g) return fail(SA_HIP_ENOMEM, who, "host allocation");
     g->device = device;
     if (const char* e = diag_env("SA_HIP_TOKEN_SHARD_CHUNK")) g->chunk_knob = strtoull(e, nullptr, 10);
+    if (const char* e = diag_env("SA_HIP_TOKEN_SHARD_TOP_FAST")) g->top_fast = atoi(e) != 0;
     auto run = [&]() -> int {
         SA_HIP_CHECK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
         for (LaunchTimer* w : g->timers()) SA_HIP_CHECK(w->create());

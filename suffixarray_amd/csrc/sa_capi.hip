@@ -1697,6 +1697,7 @@ int sa_hip_read_suffix_array(sa_hip_SuffixArray_struct* s, const char* sa_filena
 #include "capi_token_score.hpp"
 #include "capi_token_top.hpp"
 #include "capi_token_shards.hpp"
+#include "capi_token_shard_top.hpp"
 #include "capi_token_shard_match.hpp"
 #include "capi_token_shard_score.hpp"
 #include "capi_token_shard_docs.hpp"

@@ -7,7 +7,8 @@
 //                     meets every run of a span, most of them far shorter than what is left of the span, which is where the
 //                     jump step starts from).  It never stops at a cap: every run of the walked part is seen; `budget` (0: none)
 //                     cuts the walk to the first `budget` ranks behind the ended suffix, and a run cut by it counts with what
-//                     lies inside.
+//                     lies inside.  The loop is the device function tq_top_walk, which tq_shard_top_kernel (token_shard_top.hpp)
+//                     calls as well for a context whose continuations lie in one shard.
 //                     The table: lane j < k holds one entry as the 64-bit key count << 32 | (0xFFFFFFFF - symbol), larger is
 //                     better, 0 is empty; lanes >= k hold ~0, which is never the minimum.  Symbols of a text are in
 //                     [0, 2^31 - 1] and the runs of a span have distinct symbols, so the keys of a span are distinct and "count
@@ -96,6 +97,47 @@ __device__ __forceinline__ u32 tq_gallop_run(const View& x, int lane, int32_t cu
     return lo + ((u32)__ffsll((unsigned long long)~b) - 1u) * (u32)WAVE;                     // the samples still equal
 }
 
+// The walk of one wave over the ranks [start, end) of x behind the ended suffix, s(r) read at `length`: every completed run is
+// offered to tab (reset by the caller) -> the number of runs.  tq_top_kernel's loop, and the one-shard path of
+// tq_shard_top_kernel (token_shard_top.hpp); start, end and length are wave-uniform.
+__device__ __forceinline__ u32 tq_top_walk(const View& x, int lane, u32 start, u32 end, u32 length, int jump, TopTable& tab) {
+    u32 a = start, distinct = 0, run_start = start;
+    int32_t cur = 0;
+    bool have = false;
+    // every trip advances a by >= 1
+    while (a < end) {
+        const u32 left_n = end - a;
+        const u32 nact = left_n < (u32)WAVE ? left_n : (u32)WAVE;
+        const bool act = (u32)lane < nact;
+        int32_t s = cur;
+        if (act) (void)tq_next_symbol(x, a + lane, length, &s);
+        const int32_t left = lane_shift_up(s, 1);
+        const bool head = act && (lane == 0 ? (!have || s != cur) : s != left);
+        const u64 hb = __ballot(head);
+        if (hb == 0) {
+            // the window is all the running symbol
+            u32 lo = a + nact - 1;                       // known to hold cur; (lo, end): not known
+            if (jump && end - lo - 1 > NEXT_JUMP_MIN) lo = tq_gallop_run(x, lane, cur, length, lo, end);
+            a = lo + 1;
+            continue;
+        }
+        const int f = __ffsll((unsigned long long)hb) - 1;
+        if (have) tab.offer(top_key(cur, a + (u32)f - run_start), lane);         // the carried run ends at the first head
+        const u64 above = lane == WAVE - 1 ? 0ull : hb & ~((2ull << lane) - 1ull);
+        const u64 ck = head && above ? top_key(s, (u32)(__ffsll((unsigned long long)above) - 1 - lane)) : 0ull;
+        // the completed runs that beat the minimum as it stands; it only rises, and offer() tests again (<= 63 trips)
+        for (u64 m = __ballot(ck > tab.min); m; m &= m - 1) tab.offer(top_readlane(ck, __ffsll((unsigned long long)m) - 1), lane);
+        const int last = 63 - __clzll((unsigned long long)hb);
+        cur = __shfl(s, last);
+        run_start = a + (u32)last;
+        have = true;
+        distinct += (u32)__popcll(hb);
+        a += nact;
+    }
+    if (have) tab.offer(top_key(cur, end - run_start), lane);                    // the last run
+    return distinct;
+}
+
 // One wave per span.
 __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_top_kernel(View x, TopArgs g, const int jump) {
     const int lane = threadIdx.x & (WAVE - 1);
@@ -110,40 +152,7 @@ __global__ __launch_bounds__(NEXT_WAVES * WAVE) void tq_top_kernel(View x, TopAr
         const u32 end = g.budget && g.budget < k.end - start ? start + g.budget : k.end;
         TopTable tab;
         tab.reset(lane, g.k);
-        u32 a = start, distinct = 0, run_start = start;
-        int32_t cur = 0;
-        bool have = false;
-        // every trip advances a by >= 1
-        while (a < end) {
-            const u32 left_n = end - a;
-            const u32 nact = left_n < (u32)WAVE ? left_n : (u32)WAVE;
-            const bool act = (u32)lane < nact;
-            int32_t s = cur;
-            if (act) (void)tq_next_symbol(x, a + lane, k.length, &s);
-            const int32_t left = lane_shift_up(s, 1);
-            const bool head = act && (lane == 0 ? (!have || s != cur) : s != left);
-            const u64 hb = __ballot(head);
-            if (hb == 0) {
-                // the window is all the running symbol
-                u32 lo = a + nact - 1;                       // known to hold cur; (lo, end): not known
-                if (jump && end - lo - 1 > NEXT_JUMP_MIN) lo = tq_gallop_run(x, lane, cur, k.length, lo, end);
-                a = lo + 1;
-                continue;
-            }
-            const int f = __ffsll((unsigned long long)hb) - 1;
-            if (have) tab.offer(top_key(cur, a + (u32)f - run_start), lane);         // the carried run ends at the first head
-            const u64 above = lane == WAVE - 1 ? 0ull : hb & ~((2ull << lane) - 1ull);
-            const u64 ck = head && above ? top_key(s, (u32)(__ffsll((unsigned long long)above) - 1 - lane)) : 0ull;
-            // the completed runs that beat the minimum as it stands; it only rises, and offer() tests again (<= 63 trips)
-            for (u64 m = __ballot(ck > tab.min); m; m &= m - 1) tab.offer(top_readlane(ck, __ffsll((unsigned long long)m) - 1), lane);
-            const int last = 63 - __clzll((unsigned long long)hb);
-            cur = __shfl(s, last);
-            run_start = a + (u32)last;
-            have = true;
-            distinct += (u32)__popcll(hb);
-            a += nact;
-        }
-        if (have) tab.offer(top_key(cur, end - run_start), lane);                    // the last run
+        const u32 distinct = tq_top_walk(x, lane, start, end, k.length, jump, tab);
         const u64 mine = (u32)lane < g.k ? tab.key : 0ull;
         const u64 live = __ballot(mine != 0);
         u32 rank = 0;                                                                // live keys above mine (<= 64 trips)

@@ -5,6 +5,8 @@
     sti.positions([464, 2068], limit=10)           # (shard, position) pairs
     sti.next_token_counts([464, 2068])             # {token: count} of what follows the n-gram anywhere
     sti.next_tokens(contexts, cap=64, longest_suffix=True)    # backing off to the longest suffix that ANY shard holds
+    sti.top_next_tokens(contexts, k=8)             # the k most frequent next tokens over all shards, exact uint64 counts
+    sti.sample_next(contexts, samples=4, seed=0)   # next tokens drawn with the probability they have over the whole corpus
     sti.matching_statistics([doc])                 # per position: the longest match in any shard, its count, the shards that hold it
     sti.matched_spans([doc], min_length=8)         # the maximal verbatim spans of a text; sti.coverage([doc], 8): how much they cover
     sti.infgram([doc])                             # per position: the longest context any shard holds, its count, the token's count
@@ -18,7 +20,7 @@
     sti.count_documents_with_all([[[464, 2068], [11]]])          # (matched uint64[G], exact flags)
 
 The corpus is cut by the caller, at document boundaries: an n-gram never spans two shards, so its count is the sum of the shards'
-counts.  On top of include/sa_hip.h sections 6c, 6g, 6h and 6j (suffixarray_amd._capi.TokenShards).  No CPU fallback.
+counts.  On top of include/sa_hip.h sections 6c, 6g, 6h, 6j and 6l (suffixarray_amd._capi.TokenShards).  No CPU fallback.
 """
 import numpy as np
 
@@ -91,6 +93,33 @@ class ShardedTokenIndex:
         r = self.next_tokens([list(ngram)], cap=cap, longest_suffix=longest_suffix, max_length=max_length)
         w = int(r["written"][0])
         return {int(s): int(c) for s, c in zip(r["symbols"][0, :w], r["counts"][0, :w])}
+
+    def top_next_tokens(self, ngrams, k=8, longest_suffix=False, max_length=None, budget=None):
+        """As TokenIndex.top_next_tokens over all shards: the k (1 .. 64) most frequent tokens behind every n-gram, their counts
+        summed over the shards.  -> dict of arrays: symbols int32[Q, k] and counts uint64[Q, k], by count descending, ties by token
+        ascending, of which the first written[i] = min(k, distinct[i]) are valid in row i; distinct[i] = the distinct next tokens,
+        covered[i] = the sum of the written counts and total[i] = occurrences that have a next token (uint64 both), length[i] =
+        matched symbols, shards[i] = the shards that hold a continuation; spans as in _capi.TokenShards.spans_batch, [S, Q].
+        budget: only the first `budget` occurrences in the order of a single index over the whole corpus are walked (the tokens
+        with the smallest ids); exact[i] = every occurrence was walked, so row i is the true top-k.  longest_suffix: as in
+        next_tokens."""
+        r = self._set.top_batch(ngrams, k=k, mode=1 if longest_suffix else 0, max_length=max_length or 0, need_next=True, budget=budget or 0)
+        h = r["heads"]
+        return {"symbols": r["symbols"], "counts": r["counts"], "written": h["written"].copy(), "distinct": h["distinct"].copy(),
+                "covered": h["covered"].copy(), "total": h["total"].copy(), "length": h["length"].copy(), "shards": h["shards"].copy(),
+                "exact": h["total"] <= np.uint64(budget or 2 ** 64 - 1), "spans": r["spans"]}
+
+    def sample_next(self, ngrams, draws=None, samples=1, seed=None, longest_suffix=True, max_length=None):
+        """As TokenIndex.sample_next over all shards: next tokens drawn with the probability they have over the whole corpus,
+        int32[Q, samples], -1 where nothing follows.  draws: uint64[Q, samples] (or [Q]), draw d picks the occurrence
+        floor(d * total / 2^64) of the context's total, the occurrences numbered shard by shard and in suffix order inside a shard
+        -- the same draws give the same tokens; without them they come from np.random.default_rng(seed).  longest_suffix: a
+        context backs off to its longest suffix (at most max_length symbols) that has a next token in some shard."""
+        q = len(ngrams[1]) - 1 if isinstance(ngrams, tuple) else len(ngrams)
+        if draws is None:
+            draws = np.random.default_rng(seed).integers(0, 2 ** 64, size=(q, int(samples)), dtype=np.uint64)
+        return self._set.sample_batch(ngrams, draws, mode=1 if longest_suffix else 0, max_length=max_length or 0, need_next=True,
+                                      shards=False, ranks=False)["symbols"]
 
     def matching_statistics(self, docs, max_length=None):
         """Which parts of query texts stand verbatim in some shard.  docs: a list of int sequences.  -> one (length, count, shards)
