@@ -926,6 +926,80 @@ int sa_hip_token_index_all_batch(sa_hip_token_index* t, const int32_t* patterns,
                                  uint32_t cap, uint32_t budget, sa_hip_token_span* spans, int32_t* docs, int32_t* offs,
                                  sa_hip_token_all* heads);
 
+/* (6m) CNF document queries (csrc/token_cnf.hpp, csrc/capi_token_cnf.hpp): which documents satisfy an AND of clauses, every clause
+ * an OR of n-grams, some clauses negated -- "(`New York` OR `NYC`) AND `subway`, but not `boilerplate`".  The AND query of (6e) is
+ * its case of one literal per clause; it stays on its own kernel.  Needs the documents of (6d) and RK of (6e).  All results are exact.
+ *
+ * spans[S] are the literals.  The HOST table clause_offsets[C + 1] cuts them into C clauses, the HOST table group_offsets[G + 1] cuts
+ * the clauses into G groups, one query per group; negated[C] (HOST, uint8; NULL: no clause is negated) marks clause c as an exclusion
+ * with 1.  All three are copied by the call.  Every clause has >= 1 literal, every group has 1 .. SA_HIP_TOKEN_CNF_MAX_CLAUSES clauses,
+ * at most SA_HIP_TOKEN_CNF_MAX_LITERALS literals and at least one clause that is not negated.
+ *
+ * A document MATCHES a group iff for every positive clause it holds a rank of at least one of the clause's literals, and for every
+ * negated clause it holds a rank of none of its literals.
+ *
+ *   driver      the positive clause with the smallest sum of its literals' counts (formed in 64 bits), the lowest clause index on a
+ *               tie.  A negated clause is never the driver, whatever its sum.  `count` is that sum.  A positive clause whose literals
+ *               are all empty has the sum 0 and is therefore the driver: written, matched, candidates, duplicates, examined and count
+ *               are 0 then (driver and literals still name the clause), as in (6e).
+ *   walk        examined = budget ? min(count, budget) : count ranks.  The driver's literals are walked in literal order, each from
+ *               its own `first`, and the budget is consumed in that order: an earlier literal is walked whole before a later one
+ *               starts.  A walked rank r of literal l = [a_l, ..) is a first occurrence iff PV[r] < a_l.  A first occurrence is a
+ *               duplicate iff its document holds a rank of an earlier literal l' < l of the driver clause (of that literal's WHOLE
+ *               range: l' was walked whole before l began, so the document was listed there); otherwise it is a candidate.  The candidates are exactly the distinct documents of the
+ *               union of the walked pieces, each at its first literal and there at its smallest rank.
+ *   match       a candidate matches iff every other clause is satisfied.  Clauses are probed in clause order, literals in literal
+ *               order; a positive clause stops at its first literal that holds the document, a negated one fails at it.
+ *   output      the first min(matched, cap) matches in literal order, then rank order: docs[g * cap + j] the document and
+ *               offsets[g * cap + j] = SA[r] - starts[doc] for the rank r that made it a candidate.  cap == 0 counts only; docs and
+ *               offsets may then be NULL and are never touched.  Slots beyond `written` are not written.  matched is the exact
+ *               number of matching documents iff examined == count.  (duplicates is a count of up to 63 first occurrences per
+ *               document and is kept modulo 2^32.)
+ *
+ * `written` comes first in the head, so heads_dev chains into sa_hip_token_index_doc_counts_batch_device as written_dev with the
+ * stride sizeof(sa_hip_token_cnf) = 48.
+ *
+ * Errors returned as -1 before any HIP call, the message naming the call: those (6e) lists for `all` -- a NULL handle or a NULL
+ * required pointer, a handle without documents or without RK, mode or need_next other than 0 / 1, descending offsets, G * cap, S, C or
+ * G >= 2^31 --, a clause table that does not start at 0 or end at S or holds an empty clause, a group table that does not start at 0
+ * or end at C or holds an empty group, a group of more than 16 clauses or more than 64 literals, a group with no positive clause, a
+ * negated byte other than 0 / 1.  G == 0 with good arguments is a no-op returning 0.  The device form takes the spans exactly as
+ * sa_hip_token_index_spans_batch_device writes them (any rank range is a literal) and is asynchronous until sa_hip_token_index_sync;
+ * it trusts nothing on the device: spans are clamped, group and clause sizes are clamped, every search is bounded.  The host form
+ * runs the span step first and stages through buffers of the handle. */
+#define SA_HIP_TOKEN_CNF_MAX_CLAUSES 16
+#define SA_HIP_TOKEN_CNF_MAX_LITERALS 64
+
+typedef struct sa_hip_token_cnf {
+    uint32_t written;     /* min(matched, cap)                                                     */
+    uint32_t matched;     /* candidates that satisfy every other clause                            */
+    uint32_t candidates;  /* distinct documents among the examined ranks of the driver clause      */
+    uint32_t duplicates;  /* first occurrences whose document an earlier literal of the driver has */
+    uint32_t driver;      /* index inside the group of the clause that was walked                  */
+    uint32_t literals;    /* literals of that clause                                               */
+    uint64_t examined;    /* ranks walked: budget ? min(count, budget) : count                     */
+    uint64_t count;       /* sum of the driver's literal counts                                    */
+    uint64_t reserved;    /* 0                                                                     */
+} sa_hip_token_cnf;
+
+typedef struct sa_hip_token_cnf_info {
+    uint64_t q;           /* groups of the last cnf launch                                         */
+    double   ms;          /* HIP-event time of it                                                  */
+} sa_hip_token_cnf_info;
+
+/* spans_dev: sa_hip_token_span[S]; clause_offsets_host: uint64[C + 1]; negated_host: uint8[C] or NULL; group_offsets_host:
+ * uint64[G + 1]; docs_dev, offsets_dev: int32[G * cap] (may be NULL when cap == 0); heads_dev: sa_hip_token_cnf[G]. */
+int sa_hip_token_index_cnf_batch_device(sa_hip_token_index* t, const void* spans_dev, uint64_t S,
+                                        const uint64_t* clause_offsets_host, uint64_t C, const uint8_t* negated_host,
+                                        const uint64_t* group_offsets_host, uint64_t G, uint32_t cap, uint32_t budget,
+                                        void* docs_dev, void* offsets_dev, void* heads_dev);
+/* Both steps from S host patterns: spans[S] (may be NULL), docs, offs and heads[G] out. */
+int sa_hip_token_index_cnf_batch(sa_hip_token_index* t, const int32_t* patterns, const uint64_t* offsets, uint64_t S,
+                                 const uint64_t* clause_offsets, uint64_t C, const uint8_t* negated, const uint64_t* group_offsets,
+                                 uint64_t G, int mode, uint32_t max_length, int need_next, uint32_t cap, uint32_t budget,
+                                 sa_hip_token_span* spans, int32_t* docs, int32_t* offs, sa_hip_token_cnf* heads);
+int sa_hip_token_index_cnf_info(const sa_hip_token_index* t, sa_hip_token_cnf_info* out);
+
 /* (6f) matching statistics (csrc/token_match.hpp, csrc/capi_token_match.hpp): which parts of a query text stand verbatim in the
  * corpus.  For every position of the text the longest prefix of what follows that the corpus holds, with its range and count, and
  * per query document the maximal matches, the longest one and the tokens they cover.  All results are exact.

@@ -25,6 +25,10 @@ SCORE_HEAD_DTYPE = np.dtype([("scored", "<u4"), ("seen", "<u4"), ("certain", "<u
                              ("length_sum", "<u8")])                                                       # sa_hip_token_score_head
 TOP_DTYPE = np.dtype([("written", "<u4"), ("distinct", "<u4"), ("covered", "<u4"), ("total", "<u4")])       # sa_hip_token_top
 TOKEN_ALL_MAX = 16                                                                                         # SA_HIP_TOKEN_ALL_MAX
+CNF_DTYPE = np.dtype([("written", "<u4"), ("matched", "<u4"), ("candidates", "<u4"), ("duplicates", "<u4"), ("driver", "<u4"),
+                      ("literals", "<u4"), ("examined", "<u8"), ("count", "<u8"), ("reserved", "<u8")])      # sa_hip_token_cnf
+TOKEN_CNF_MAX_CLAUSES = 16                                                                                 # SA_HIP_TOKEN_CNF_MAX_CLAUSES
+TOKEN_CNF_MAX_LITERALS = 64                                                                                # SA_HIP_TOKEN_CNF_MAX_LITERALS
 SHARDS_NEXT_DTYPE = np.dtype([("written", "<u4"), ("length", "<u4"), ("covered", "<u8"), ("total", "<u8")])  # sa_hip_token_shards_next
 SHARDS_MATCH_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("count", "<u8")])                      # sa_hip_token_shards_match
 SHARDS_SCORE_DTYPE = np.dtype([("length", "<u4"), ("shards", "<u4"), ("context_count", "<u8"),
@@ -67,6 +71,7 @@ EXPORTS = [
     "sa_hip_token_index_prepare_doc_ranks", "sa_hip_token_index_get_doc_ranks", "sa_hip_token_index_doc_ranks_info",
     "sa_hip_token_index_doc_counts_batch_device", "sa_hip_token_index_doc_counts_batch", "sa_hip_token_index_all_batch_device",
     "sa_hip_token_index_all_batch",
+    "sa_hip_token_index_cnf_batch_device", "sa_hip_token_index_cnf_batch", "sa_hip_token_index_cnf_info",
     "sa_hip_token_index_match_batch_device", "sa_hip_token_index_match_docs_batch_device", "sa_hip_token_index_match_batch",
     "sa_hip_token_index_match_docs_batch", "sa_hip_token_index_match_info",
     "sa_hip_token_index_score_batch_device", "sa_hip_token_index_score_docs_batch_device", "sa_hip_token_index_score_batch",
@@ -255,6 +260,20 @@ class TokenDocRanksInfo(C.Structure):
     """sa_hip_token_doc_ranks_info: the rank-by-document array of a token index and its last doc_counts and all launches."""
     _fields_ = [("present", C.c_uint32), ("sort_passes", C.c_uint32), ("bytes", C.c_uint64), ("prepare_ms", C.c_double),
                 ("counts_q", C.c_uint64), ("counts_ms", C.c_double), ("all_q", C.c_uint64), ("all_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TokenCnf(C.Structure):
+    _fields_ = [("written", C.c_uint32), ("matched", C.c_uint32), ("candidates", C.c_uint32), ("duplicates", C.c_uint32),
+                ("driver", C.c_uint32), ("literals", C.c_uint32), ("examined", C.c_uint64), ("count", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
+class TokenCnfInfo(C.Structure):
+    """sa_hip_token_cnf_info: the last cnf launch of a token index."""
+    _fields_ = [("q", C.c_uint64), ("ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -687,6 +706,13 @@ def lib():
     L.sa_hip_token_index_all_batch_device.argtypes = [vp, vp, u64, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.sa_hip_token_index_all_batch.restype = C.c_int
     L.sa_hip_token_index_all_batch.argtypes = [vp, vp, vp, u64, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.sa_hip_token_index_cnf_batch_device.restype = C.c_int
+    L.sa_hip_token_index_cnf_batch_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.sa_hip_token_index_cnf_batch.restype = C.c_int
+    L.sa_hip_token_index_cnf_batch.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, u64, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                               vp, vp, vp, vp]
+    L.sa_hip_token_index_cnf_info.restype = C.c_int
+    L.sa_hip_token_index_cnf_info.argtypes = [vp, C.POINTER(TokenCnfInfo)]
     L.sa_hip_token_index_match_batch_device.restype = C.c_int
     L.sa_hip_token_index_match_batch_device.argtypes = [vp, vp, vp, u64, u64, C.c_uint32, vp]
     L.sa_hip_token_index_match_docs_batch_device.restype = C.c_int
@@ -1730,6 +1756,45 @@ class TokenIndex(_TokenHandle):
         self._call(g, self._lib.sa_hip_token_index_all_batch, _ptr(buf), _ptr(off), s, go.ctypes.data, g, int(mode), int(max_length),
                    int(bool(need_next)), cap, int(budget), _ptr(spans), _ptr(docs), _ptr(offs), _ptr(heads))
         return {"spans": spans[:s], "docs": docs[:g], "offsets": offs[:g], "heads": heads[:g]}
+
+    @staticmethod
+    def _cnf_tables(clause_offsets, negated, group_offsets):
+        """-> (uint64 clause offsets, uint8 negated or None, uint64 group offsets), contiguous"""
+        co = np.ascontiguousarray(clause_offsets, dtype=np.uint64)
+        go = np.ascontiguousarray(group_offsets, dtype=np.uint64)
+        ng = None if negated is None else np.ascontiguousarray(negated, dtype=np.uint8)
+        if ng is not None and ng.size != max(co.size - 1, 0):
+            raise ValueError("negated: one byte per clause")
+        return co, ng, go
+
+    def cnf_batch_device(self, spans_dev_ptr, s, clause_offsets, negated, group_offsets, cap, budget, docs_dev_ptr, offsets_dev_ptr,
+                         heads_dev_ptr):
+        """Documents that satisfy every group's CNF query over device spans (the literals).  clause_offsets uint64[C + 1], negated
+        uint8[C] or None and group_offsets uint64[G + 1] are HOST arrays (copied by the call), everything else is on the device (cap
+        0: counts only, docs and offsets may be None); heads are CNF_DTYPE; asynchronous until sync()."""
+        co, ng, go = self._cnf_tables(clause_offsets, negated, group_offsets)
+        check(self._lib.sa_hip_token_index_cnf_batch_device(self._h, spans_dev_ptr, int(s), co.ctypes.data, max(co.size - 1, 0),
+                                                            None if ng is None else ng.ctypes.data, go.ctypes.data, max(go.size - 1, 0),
+                                                            int(cap), int(budget), docs_dev_ptr, offsets_dev_ptr, heads_dev_ptr))
+
+    def cnf_batch(self, patterns, clause_offsets, negated, group_offsets, cap=16, budget=0, mode=0, max_length=0, need_next=False, fill=0):
+        """Spans as in spans_batch (the literals), cut into clauses by clause_offsets (uint64[C + 1]) and the clauses into groups by
+        group_offsets (uint64[G + 1]: 1 .. TOKEN_CNF_MAX_CLAUSES clauses and at most TOKEN_CNF_MAX_LITERALS literals each); negated
+        uint8[C] or None marks exclusions.  -> dict: spans [S], docs int32[G, cap], offsets int32[G, cap], heads CNF_DTYPE[G].  Cells
+        beyond heads['written'] keep `fill`."""
+        buf, off, s = self._contexts(patterns)
+        co, ng, go = self._cnf_tables(clause_offsets, negated, group_offsets)
+        c, g = max(co.size - 1, 0), max(go.size - 1, 0)
+        cap = int(cap)
+        spans, heads = _rows(s, SPAN_DTYPE), _rows(g, CNF_DTYPE)
+        docs, offs = _rows(g, np.int32, cap, fill), _rows(g, np.int32, cap, fill)
+        self._call(g, self._lib.sa_hip_token_index_cnf_batch, _ptr(buf), _ptr(off), s, co.ctypes.data, c, None if ng is None else ng.ctypes.data,
+                   go.ctypes.data, g, int(mode), int(max_length), int(bool(need_next)), cap, int(budget), _ptr(spans), _ptr(docs), _ptr(offs),
+                   _ptr(heads))
+        return {"spans": spans[:s], "docs": docs[:g], "offsets": offs[:g], "heads": heads[:g]}
+
+    def cnf_info(self):
+        return self._info(self._lib.sa_hip_token_index_cnf_info, TokenCnfInfo)
 
     def match_batch_device(self, patterns_dev_ptr, offsets_dev_ptr, q, total, max_length, spans_dev_ptr):
         """The match of every one of the `total` = offsets[q] positions of q device documents (max_length 0: no cap) into

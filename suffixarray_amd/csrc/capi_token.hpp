@@ -1,6 +1,6 @@
 // capi_token.hpp -- the C ABI of the token index (include/sa_hip.h section 6), included by sa_capi.hip (same translation unit).
 // The kernels and the search structures are csrc/token_query.hpp, spans and next symbols csrc/token_next.hpp, documents csrc/token_docs.hpp (their entry points:
-// capi_token_docs.hpp), per-document counts and AND groups csrc/token_all.hpp (capi_token_all.hpp), matching statistics csrc/token_match.hpp
+// capi_token_docs.hpp), per-document counts and AND groups csrc/token_all.hpp (capi_token_all.hpp), CNF queries csrc/token_cnf.hpp (capi_token_cnf.hpp), matching statistics csrc/token_match.hpp
 // (capi_token_match.hpp), infinity-gram scores csrc/token_score.hpp (capi_token_score.hpp), top-k next symbols and draws
 // csrc/token_top.hpp (capi_token_top.hpp); the suffix array of sa_hip_token_index_build comes from
 // the build behind sa_hip_libsais_int_device (capi_dropins.hpp: int_device).
@@ -59,13 +59,20 @@ struct sa_hip_token_index {
     DevBuf tp_draws;                         // staging of the host form's draws
     LaunchTimer tm_tp, tm_sm;                // the last top / sample launch
     u64 tp_last = 0;                         // spans of the last launch of either kind
+    // CNF document queries (token_cnf.hpp, capi_token_cnf.hpp); the host form stages through s_spans, d_docs, d_offs, d_heads
+    DevBuf c_tab;                            // group offsets, clause offsets and negated bytes of the last cnf launch
+    unsigned char* c_pin = nullptr;          // pinned: what the asynchronous copy into c_tab reads
+    size_t c_pin_cap = 0;                    // ... in bytes
+    hipEvent_t c_copied = nullptr;           // that copy is done: the pinned buffer may be rewritten
+    bool c_copy_pending = false;
+    LaunchTimer tm_cnf;                      // the last cnf launch (q: groups)
 
-    std::array<LaunchTimer*, 13> timers() {
-        return {&tm_q, &tm_sp, &tm_nx, &tm_lc, &tm_dc, &tm_tf, &tm_al, &tm_mt, &tm_md, &tm_sc, &tm_sd, &tm_tp, &tm_sm};
+    std::array<LaunchTimer*, 14> timers() {
+        return {&tm_q, &tm_sp, &tm_nx, &tm_lc, &tm_dc, &tm_tf, &tm_al, &tm_mt, &tm_md, &tm_sc, &tm_sd, &tm_tp, &tm_sm, &tm_cnf};
     }
     auto buffers() {                         // every DevBuf member above (x, docs and ranks release their own)
         return std::array{&q_pat, &q_off, &q_out, &s_spans, &s_sym, &s_cnt, &s_heads, &s_list, &d_docs, &d_offs, &d_heads, &a_goff, &a_cnt,
-                          &a_wr, &m_spans, &m_pos, &m_out, &m_heads, &sc_scores, &sc_heads, &tp_draws};
+                          &a_wr, &m_spans, &m_pos, &m_out, &m_heads, &sc_scores, &sc_heads, &tp_draws, &c_tab};
     }
 };
 
@@ -85,6 +92,7 @@ int token_create(sa_hip_token_index** out, int device, const char* who) {
     hipError_t e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
     for (LaunchTimer* w : t->timers()) if (e == hipSuccess) e = w->create();
     if (e == hipSuccess) e = hipEventCreate(&t->a_copied);
+    if (e == hipSuccess) e = hipEventCreate(&t->c_copied);
     if (e != hipSuccess) {
         sa_hip_token_index_destroy(t);
         return fail(e == hipErrorOutOfMemory ? SA_HIP_ENOMEM : SA_HIP_EHIP, who, hipGetErrorString(e));
@@ -217,6 +225,8 @@ void sa_hip_token_index_destroy(sa_hip_token_index* t) {
     for (DevBuf* b : t->buffers()) b->release();
     if (t->a_goff_pin) (void)hipHostFree(t->a_goff_pin);
     if (t->a_copied) (void)hipEventDestroy(t->a_copied);
+    if (t->c_pin) (void)hipHostFree(t->c_pin);
+    if (t->c_copied) (void)hipEventDestroy(t->c_copied);
     for (LaunchTimer* w : t->timers()) w->destroy();
     if (t->stream) (void)hipStreamDestroy(t->stream);
     delete t;

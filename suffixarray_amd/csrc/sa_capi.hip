@@ -4,11 +4,11 @@
 //
 // This file: the index handle with its build, query, record-retrieval, replica, multi-GPU, CSV and on-disk entry points.
 // capi_dropins.hpp (included below, same translation unit): the libsais- / engine-call-compatible entry points, their device
-// forms and the process-level workspace they share.  capi_token.hpp, capi_token_docs.hpp, capi_token_all.hpp, capi_token_match.hpp and
-// capi_token_shards.hpp with capi_token_shard_match.hpp, capi_token_shard_score.hpp, capi_token_shard_docs.hpp and
-// capi_token_shard_all.hpp (included at the end): the token index, its documents, per-document counts and AND groups, matching
-// statistics, and sets of token indexes with their matching statistics, infinity-gram scores, documents, per-document counts and
-// AND groups.
+// forms and the process-level workspace they share.  capi_token.hpp, capi_token_docs.hpp, capi_token_all.hpp, capi_token_cnf.hpp,
+// capi_token_match.hpp and capi_token_shards.hpp with capi_token_shard_match.hpp, capi_token_shard_score.hpp,
+// capi_token_shard_docs.hpp and capi_token_shard_all.hpp (included at the end): the token index, its documents, per-document counts,
+// AND groups and CNF queries, matching statistics, and sets of token indexes with their matching statistics, infinity-gram scores,
+// documents, per-document counts and AND groups.
 #include <array>
 #include <exception>
 #include <mutex>
@@ -1693,6 +1693,7 @@ int sa_hip_read_suffix_array(sa_hip_SuffixArray_struct* s, const char* sa_filena
 #include "capi_token.hpp"
 #include "capi_token_docs.hpp"
 #include "capi_token_all.hpp"
+#include "capi_token_cnf.hpp"
 #include "capi_token_match.hpp"
 #include "capi_token_score.hpp"
 #include "capi_token_top.hpp"

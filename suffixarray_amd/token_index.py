@@ -13,6 +13,7 @@
     ti.documents(ngrams, cap=16)           # which documents, in order of first appearance by rank
     ti.term_counts(ngrams, docs)           # how often every n-gram occurs in every one of these documents: uint32[Q, len(docs)]
     ti.documents_with_all([[[464, 2068], [11]]], cap=16)    # per group of n-grams: the documents that hold all of them
+    ti.documents_with_cnf([[[[464, 2068], [7]], [[11]]]], exclude=[[[13]]])   # (A or B) and C, but not D: the documents
     ti.matching_statistics([text])         # per position of a query text: the longest prefix of what follows that the corpus holds
     ti.matched_spans([text], min_length=8)    # its maximal verbatim spans as (position, length, count, first)
     ti.coverage([text], min_length=8)      # how many of its tokens lie inside such a span, the longest one, how many there are
@@ -127,6 +128,63 @@ class TokenIndex:
             return np.zeros(0, np.uint32), np.zeros(0, np.bool_)
         self.prepare_document_ranks()
         h = self._idx.all_batch(flat, goff, cap=0, budget=budget or 0)["heads"]
+        return h["matched"].copy(), h["examined"] == h["count"]
+
+    @staticmethod
+    def _cnf_tables(queries, exclude):
+        """-> (literals, clause offsets uint64, negated uint8, group offsets uint64) of CNF queries; exclude[i] becomes one negated
+        clause behind the clauses of query i"""
+        if exclude is not None and len(exclude) != len(queries):
+            raise ValueError("exclude: one list of n-grams per query (an empty one or None for no exclusion)")
+        flat, coff, neg, goff = [], [0], [], [0]
+        for i, q in enumerate(queries):
+            clauses = [([list(x) for x in c], 0) for c in q]
+            if not clauses:
+                raise ValueError("a query holds at least one clause")
+            ex = exclude[i] if exclude is not None else None
+            if ex is not None and len(ex):
+                clauses.append(([list(x) for x in ex], 1))
+            if len(clauses) > _capi.TOKEN_CNF_MAX_CLAUSES:
+                raise ValueError("a query holds at most %d clauses, its exclusion included" % _capi.TOKEN_CNF_MAX_CLAUSES)
+            if sum(len(c) for c, _ in clauses) > _capi.TOKEN_CNF_MAX_LITERALS:
+                raise ValueError("a query holds at most %d n-grams" % _capi.TOKEN_CNF_MAX_LITERALS)
+            for c, n in clauses:
+                if not c:
+                    raise ValueError("a clause holds at least one n-gram")
+                flat += c
+                coff.append(len(flat))
+                neg.append(n)
+            goff.append(len(neg))
+        return flat, np.array(coff, np.uint64), np.array(neg, np.uint8), np.array(goff, np.uint64)
+
+    def documents_with_cnf(self, queries, exclude=None, cap=16, budget=None, longest_suffix=False, max_length=None):
+        """Which documents satisfy a CNF query: queries[i] is a list of clauses, a clause a list of n-grams of which the document
+        holds at least one; exclude[i] (optional) is a list of n-grams none of which may occur.  At most 16 clauses (the exclusion
+        counts as one) and 64 n-grams per query.  -> one dict per query: documents and offsets (int32 arrays, at most cap entries:
+        the matching documents in the order of the driver clause's n-grams and then by rank, each with the offset of the occurrence
+        that listed it), matched (how many documents matched among the first `budget` occurrences of the driver clause), exact
+        (these were all its occurrences, so matched is the number of documents that satisfy the query), driver (the index of the
+        clause with the fewest occurrences, which was walked), duplicates (documents met again under a later n-gram of the driver)."""
+        flat, coff, neg, goff = self._cnf_tables(queries, exclude)
+        if not len(queries):
+            return []
+        self.prepare_document_ranks()
+        r = self._idx.cnf_batch(flat, coff, neg, goff, cap=cap, budget=budget or 0, mode=1 if longest_suffix else 0,
+                                max_length=max_length or 0, need_next=False)
+        out = []
+        for i, h in enumerate(r["heads"]):
+            w = int(h["written"])
+            out.append({"documents": r["docs"][i, :w].copy(), "offsets": r["offsets"][i, :w].copy(), "matched": int(h["matched"]),
+                        "exact": bool(h["examined"] == h["count"]), "driver": int(h["driver"]), "duplicates": int(h["duplicates"])})
+        return out
+
+    def count_documents_with_cnf(self, queries, exclude=None, budget=None):
+        """-> (matched uint32[G], exact bool[G]): how many documents satisfy every CNF query"""
+        flat, coff, neg, goff = self._cnf_tables(queries, exclude)
+        if not len(queries):
+            return np.zeros(0, np.uint32), np.zeros(0, np.bool_)
+        self.prepare_document_ranks()
+        h = self._idx.cnf_batch(flat, coff, neg, goff, cap=0, budget=budget or 0)["heads"]
         return h["matched"].copy(), h["examined"] == h["count"]
 
     def ranges(self, ngrams):
