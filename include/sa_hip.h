@@ -623,6 +623,12 @@ const void* sa_hip_token_index_text_dev(const sa_hip_token_index* t);
 const void* sa_hip_token_index_sa_dev(const sa_hip_token_index* t);
 /* Copy SA[first .. first + count) to the host (the positions of a range); first + count > n returns -1. */
 int sa_hip_token_index_get_sa_range(sa_hip_token_index* t, uint64_t first, uint64_t count, int32_t* out_host);
+/* Copy entries [first, first + count) of the first-symbol directory (uint32, dir_entries of them: entry j = number of suffixes
+ * whose first symbol is < min_symbol + j) or of the key array (uint64, n of them: entry r = ((T[p] + 1) << 32) | (p + 1 < n ?
+ * T[p + 1] + 1 : 0), p = SA[r]) to the host, synchronising on the handle's stream.  -1 with a message: the handle has no such
+ * structure (dir_entries == 0 / key_bytes == 0 in sa_hip_token_info), first + count lies beyond it, or a NULL pointer. */
+int sa_hip_token_index_get_dir_range(sa_hip_token_index* t, uint64_t first, uint64_t count, uint32_t* out_host);
+int sa_hip_token_index_get_key_range(sa_hip_token_index* t, uint64_t first, uint64_t count, uint64_t* out_host);
 int sa_hip_token_index_info(const sa_hip_token_index* t, sa_hip_token_info* out);
 
 /* (6b) longest-suffix spans and next-symbol counts (csrc/token_next.hpp): given a context, the longest suffix of it that the text

@@ -62,7 +62,7 @@ EXPORTS = [
     "sa_hip_plcp_int_device", "sa_hip_sufcheck_long_device",
     "sa_hip_token_index_build", "sa_hip_token_index_load_device", "sa_hip_token_index_destroy", "sa_hip_token_index_query_batch",
     "sa_hip_token_index_query_batch_device", "sa_hip_token_index_sync", "sa_hip_token_index_text_dev", "sa_hip_token_index_sa_dev",
-    "sa_hip_token_index_get_sa_range", "sa_hip_token_index_info",
+    "sa_hip_token_index_get_sa_range", "sa_hip_token_index_get_dir_range", "sa_hip_token_index_get_key_range", "sa_hip_token_index_info",
     "sa_hip_token_index_spans_batch", "sa_hip_token_index_spans_batch_device", "sa_hip_token_index_next_batch_device",
     "sa_hip_token_index_next_batch", "sa_hip_token_index_next_of_spans", "sa_hip_token_index_next_info",
     "sa_hip_token_index_set_documents", "sa_hip_token_index_get_doc_range", "sa_hip_token_index_docs_info",
@@ -664,6 +664,10 @@ def lib():
     L.sa_hip_token_index_sa_dev.argtypes = [vp]
     L.sa_hip_token_index_get_sa_range.restype = C.c_int
     L.sa_hip_token_index_get_sa_range.argtypes = [vp, u64, u64, vp]
+    L.sa_hip_token_index_get_dir_range.restype = C.c_int
+    L.sa_hip_token_index_get_dir_range.argtypes = [vp, u64, u64, vp]
+    L.sa_hip_token_index_get_key_range.restype = C.c_int
+    L.sa_hip_token_index_get_key_range.argtypes = [vp, u64, u64, vp]
     L.sa_hip_token_index_info.restype = C.c_int
     L.sa_hip_token_index_info.argtypes = [vp, C.POINTER(TokenInfo)]
     L.sa_hip_token_index_spans_batch.restype = C.c_int
@@ -1467,6 +1471,14 @@ def _rows(q, dtype, cap=None, fill=0):
     return np.full(shape, fill, dtype=dt) if fill else np.zeros(shape, dtype=dt)
 
 
+def _range_args(first, count):
+    """(first, count) of a read-back as non-negative ints (a negative one would reach the library as a huge uint64)"""
+    first, count = int(first), int(count)
+    if first < 0 or count < 0:
+        raise ValueError("first and count are non-negative")
+    return first, count
+
+
 class _TokenHandle:
     """What TokenIndex and TokenShards share: the handle and its release through the library's _destroy, the packing of a host
     batch, the call of a host form and the *_info calls."""
@@ -1561,6 +1573,20 @@ class TokenIndex(_TokenHandle):
     def sa_range(self, first, count):
         out = np.empty(max(count, 1), dtype=np.int32)
         check(self._lib.sa_hip_token_index_get_sa_range(self._h, int(first), int(count), out.ctypes.data))
+        return out[:count]
+
+    def dir_range(self, first, count):
+        """-> uint32 entries [first, first + count) of the first-symbol directory; raises when the handle has none"""
+        first, count = _range_args(first, count)
+        out = np.empty(max(count, 1), dtype=np.uint32)
+        check(self._lib.sa_hip_token_index_get_dir_range(self._h, int(first), int(count), out.ctypes.data))
+        return out[:count]
+
+    def key_range(self, first, count):
+        """-> uint64 entries [first, first + count) of the key array; raises when the handle has none"""
+        first, count = _range_args(first, count)
+        out = np.empty(max(count, 1), dtype=np.uint64)
+        check(self._lib.sa_hip_token_index_get_key_range(self._h, int(first), int(count), out.ctypes.data))
         return out[:count]
 
     def info(self):

@@ -333,6 +333,35 @@ int sa_hip_token_index_get_sa_range(sa_hip_token_index* t, uint64_t first, uint6
     return 0;
 }
 
+// the two search structures as prepare() left them (tests compare them entry by entry with their definitions)
+int sa_hip_token_index_get_dir_range(sa_hip_token_index* t, uint64_t first, uint64_t count, uint32_t* out_host) {
+    const char* who = "sa_hip_token_index_get_dir_range";
+    if (!t || !out_host) return fail(SA_HIP_EINVAL, who, "NULL argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    if (!t->x.dir_entries) return fail(SA_HIP_EINVAL, who, "the handle has no directory");
+    if (first > t->x.dir_entries || count > t->x.dir_entries - first) return fail(SA_HIP_EINVAL, who, "range beyond the directory");
+    if (count == 0) return 0;
+    int rc = set_device(t->device);
+    if (rc) return rc;
+    SA_HIP_CHECK(hipMemcpyAsync(out_host, t->x.dir.as<u32>() + first, (size_t)count * 4, hipMemcpyDeviceToHost, t->stream));
+    SA_HIP_CHECK(hipStreamSynchronize(t->stream));
+    return 0;
+}
+
+int sa_hip_token_index_get_key_range(sa_hip_token_index* t, uint64_t first, uint64_t count, uint64_t* out_host) {
+    const char* who = "sa_hip_token_index_get_key_range";
+    if (!t || !out_host) return fail(SA_HIP_EINVAL, who, "NULL argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    if (!t->x.key_bytes) return fail(SA_HIP_EINVAL, who, "the handle has no key array");
+    if (first > t->x.n || count > t->x.n - first) return fail(SA_HIP_EINVAL, who, "range beyond the key array");
+    if (count == 0) return 0;
+    int rc = set_device(t->device);
+    if (rc) return rc;
+    SA_HIP_CHECK(hipMemcpyAsync(out_host, t->x.keys.as<u64>() + first, (size_t)count * 8, hipMemcpyDeviceToHost, t->stream));
+    SA_HIP_CHECK(hipStreamSynchronize(t->stream));
+    return 0;
+}
+
 int sa_hip_token_index_info(const sa_hip_token_index* ct, sa_hip_token_info* out) {
     if (!ct || !out) return fail(SA_HIP_EINVAL, "sa_hip_token_index_info", "NULL argument");
     sa_hip_token_index* t = const_cast<sa_hip_token_index*>(ct);
